@@ -11,9 +11,20 @@ d=32, MF batch 1024, TR batch 256, multi_num 10).  Inputs (every epoch's triples
 validation rows, tables) are resident in HBM before the timed region.
 
 Prints ONE JSON line on rank 0.  `value` = training triples (MF + TR stage) per second,
-whole job.  Extra objects: `roofline` for the kernel that dominates GPU time (measured
-with HIP events inside this process) and `cpu_baseline` (the CPU oracle timed on a
-bounded sample of the same workload, N=1 only).
+whole job; `ms_per_step` = milliseconds per timed step.  A plain run sets up, warms up,
+times the steps and prints that line, nothing else.  `--full` adds the legs that take runs
+of their own: `roofline` / `kernels` for the kernel that dominates GPU time (one more
+period with HIP events inside this process), `strong_scaling` (N > 1), `a3` (the bare
+embed+loss+SGD step at table scale) and `cpu_baseline` (the CPU oracle timed on a bounded
+sample of the same workload, N=1 only); `--no-cpu` / `--no-roofline` / `--no-a3` drop
+single legs of a full run.
+
+`--dump-outputs DIR` writes what the last timed step computed, as rank 0's caller would
+receive it (losses of the last MF / TR epoch, the user and item tables after the period's
+final updata, the transfer net's parameters; `--workload bare`: the last epoch's losses
+and the tables), as DIR/<name>.npy in float32, at most 64 MB in all: a table too large for
+that is written as a fixed, seeded sample of its rows.  Inputs are seeded: the same
+arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -77,6 +88,11 @@ def parse():
     ap.add_argument("--neg", type=int, default=999)
     ap.add_argument("--multi_num", type=int, default=10)
     ap.add_argument("--no-val", action="store_true", help="skip the validation evaluations (not the reference default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the roofline / per-kernel object (one more profiled period), the strong-scaling "
+                         "leg (N > 1), the a3 table-scale legs and the CPU baseline (N = 1); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-a3", action="store_true", help="skip the a3 (bare fused embed+loss+SGD) table-scale leg")
@@ -106,6 +122,28 @@ def parse():
     ap.add_argument("--one-device", action="store_true",
                     help="test mode for a 1-GPU box: all N rank processes share device 0 (gloo carries torch.distributed)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 60 * 10 ** 6       # under the 64 MB --dump-outputs promises, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: arrays = [(name, tensor or None)] -> out_dir/<name>.npy in float32 (float64 stays float64).
+    When the whole set exceeds DUMP_BYTES, every array of two or more dimensions keeps the same share of its rows: a
+    sample drawn with a fixed seed (sorted row indices), so that two runs with the same arguments write the same rows."""
+    arrays = [(n, t.detach()) for n, t in arrays if t is not None]
+    size = lambda t: t.numel() * (8 if t.dtype == torch.float64 else 4)
+    big = sum(size(t) for _, t in arrays if t.dim() >= 2)
+    small = sum(size(t) for _, t in arrays if t.dim() < 2)
+    frac = 1.0 if small + big <= DUMP_BYTES else max(DUMP_BYTES - small, 0) / float(big)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays:
+        if t.dim() >= 2 and frac < 1.0:
+            k = max(1, int(t.shape[0] * frac))
+            rows = np.sort(np.random.RandomState(0).choice(t.shape[0], k, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu()
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
 
 
 def zipf_head_rows(n_item, zipf_a, occ_per_batch, d, net_size):
@@ -164,13 +202,17 @@ def bench_bare_sharded(a, device, dist):
         eng.bare_epoch_sharded(wu, tri, a.bare_batch, 0.05, 1e-6, 1e-6, sh, bce=True)
     barrier()
     t0 = time.perf_counter()
+    loss = None
     for _ in range(a.steps):
-        eng.bare_epoch_sharded(wu, tri, a.bare_batch, 0.05, 1e-6, 1e-6, sh, bce=True)
+        loss = eng.bare_epoch_sharded(wu, tri, a.bare_batch, 0.05, 1e-6, 1e-6, sh, bce=True)
     barrier()
     dtm = time.perf_counter() - t0
     tt = torch.tensor([dtm], device=device, dtype=torch.float64)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dtm = float(tt.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, [("loss", loss), ("user_emb", wu), ("item_emb_head", w_head if H > 0 else None),
+                                      ("item_emb_shard", shard)])
     eng.profile(True)
     eng.bare_epoch_sharded(wu, tri, a.bare_batch, 0.05, 1e-6, 1e-6, sh, bce=True)
     torch.cuda.synchronize(device)
@@ -249,15 +291,18 @@ def bench_bare(a, device, dist=None):
     nxt = eng.bare_prepare(tri, a.bare_batch, users_local, a.items, exchange=ex)
     barrier()
     t0 = time.perf_counter()
+    loss = None
     for _ in range(a.steps):
         cur, nxt = nxt, eng.bare_prepare(tri, a.bare_batch, users_local, a.items, exchange=ex)
-        eng.bare_epoch(wu, wi, tri, a.bare_batch, 0.05, 1e-6, 1e-6, bce=True, prepared=cur)
+        loss = eng.bare_epoch(wu, wi, tri, a.bare_batch, 0.05, 1e-6, 1e-6, bce=True, prepared=cur)
     barrier()
     dtm = time.perf_counter() - t0
     if dist is not None:
         tt = torch.tensor([dtm], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dtm = float(tt.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, [("loss", loss), ("user_emb", wu), ("item_emb", wi)])
     # the index preparation alone (nothing else on the chip): its own time and rate
     barrier()
     tp0 = time.perf_counter()
@@ -428,6 +473,7 @@ def a3_object(a, device):
         # (an epoch is about a millisecond: 4 untimed + 16 timed epochs per configuration -- the first epochs after the
         # tables are allocated run up to 25 % slower than the steady state)
         b.bare_batch, b.bare_triples, b.steps, b.warmup = 262144, 1 << 22, 16, 4
+        b.dump_outputs = None          # (the headline's outputs, not a leg's)
         try:
             r = bench_bare(b, device)
             res[tag] = {"users": users, "items": items, "d": d, "dtype": dt, "item_zipf": zipf, "batch": b.bare_batch,
@@ -784,9 +830,10 @@ def main():
     gc.freeze()
     barrier()
     t0 = time.perf_counter()
+    last = (None, None)
     with engine.partition():
         for s in range(a.steps):
-            run_period(engine, st, plans[(a.warmup + s) % len(plans)], hp, overlap=not a.no_overlap, exchanges=exchanges)
+            last = run_period(engine, st, plans[(a.warmup + s) % len(plans)], hp, overlap=not a.no_overlap, exchanges=exchanges)
     barrier()
     dt = time.perf_counter() - t0
     engine.side_sync_check()          # the periods dropped their evaluation results: an unordered evaluation still fails the run
@@ -799,6 +846,11 @@ def main():
         dctx.check_exchange(engine, "bench (%s scaling)" % a.scaling, replicas=replicas())
         peer_timeouts = int(engine.peer_status()) if dctx.mode == "peer" else 0
     value = a.steps * triples_per_period / dt
+    if a.dump_outputs and rank == 0:
+        # (before the --full legs: the roofline period trains the same state further)
+        dump_outputs(a.dump_outputs, [("mf_loss", last[0]), ("tr_loss", last[1]),
+                                      ("user_emb", st.MFbase.user_laten.weight), ("item_emb", st.MFbase.item_laten.weight)]
+                     + [("transfer." + k, v) for k, v in st.transfer.state_dict().items()])
 
     carriers = {"peer": "one-shot exchange over peer mappings (hipIpc, no collective library on the data path)",
                 "rccl": "native RCCL exchange", "torch": "torch.distributed hooks"}
@@ -824,11 +876,11 @@ def main():
     if dist is not None:
         out["config"].update({"carrier": dctx.mode, "carrier_wanted": getattr(dctx, "wanted", None), "peer_timeouts": peer_timeouts,
                               "replicas_bit_identical": True, "ranks_share_one_device": launch.one_device()})
-        if not strong and not a.no_roofline and os.environ.get("SML_BENCH_STRONG_LEG", "1") != "0":
+        if a.full and not strong and not a.no_roofline and os.environ.get("SML_BENCH_STRONG_LEG", "1") != "0":
             # the strong-scaling leg beside the weak one: ONE period (the same on every rank), reference batches split by owner
             out["strong_scaling"] = strong_leg(a, hp, engine, dctx, dist, device, world, rank)
 
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         engine.profile(True)
         with engine.partition():
             run_period(engine, st, plans[0], hp, overlap=not a.no_overlap, exchanges=exchanges)
@@ -878,7 +930,7 @@ def main():
                                    "avg_launch_us_rocprof": rp_us, "rocprof_profile": rp_file,
                                    "frac_rocprof": ((per_launch / (rp_us * 1e-6) / (1e9 if bound == "hbm" else 1e12)) / peak) if rp_us else None}
             out["kernels"] = kern
-    if not a.no_a3:
+    if a.full and not a.no_a3:
         del plans, st, exchanges
         torch.cuda.empty_cache()
         if world == 1 and dist is None:
@@ -889,7 +941,7 @@ def main():
             if dctx.mode == "peer":
                 engine.peer_detach()
             out["a3"] = a3_object_sharded(a, device, dist)
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         out["cpu_baseline"] = cpu_baseline(a, hp)
     if rank == 0:
         quiet.emit(json.dumps(out))
@@ -944,6 +996,7 @@ def a3_object_sharded(a, device, dist):
         b = copy.copy(a)
         b.users, b.items, b.d, b.bare_dtype, b.item_zipf = users, items, d, dt, zipf
         b.bare_batch, b.bare_triples, b.steps, b.warmup = 262144, 1 << 22, 8, 2
+        b.dump_outputs = None
         err = None
         try:
             r = bench_bare_sharded(b, device, dist)

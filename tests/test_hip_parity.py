@@ -2435,7 +2435,7 @@ def test_bench_gpus_2_starts_its_own_ranks_and_prints_one_valid_line():
     0, gloo carrying torch.distributed -- which run the period workload over the one-shot peer exchange through hipIpc
     mappings, verify after the timed loop that no consumer timed out and that theta / the item table are bit-identical on
     both ranks, add the strong-scaling leg (reference batches split by user owner), and rank 0 prints the line."""
-    out = _run_bench(["--gpus", "2", "--one-device", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-a3", "--users", "6000", "--items", "12300",
+    out = _run_bench(["--gpus", "2", "--one-device", "--full", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-a3", "--users", "6000", "--items", "12300",
                       "--inter", "7500", "--neg", "99", "--multi_num", "2"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     cfg = out["config"]
@@ -2444,6 +2444,20 @@ def test_bench_gpus_2_starts_its_own_ranks_and_prints_one_valid_line():
     st = out["strong_scaling"]
     assert st["scaling"] == "strong" and st["carrier"] == "peer" and st["peer_timeouts"] == 0 and st["triples_per_s"] > 0
     assert st["global_batches"] == [1024, 256]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run is the headline alone (no --full legs in the line) over exactly --steps timed periods, and
+    --dump-outputs writes the last timed period's losses, tables and transfer parameters as float32 .npy files."""
+    out = _run_bench(["--steps", "2", "--warmup", "1", "--users", "6000", "--items", "12300", "--inter", "7500", "--neg", "99",
+                      "--multi_num", "2", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert not {"roofline", "kernels", "a3", "cpu_baseline", "strong_scaling"} & set(out)
+    z = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert z["user_emb"].shape == (6000, 32) and z["item_emb"].shape == (12300, 32)
+    assert z["mf_loss"].shape == (8,) and z["tr_loss"].shape == (30,)          # ceil(7500 / 1024), ceil(7500 / 256) batches
+    assert any(k.startswith("transfer.") for k in z)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in z.values())
 
 
 @pytest.mark.parametrize("n", [2, 4])

@@ -908,3 +908,32 @@ def test_zipf_head_rows_of_the_sharded_bare_step():
     assert 0 < h <= 2 * 197000 // 64 and h % 4 == 0                                # capped by the dense partial's slot
     small = bench.zipf_head_rows(1000000, 1.0, 2 * 4096, 32, 98943)
     assert 0 < small < 100                                                         # few rows reach 16 occurrences of 8,192
+
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_under_64_mb(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, whole when they fit, otherwise the same seeded rows of every table in
+    every run, and never more than 64 MB in all."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_dump", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    loss, wu, wi = torch.rand(16, generator=g), torch.rand(1000000, 32, generator=g), torch.rand(300000, 32, generator=g).half()
+    small = tmp_path / "small"
+    bench.dump_outputs(str(small), [("loss", loss), ("absent", None), ("item_emb", wi[:1000])])
+    assert sorted(os.listdir(str(small))) == ["item_emb.npy", "loss.npy"]
+    np.testing.assert_array_equal(np.load(str(small / "item_emb.npy")), wi[:1000].float().numpy())
+    runs = []
+    for r in range(2):
+        d = tmp_path / ("big%d" % r)
+        bench.dump_outputs(str(d), [("loss", loss), ("user_emb", wu), ("item_emb", wi)])
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) <= 64 * 10 ** 6
+        runs.append({f: np.load(str(d / f)) for f in os.listdir(str(d))})
+    assert all(v.dtype == np.float32 for v in runs[0].values())
+    assert 0 < runs[0]["user_emb.npy"].shape[0] < wu.shape[0] and 0 < runs[0]["item_emb.npy"].shape[0] < wi.shape[0]
+    np.testing.assert_array_equal(runs[0]["loss.npy"], loss.numpy())
+    for f in runs[0]:
+        np.testing.assert_array_equal(runs[0][f], runs[1][f])
+    where = {r.tobytes(): k for k, r in enumerate(wu.numpy())}
+    rows = [where[r.tobytes()] for r in runs[0]["user_emb.npy"]]          # (KeyError: not a row of the table)
+    assert all(a < b for a, b in zip(rows, rows[1:]))                      # distinct rows, in table order

@@ -10,7 +10,7 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
-PERIOD="bench.py --no-cpu --no-a3 --steps 4 --warmup 2"      # (the step counter passes 1,024 -- closed-form replay -- in the second period)
+PERIOD="bench.py --full --no-cpu --no-a3 --steps 4 --warmup 2"      # (the step counter passes 1,024 -- closed-form replay -- in the second period)
 BARE="bench.py --workload bare --users 10000000 --items 1000000 --bare-batch 262144 --steps 2 --warmup 1"
 run() { # name, rocprof args..., -- cmd
     local name=$1; shift
