@@ -422,6 +422,31 @@ int sml_flag_wait(int32_t* flag, int value, double timeout_s, void* stream);
 /* hits = #{rank < topk}, ndcg = sum 1/log2(rank+2) over hits; out[0]=hits, out[1]=ndcg (device). */
 int sml_eval_metrics(sml_ctx* ctx, const int32_t* rank, int64_t n, int topk, float* out, void* stream);
 
+/* ---- full-catalogue retrieval ------------------------------------------------------ */
+/* S(u, i) = <w_user[u], w_item[i]> in fp32 (no bias terms, as MFbasemode.test scores), one fmaf chain over the d
+ * dims in a fixed order shared by both entry points: the two score every (u, i) to the same float, bit for bit.
+ * d (the ctx's) must be 32 or 64; 0 < n_item < 2^31.  Seen(u), the items excluded for user u, is a CSR over users:
+ * seen_off int64 [n_user + 1], seen_items int32 ascending and unique inside each user's range; both NULL = nothing
+ * excluded, exactly one NULL is refused.  Exclusion is by item id, never by score.  Indices are trusted.
+ *
+ * sml_full_rank: rows int64 [n, n_cols >= 2] (col 0 user u, col 1 positive p, further columns ignored);
+ *   rank[r] = #{i in [0, n_item): i != p, i not in Seen(u), S(u,i) > S(u,p)} -- strictly greater, IEEE (a NaN is never
+ *   above, a NaN positive gets rank 0); p itself is never excluded.  The ranks feed sml_eval_metrics unchanged. */
+int sml_full_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item,
+                  const int64_t* rows, int64_t n, int n_cols,
+                  const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, void* stream);
+/* Bytes of `scratch` sml_topk_items needs for n users at this k (1 <= k <= 128) and n_item (16-byte aligned base;
+ * contents not needed afterwards).  It grows linearly in n: callers with many users go in chunks.  < 0: bad argument. */
+int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item);
+/* sml_topk_items: for users int64 [n], items int32 [n, k] and scores float [n, k] = the k eligible items (not in
+ * Seen(u), score not NaN) in order of score descending, then item id ascending; slots past the eligible count hold
+ * item -1 and score -inf.  Deterministic (the same bytes whatever the schedule).  With the same Seen, the positive of
+ * a row (u, p) sits at position rank + #{eligible i != p : S(u,i) == S(u,p), i < p} of u's list whenever that is < k. */
+int sml_topk_items(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item,
+                   const int64_t* users, int64_t n, int k,
+                   const int64_t* seen_off, const int32_t* seen_items,
+                   void* scratch, int32_t* items, float* scores, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------ */
 /* Optional HIP-event timing of every kernel launch on the caller's stream, by kernel class
  * (bench.py's roofline leg).  Off by default; when on, each launch is bracketed by two

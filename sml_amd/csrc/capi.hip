@@ -1681,6 +1681,44 @@ int sml_eval_metrics(sml_ctx* ctx, const int32_t* rank, int64_t n, int topk, flo
     return SML_OK;
 }
 
+// ---- full-catalogue retrieval (retrieval.hip) ----------------------------------------------------------------------
+static bool retrieval_args_ok(sml_ctx* ctx, int64_t n_item, const int64_t* seen_off, const int32_t* seen_items) {
+    return ctx && (ctx->d == 32 || ctx->d == 64) && n_item > 0 && n_item < ((int64_t)1 << 31) && (!seen_off) == (!seen_items);
+}
+
+int sml_full_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* rows, int64_t n,
+                  int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, void* stream) {
+    if (!retrieval_args_ok(ctx, n_item, seen_off, seen_items) || n_cols < 2 || n < 0)
+        return fail(SML_EINVAL, "sml_full_rank", "bad argument (d must be 32/64, 0 < n_item < 2^31, n_cols >= 2, seen_off and seen_items both or neither)");
+    if (n == 0) return SML_OK;
+    if (!w_user || !w_item || !rows || !rank) return fail(SML_EINVAL, "sml_full_rank", "null argument");
+    DevGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    ctx->prof.begin(PC_MISC, st);
+    HIPCHK(sml_launch_full_rank(ctx->d, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, st));
+    ctx->prof.end(st);
+    return SML_OK;
+}
+
+int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item) {
+    if (!ctx || n < 0 || k < 1 || k > 128 || n_item <= 0 || n_item >= ((int64_t)1 << 31)) return fail(SML_EINVAL, "sml_topk_scratch_bytes", "bad argument");
+    return n == 0 ? 0 : sml_topk_scratch_size(n, k, n_item);
+}
+
+int sml_topk_items(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
+                   const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores, void* stream) {
+    if (!retrieval_args_ok(ctx, n_item, seen_off, seen_items) || k < 1 || k > 128 || n < 0)
+        return fail(SML_EINVAL, "sml_topk_items", "bad argument (d must be 32/64, 1 <= k <= 128, 0 < n_item < 2^31, seen_off and seen_items both or neither)");
+    if (n == 0) return SML_OK;
+    if (!w_user || !w_item || !users || !scratch || !items || !scores) return fail(SML_EINVAL, "sml_topk_items", "null argument");
+    DevGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    ctx->prof.begin(PC_MISC, st);
+    HIPCHK(sml_launch_topk(ctx->d, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, st));
+    ctx->prof.end(st);
+    return SML_OK;
+}
+
 int sml_comm_load(const char* path) {
     if (g_rccl.ok()) return SML_OK;
     if (!path) return fail(SML_EINVAL, "sml_comm_load", "null path");

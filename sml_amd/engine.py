@@ -661,6 +661,57 @@ class HipEngine(object):
                   "sml_eval_ranks")
         return rank
 
+    # ---- full-catalogue retrieval (retrieval.hip) ----
+    TOPK_SCRATCH_BYTES = 256 << 20       # users of one sml_topk_items call are capped so its candidate scratch fits this
+
+    def _seen(self, seen):
+        if seen is None:
+            return None, None
+        off, items = seen
+        off, items = self._dev(off, torch.int64), self._dev(items, torch.int32)
+        if items.numel() == 0:           # an empty Seen still passes BOTH arrays (torch gives an empty tensor a null pointer)
+            items = torch.zeros(1, device=self.device, dtype=torch.int32)
+        return off, items
+
+    def full_rank(self, user_tab, item_tab, rows, seen=None):
+        """int32 [n]: per row (u, p, ...) the number of items i != p, not in Seen(u), scoring strictly above p over the
+        WHOLE item table (include/sml_hip.h, sml_full_rank).  seen = (seen_off int64 [n_user + 1], seen_items int32)."""
+        wu, wi = self._table(user_tab), self._table(item_tab)
+        rows = self._dev(rows, torch.int64)
+        n, c = rows.shape
+        rank = torch.empty(n, device=self.device, dtype=torch.int32)
+        if n == 0:
+            return rank
+        off, items = self._seen(seen)
+        check(self.lib.sml_full_rank(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(rows), n, c, _ptr(off), _ptr(items),
+                                     _ptr(rank), self._stream()), "sml_full_rank")
+        return rank
+
+    def topk_items(self, user_tab, item_tab, users, k, seen=None):
+        """(int64 items [n, k], float32 scores [n, k]): each user's k best items not in Seen(u), score descending then id
+        ascending; missing slots are (-1, -inf) (include/sml_hip.h, sml_topk_items)."""
+        wu, wi = self._table(user_tab), self._table(item_tab)
+        users = self._dev(users, torch.int64).reshape(-1)
+        n, k = users.shape[0], int(k)
+        off, seen_items = self._seen(seen)
+        total = int(self.lib.sml_topk_scratch_bytes(self._ctx, n, k, wi.shape[0]))
+        if total < 0 or n == 0:          # argument checks (k, n_item) and the empty call go through the library
+            check(self.lib.sml_topk_items(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users), 0, k, _ptr(off),
+                                          _ptr(seen_items), None, None, None, self._stream()), "sml_topk_items")
+        items = torch.empty(n, k, device=self.device, dtype=torch.int32)
+        scores = torch.empty(n, k, device=self.device, dtype=torch.float32)
+        chunk = n if total <= self.TOPK_SCRATCH_BYTES else max(1, int(n * self.TOPK_SCRATCH_BYTES // total))
+        scratch = None
+        for c0 in range(0, n, chunk):
+            m = min(chunk, n - c0)
+            nbytes = int(self.lib.sml_topk_scratch_bytes(self._ctx, m, k, wi.shape[0]))
+            if scratch is None or scratch.numel() < nbytes:
+                scratch = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+            check(self.lib.sml_topk_items(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, k, _ptr(off),
+                                          _ptr(seen_items), _ptr(scratch), _ptr(items[c0:]), _ptr(scores[c0:]), self._stream()),
+                  "sml_topk_items")
+        return items.long(), scores
+
     # Evaluations never sit on the training stream.  eval_submit copies the two tables into a snapshot (one copy
     # kernel, a few tens of MB) on the CURRENT stream and queues the rank pass over the snapshot on the engine's side
     # stream; the training kernels that follow on the current stream -- which may overwrite the tables at once -- do

@@ -54,3 +54,29 @@ def test_model(model, test_set, old_user=None, old_item=None, topK=10, need_pbar
         ndcg += float(batch_ndcg)
         num_test += datas.shape[0]
     return hits / num_test, torch.tensor(np.float32(ndcg / num_test))
+
+
+def test_model_full(model, test_set, seen=None, topK=10):
+    """(recall@topK, ndcg@topK) as test_model returns them, with every positive ranked against the whole catalogue
+    (MFbasemode.test_full), leaving out `seen` (a sml_amd.retrieval.SeenItems or a (seen_off, seen_items) CSR).
+    test_set: a DeviceRows, an array / tensor [n, >= 2], or an iterable of such batches.  Unlike test_model this
+    makes no DataLoader-emulating RNG draw: the run's random streams stay where they were."""
+    model.eval()
+    device = model.user_laten.weight.device
+    if isinstance(test_set, DeviceRows):
+        test_set.wait_ready()
+        batches = [test_set.rows]
+    elif isinstance(test_set, (np.ndarray, torch.Tensor)):
+        batches = [test_set]
+    else:
+        batches = test_set
+    num_test = 0
+    hits = 0.0
+    ndcg = 0.0
+    for datas in batches:
+        datas = torch.as_tensor(datas).long().to(device)
+        batch_hit, batch_ndcg, _ = model.test_full(datas, topK=topK, exclude=seen)
+        hits += batch_hit
+        ndcg += float(batch_ndcg)
+        num_test += datas.shape[0]
+    return hits / num_test, torch.tensor(np.float32(ndcg / num_test))

@@ -69,6 +69,28 @@ class MFbasemode(nn.Module):
         hit_rows = (ranks < topK).nonzero()[:, 0]
         return hit_rows, ranks, hits * 1.0, (torch.tensor(ndcg) if hits > 0 else 0)
 
+    def recommend(self, users, topK=20, exclude=None):
+        """(items int64 [n, topK], scores float32 [n, topK]): each user's topK items over the whole catalogue by the score
+        test() uses (no bias terms), score descending then item id ascending, leaving out `exclude` (a
+        sml_amd.retrieval.SeenItems or a (seen_off, seen_items) CSR); missing slots are (-1, -inf)."""
+        from .retrieval import as_csr
+        eng = _engine_for(self)
+        w = self.user_laten.weight
+        return eng.topk_items(w.data, self.item_laten.weight.data, users, topK, as_csr(exclude, w.device))
+
+    def test_full(self, inputs_data, topK=20, exclude=None):
+        """test() with the positive ranked against the WHOLE catalogue: inputs_data [n, >= 2] (user, positive, ... --
+        further columns are ignored), rank = #{items != positive, not excluded, scoring strictly above it}.
+        Returns (hits, ndcg_sum, indices of the rows that hit)."""
+        from .retrieval import as_csr
+        eng = _engine_for(self)
+        w = self.user_laten.weight
+        ranks = eng.full_rank(w.data, self.item_laten.weight.data, inputs_data, as_csr(exclude, w.device))
+        hits, ndcg = eng.eval_metrics(ranks, topK)
+        hit_rows = (ranks < topK).nonzero()[:, 0]
+        batch_ndcg = torch.tensor(ndcg) if hits > 0 else 0
+        return hits * 1.0, batch_ndcg, hit_rows
+
     def set_parameters(self, user_weight, item_weight):
         # last column is the bias (model/MF.py:108-112)
         self.user_laten.weight.data.copy_(user_weight[:, 0:-1])

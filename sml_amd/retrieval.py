@@ -1,0 +1,81 @@
+"""Full-catalogue retrieval helpers: the Seen-items exclusion set of sml_full_rank / sml_topk_items.
+
+SeenItems keeps, per user, the items to leave out of recommendations and full-catalogue ranks (typically everything
+the user interacted with in earlier periods) as a CSR over users:
+
+    seen_off    int64 [n_user + 1]
+    seen_items  int32, ascending and unique inside each user's range [seen_off[u], seen_off[u + 1])
+
+It is built on the host with numpy (a unique over the key u * n_item + i) and touches no random number generator.
+"""
+import os
+
+import numpy as np
+import torch
+
+
+class SeenItems(object):
+    def __init__(self, n_user, n_item):
+        self.n_user, self.n_item = int(n_user), int(n_item)
+        self._keys = np.zeros(0, dtype=np.int64)     # sorted unique u * n_item + i
+        self._host = None
+        self._dev = {}
+
+    def add(self, pairs):
+        """Union in an int array [m, 2] of (user, item); duplicates are allowed."""
+        pairs = np.asarray(pairs)
+        if pairs.size == 0:
+            return self
+        if pairs.ndim != 2 or pairs.shape[1] < 2:
+            raise ValueError("expected (user, item) pairs [m, 2], got shape %s" % (pairs.shape,))
+        u, i = pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64)
+        if u.min() < 0 or u.max() >= self.n_user or i.min() < 0 or i.max() >= self.n_item:
+            raise ValueError("pair out of range (n_user=%d, n_item=%d)" % (self.n_user, self.n_item))
+        self._keys = np.union1d(self._keys, u * self.n_item + i)
+        self._host = None
+        self._dev = {}
+        return self
+
+    def host(self):
+        """(seen_off int64 [n_user + 1], seen_items int32) numpy arrays."""
+        if self._host is None:
+            u = self._keys // self.n_item
+            off = np.zeros(self.n_user + 1, dtype=np.int64)
+            np.cumsum(np.bincount(u, minlength=self.n_user), out=off[1:])
+            self._host = (off, (self._keys - u * self.n_item).astype(np.int32))
+        return self._host
+
+    def device(self, device):
+        """The cached (seen_off, seen_items) tensors on `device`; rebuilt only after an add."""
+        key = str(torch.device(device))
+        if key not in self._dev:
+            off, items = self.host()
+            self._dev[key] = (torch.from_numpy(off).to(device), torch.from_numpy(items).to(device))
+        return self._dev[key]
+
+    def __len__(self):
+        return int(self._keys.shape[0])
+
+    @classmethod
+    def from_periods(cls, root, name, periods, n_user=None, n_item=None):
+        """Union of the train/<p>.npy pairs of dataset root/name (the format sml_amd/synth.py documents) over `periods`.
+        n_user / n_item default to the dataset's information.npy."""
+        base = os.path.join(root, name)
+        if n_user is None or n_item is None:
+            info = np.load(os.path.join(base, "information.npy"))
+            n_user = int(info[1]) if n_user is None else n_user
+            n_item = int(info[2]) if n_item is None else n_item
+        seen = cls(n_user, n_item)
+        for p in periods:
+            seen.add(np.load(os.path.join(base, "train", "%d.npy" % p))[:, :2])
+        return seen
+
+
+def as_csr(exclude, device):
+    """exclude: None, a SeenItems, or a (seen_off, seen_items) pair -> what the engine's retrieval calls take."""
+    if exclude is None:
+        return None
+    if isinstance(exclude, SeenItems):
+        return exclude.device(device)
+    off, items = exclude
+    return torch.as_tensor(off), torch.as_tensor(items)
