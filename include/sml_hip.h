@@ -425,6 +425,9 @@ int sml_eval_metrics(sml_ctx* ctx, const int32_t* rank, int64_t n, int topk, flo
 /* ---- full-catalogue retrieval ------------------------------------------------------ */
 /* S(u, i) = <w_user[u], w_item[i]> in fp32 (no bias terms, as MFbasemode.test scores), one fmaf chain over the d
  * dims in a fixed order shared by both entry points: the two score every (u, i) to the same float, bit for bit.
+ * The order pairs dim s with dim s + d/2: acc = 0; for s = 0 .. d/2 - 1 { acc = fmaf(x[s], u[s], acc);
+ * acc = fmaf(x[s + d/2], u[s + d/2], acc); } with u = w_user[u], x = w_item[i], each fmaf rounded once (round to
+ * nearest even, subnormals kept).
  * d (the ctx's) must be 32 or 64; 0 < n_item < 2^31.  Seen(u), the items excluded for user u, is a CSR over users:
  * seen_off int64 [n_user + 1], seen_items int32 ascending and unique inside each user's range; both NULL = nothing
  * excluded, exactly one NULL is refused.  Exclusion is by item id, never by score.  Indices are trusted.

@@ -5,7 +5,9 @@
 // one user column (lane & 31) and 16 item scores (rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5), r = 0..15), so every
 // per-user test is a per-lane compare.  Lane half h carries dims [h D/2, (h+1) D/2) of its row (contiguous 16-byte
 // loads); MFMA step s therefore feeds dim s (k0) and then dim s + D/2 (k1), and the score of (u, i) is the fmaf chain
-// score_chain() spells out on the VALU -- the positive's score in rank mode is computed that way, bit-identical.
+// score_chain() spells out on the VALU -- the positive's score in rank mode is computed that way, bit-identical.  That
+// order (dims 0, D/2, 1, D/2 + 1, ..., each fmaf rounded once, subnormals kept) is part of the contract in sml_hip.h;
+// tests/test_retrieval_gpu.py compares ranks, lists and score bits with an exact emulation of it.
 //
 // Grid: (32 * W users) x slices; slice = blockIdx % slices, so with slices a multiple of 8 an XCD walks 1/8 of the
 // item table.  Every wave owns 32 users and walks its slice tile by tile (32 items), loading the next tile's item rows

@@ -306,3 +306,242 @@ def test_yelp_scale():
     assert recall == pytest.approx(float((full < 10).sum()) / 10000)
     want_ndcg = float((1.0 / np.log2(full[full < 10] + 2.0)).sum()) / 10000
     assert float(ndcg) == pytest.approx(want_ndcg, rel=1e-5)
+
+
+# ---- exact comparisons against the fp32 chain of the kernels (tests/_fp32_chain.py) ---------------------------------
+# Every score is the fmaf chain in the kernels' k order, emulated exactly; ranks, item lists and score BYTES must equal
+# the reference.  test_retrieval_host.py::test_exact_tests_have_teeth shows the same data tells other orders apart.
+
+def csr_dev(seen):
+    return None if seen is None else (gpu(seen[0]), gpu(seen[1]))
+
+
+def check_exact(eng, wu, wi, rows=None, users=None, ks=(), seen=None, ref_device="cpu", chunk=1 << 16):
+    """ranks of `rows` and the top-k lists of `users` for every k in ks, exactly as the fp32-chain reference has them.
+    wu / wi: numpy arrays or device tensors."""
+    import _fp32_chain as F
+    tu = wu if torch.is_tensor(wu) else gpu(wu)
+    ti = wi if torch.is_tensor(wi) else gpu(wi)
+    csr = csr_dev(seen)
+    if rows is not None:
+        got = eng.full_rank(tu, ti, gpu(rows), csr).cpu().numpy()
+        want = F.ref_full_rank(wu, wi, rows, seen, device=ref_device, chunk=chunk)
+        bad = np.nonzero(got != want)[0]
+        assert len(bad) == 0, ("rank", len(bad), bad[:8], got[bad[:8]], want[bad[:8]])
+    if ks:
+        want_i, want_s = F.ref_topk(wu, wi, users, max(ks), seen, device=ref_device, chunk=chunk)
+        for k in ks:
+            items, scores = eng.topk_items(tu, ti, gpu(users), k, csr)
+            items, scores = items.cpu().numpy(), scores.cpu().numpy()
+            wi_k, ws_k = want_i[:, :k], np.ascontiguousarray(want_s[:, :k])
+            bad = np.nonzero((items != wi_k).any(1) | (scores.view(np.int32) != ws_k.view(np.int32)).any(1))[0]
+            assert len(bad) == 0, ("topk", k, len(bad), bad[:4], items[bad[:1]], wi_k[bad[:1]])
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_exact_on_random_floats(d):
+    import _fp32_chain as F
+    c = F.random_case(d, seed=800 + d)
+    check_exact(engine(d), c["wu"], c["wi"], c["rows"], c["users"], (1, 20, 128), c["seen"])
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_exact_on_planted_near_ties(d):
+    """Exact copies, +-1 ulp copies and rounding-only copies of the positives; k-th entries copied across slices; users
+    whose scores are all subnormal (a flushing path would tie them all)."""
+    import _fp32_chain as F
+    c = F.near_tie_case(d)
+    check_exact(engine(d), c["wu"], c["wi"], c["rows"], c["users"], (1, 20, 128), c["seen"])
+
+
+def _sweep_users(rng, U, n):
+    """n user ids, unsorted, with duplicates."""
+    users = rng.randint(0, U, size=n)
+    if n > 2:
+        users[n // 2] = users[0]
+        users[-1] = users[1]
+    return users
+
+
+def test_geometry_every_topk_wave_count():
+    """k in {1, 2, 63, 64, 65, 85, 86, 127, 128}: 4-, 3- and 2-wave blocks of k_topk_slice."""
+    import _fp32_chain as F
+    ks = (1, 2, 63, 64, 65, 85, 86, 127, 128)
+    assert {F.topk_waves(k) for k in ks} == {4, 3, 2}
+    c = F.random_case(32, seed=900, U=200, I=3001)
+    users = _sweep_users(c["rng"], 200, 200)
+    check_exact(engine(32), c["wu"], c["wi"], None, users, ks, c["seen"])
+
+
+@pytest.mark.parametrize("n", [1, 31, 33, 95, 97, 127, 129])
+def test_geometry_user_counts(n):
+    """Partial waves and blocks: n around 32 (a wave), 96 (a 3-wave block) and 128 (a 4-wave block); duplicate and
+    unsorted users and rows."""
+    import _fp32_chain as F
+    c = F.random_case(32, seed=1000 + n, U=150, I=1500, n=n)
+    rng = c["rng"]
+    users = _sweep_users(rng, 150, n)
+    rows = c["rows"].copy()
+    rows[:, 0] = _sweep_users(rng, 150, n)
+    if n > 3:
+        rows[2] = rows[0]
+    check_exact(engine(32), c["wu"], c["wi"], rows, users, (20, 65, 128), c["seen"])
+
+
+@pytest.mark.parametrize("n_item", [1, 5, 31, 32, 33])
+@pytest.mark.parametrize("d", [32, 64])
+def test_geometry_small_catalogue(d, n_item):
+    """Catalogues of one tile or less (most slices empty), k above n_item, Seen covering all items / all but one."""
+    import _fp32_chain as F
+    rng = np.random.RandomState(1100 + n_item + d)
+    U = 40
+    wu = rng.randn(U, d).astype(np.float32)
+    wi = rng.randn(n_item, d).astype(np.float32)
+    lists = {0: range(n_item), 1: [i for i in range(n_item) if i != n_item // 2], 2: {0, n_item - 1},
+             3: {i for i in (31, 32) if i < n_item}}
+    seen = F.seen_csr(U, n_item, lists)
+    rows = np.stack([np.repeat(np.arange(U), 2)[:70], rng.randint(0, n_item, size=70)], 1).astype(np.int64)
+    check_exact(engine(d), wu, wi, rows, _sweep_users(rng, U, 40), (1, 2, 33, 128), seen)
+    items, _ = engine(d).topk_items(gpu(wu), gpu(wi), gpu(np.arange(4)), 128, csr_dev(seen))
+    items = items.cpu().numpy()
+    assert (items[0] == -1).all() and items[1, 0] == n_item // 2 and (items[1, 1:] == -1).all()
+
+
+def _slice_edges(slices, slice_tiles, n_item):
+    e = set()
+    for q in range(slices):
+        a, b = q * slice_tiles * 32, min((q + 1) * slice_tiles * 32, n_item)
+        if a < b:
+            e |= {a, b - 1}
+    return e
+
+
+@pytest.mark.parametrize("n_item,n_rows,n_users,empty_rank,empty_topk", [
+    (288, 100, 100, 3, 3),          # 9 tiles over 8 slices: the last 3 empty
+    (16411, 40, 3, 1, 1),           # 513 tiles, 32 slices (both kernels), the last one empty, the last tile partial
+    (262145, 100, 100, 30, 0),      # the rank kernel at its 512-slice maximum, 30 of them empty
+])
+def test_geometry_slices_and_seen_edges(n_item, n_rows, n_users, empty_rank, empty_topk):
+    """Empty trailing slices, Seen on items 0, 31, 32, n_item - 1 and on the first and last item of every slice, a user
+    whose Seen is a whole slice (its cand_n is 0 there), all items but one, and all items."""
+    import _fp32_chain as F
+    d = 32
+    rng = np.random.RandomState(1200 + n_item % 1000)
+    U = 120
+    rs, rst, rempty = F.rank_plan(n_rows, n_item)
+    tw, ts, tst, tempty = F.topk_plan(n_users, 20, n_item)
+    assert (rempty, tempty) == (empty_rank, empty_topk)
+    if n_item == 262145:
+        assert rs == 512
+    wu = rng.randn(U, d).astype(np.float32)
+    wi = rng.randn(n_item, d).astype(np.float32)
+    edges = {0, 31, 32, n_item - 1} | _slice_edges(rs, rst, n_item) | _slice_edges(ts, tst, n_item)
+    lists = {0: edges, 1: range(tst * 32, min(2 * tst * 32, n_item)), 2: range(rst * 32, min(2 * rst * 32, n_item)),
+             3: [i for i in range(n_item) if i != n_item - 2], 4: range(n_item)}
+    for u in range(5, U):
+        lists[u] = rng.choice(n_item, size=min(n_item // 4, 50), replace=False)
+    seen = F.seen_csr(U, n_item, lists)
+    # positives on and next to the edges, and inside the users' own Seen
+    pos = np.array(sorted(edges))
+    pos = rng.permutation(np.concatenate([pos, np.clip(pos + 1, 0, n_item - 1), rng.randint(0, n_item, size=n_rows)]))[:n_rows]
+    pos[0] = n_item - 1                     # user 0's positive, inside its own Seen
+    rows = np.stack([np.arange(n_rows) % U, pos], 1).astype(np.int64)
+    users = np.concatenate([np.arange(min(5, n_users)), rng.randint(0, U, size=max(0, n_users - 5))])
+    on_gpu = n_item > 100000
+    check_exact(engine(d), wu, wi, rows, users, (20, 128), seen, ref_device=DEV if on_gpu else "cpu")
+    items, scores = engine(d).topk_items(gpu(wu), gpu(wi), gpu(np.arange(5)), 20, csr_dev(seen))
+    items = items.cpu().numpy()
+    assert (items[4] == -1).all() and items[3, 0] == n_item - 2 and (items[3, 1:] == -1).all()
+    assert not (set(items[1].tolist()) & set(lists[1]))
+
+
+def test_item_table_above_2_to_the_31_bytes():
+    """d = 32, 2^24 + 4,099 items (2.15 GB): item rows and Seen past 2^31 bytes / 2^24 rows, near-ties planted at the far
+    end; 64 rank rows and the top-20 of 64 users, exact through the float64 filter (on the device)."""
+    import _fp32_chain as F
+    d, U, I = 32, 256, (1 << 24) + 4099
+    free, _ = torch.cuda.mem_get_info()
+    assert free > 12 * (1 << 30), free
+    g = torch.Generator(device=DEV)
+    g.manual_seed(1300)
+    ti = torch.randn(I, d, generator=g, device=DEV)
+    rng = np.random.RandomState(1300)
+    wu = rng.randn(U, d).astype(np.float32)
+    n = 64
+    far = (1 << 24) + rng.randint(0, 4099, size=n)
+    rows = np.stack([rng.randint(0, U, size=n), far], 1).astype(np.int64)
+    rows[: n // 2, 1] = rng.randint(0, I, size=n // 2)
+    # exact and one-ulp copies of some positives, far and near
+    src = torch.from_numpy(rows[:16, 1]).to(DEV)
+    dst_far = torch.from_numpy(I - 1 - np.arange(16)).to(DEV)
+    dst_near = torch.from_numpy(np.arange(16) * 1000 + 7).to(DEV)
+    ti[dst_far] = ti[src]
+    ti[dst_near] = torch.nextafter(ti[src], torch.full_like(ti[src], np.inf))
+    lists = {u: np.concatenate([[I - 1, I - 17, (1 << 24) + 3], rng.randint(0, I, size=20)]) for u in range(U)}
+    seen = F.seen_csr(U, I, lists)
+    users = rng.choice(U, size=64, replace=False)
+    check_exact(engine(d), gpu(wu), ti, rows, users, (20,), seen, ref_device=DEV, chunk=1 << 19)
+
+
+def test_chunked_topk_equals_one_call(monkeypatch):
+    """HipEngine.topk_items splits a call whose scratch exceeds TOPK_SCRATCH_BYTES: chunks of an odd user count (and a
+    ragged last chunk) give the same bytes as one call."""
+    import _fp32_chain as F
+    from sml_amd.engine import HipEngine
+    c = F.random_case(32, seed=1400, U=500, I=5000, n=300)
+    eng = engine(32)
+    tu, ti, csr = gpu(c["wu"]), gpu(c["wi"]), csr_dev(c["seen"])
+    users = _sweep_users(c["rng"], 500, 300)
+    k = 65
+    one_i, one_s = eng.topk_items(tu, ti, gpu(users), k, csr)
+    total = int(eng.lib.sml_topk_scratch_bytes(eng._ctx, len(users), k, c["wi"].shape[0]))
+    monkeypatch.setattr(HipEngine, "TOPK_SCRATCH_BYTES", -(-37 * total // len(users)))
+    calls = []
+    real = eng.lib.sml_topk_items
+
+    def counting(*a):
+        calls.append(a[5])
+        return real(*a)
+    monkeypatch.setattr(eng.lib, "sml_topk_items", counting)
+    ch_i, ch_s = eng.topk_items(tu, ti, gpu(users), k, csr)
+    assert calls[0] == 37 and len(calls) == 9 and sum(calls) == 300, calls
+    assert ch_i.cpu().numpy().tobytes() == one_i.cpu().numpy().tobytes()
+    assert ch_s.cpu().numpy().tobytes() == one_s.cpu().numpy().tobytes()
+    want_i, want_s = F.ref_topk(c["wu"], c["wi"], users, k, c["seen"])
+    np.testing.assert_array_equal(ch_i.cpu().numpy(), want_i)
+    assert ch_s.cpu().numpy().tobytes() == want_s.tobytes()
+
+
+def test_host_layers_against_exact_reference():
+    """evaluation.test_model_full over one array, a list of unequal batches and a DeviceRows; MFbasemode.recommend;
+    recall / NDCG against the oracle's metrics on the exact ranks."""
+    import _fp32_chain as F
+    from oracle.sml_oracle import eval_metrics
+    from sml_amd.evaluation import DeviceRows, test_model_full
+    from sml_amd.retrieval import SeenItems
+    c = F.near_tie_case(32, seed=5)
+    wu, wi, rows = c["wu"], c["wi"], c["rows"]
+    U, I = wu.shape[0], wi.shape[0]
+    off, its = c["seen"]
+    pairs = np.stack([np.repeat(np.arange(U), np.diff(off)), its], 1)
+    seen = SeenItems(U, I).add(pairs)
+    assert all((x == y).all() for x, y in zip(seen.host(), c["seen"]))
+    mf = make_mf(U, I, 32, wu, wi, device=DEV)
+    ranks = F.ref_full_rank(wu, wi, rows, c["seen"])
+    for topK in (1, 10, 100):
+        hits, ndcg = eval_metrics(torch.from_numpy(ranks), topK)
+        want_r, want_n = hits / len(rows), ndcg / len(rows)
+        cuts = [0, 1, 40, 41, 160, len(rows)]
+        batches = [rows[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        for ts in (rows, batches, [gpu(b) for b in batches], DeviceRows(rows, DEV)):
+            r, nd = test_model_full(mf, ts, seen=seen, topK=topK)
+            assert r == want_r, (topK, type(ts))
+            assert float(nd) == pytest.approx(want_n, rel=1e-6, abs=1e-7), (topK, type(ts))
+    users = c["users"]
+    for k in (1, 20, 128):
+        ri, rs = mf.recommend(gpu(users), topK=k, exclude=seen)
+        ti_, ts_ = engine(32).topk_items(gpu(wu), gpu(wi), gpu(users), k, csr_dev(c["seen"]))
+        assert ri.cpu().numpy().tobytes() == ti_.cpu().numpy().tobytes()
+        assert rs.cpu().numpy().tobytes() == ts_.cpu().numpy().tobytes()
+        want_i, want_s = F.ref_topk(wu, wi, users, k, c["seen"])
+        np.testing.assert_array_equal(ri.cpu().numpy(), want_i)
