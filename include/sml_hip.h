@@ -449,6 +449,33 @@ int sml_topk_items(sml_ctx* ctx, const float* w_user, const float* w_item, int64
                    const int64_t* users, int64_t n, int k,
                    const int64_t* seen_off, const int32_t* seen_items,
                    void* scratch, int32_t* items, float* scores, void* stream);
+/* Per-user ranking of held-out sets (same S, d, n_item and Seen rules as above).  users int64 [n], n < 2^31 (a user may
+ * appear more than once); pos_off int64 [n + 1] (pos_off[0] = 0, non-decreasing, pos_off[n] = n_pos < 2^31); pos_items int32
+ * [n_pos]: T(x), the held-out items of users[x], ascending and unique inside [pos_off[x], pos_off[x + 1]) (may be empty).
+ * (An item repeated inside a range is not refused: every copy gets that item's above / pos, and nothing is written
+ * outside above / pos [n_pos].)
+ * An item i is ELIGIBLE for u when i is not in Seen(u) and S(u, i) is not NaN.  For each held-out p of u:
+ *   above[e] = #{eligible i != p : S(u,i) > S(u,p)} -- exactly sml_full_rank's rank of the row (u, p), NaN rule included;
+ *   pos[e]   = #{eligible i : (S(u,i), i) before (S(u,p), p)} in the top-K order (score descending, then id ascending):
+ *              p's index in u's sml_topk_items list; -1 when p itself is not eligible (in Seen(u) or scoring NaN).
+ * pos is strictly increasing along a user's eligible held-out items taken in that order.  Integer counts: the same bytes
+ * whatever the schedule.  The item table is read once per (32-user group, item slice); no score matrix is written.
+ * sml_user_rank_scratch_bytes: bytes of `scratch` for n users and n_pos held-out items (16-byte aligned base; contents
+ *   not needed afterwards), linear in n_pos.  < 0: bad argument. */
+int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int64_t n_item);
+int sml_user_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item,
+                  const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
+                  const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos,
+                  void* stream);
+/* Per-user metrics from pos (as sml_user_rank writes it; any value < 0 is never a hit) over the ranges of pos_off,
+ * n < 2^31.  ks: HOST int32 [n_k], 1 <= n_k <= 8, every K >= 1.  For user x with m = |T(x)| and each K (outputs [n, n_k], row-major):
+ *   hits = #{p : 0 <= pos(p) < K};  dcg = sum over hits of 1/log2(pos + 2), fp32, summed in ascending pos;
+ *   ap = sum over the j-th hit (j = 1, 2, ... in ascending pos) of j / (pos + 1), fp32, same order;
+ *   first[x] = the smallest pos >= 0, -1 if none.  Normalisation (by m, K, IDCG) is the caller's.
+ * The sums take each non-negative pos value once: a value repeated inside a range (sml_user_rank never writes one for
+ * unique held-out items) counts in hits once per copy but adds one term to dcg / ap.  Every output is written. */
+int sml_user_metrics(sml_ctx* ctx, const int32_t* pos, const int64_t* pos_off, int64_t n, const int32_t* ks, int n_k,
+                     int32_t* hits, float* dcg, float* ap, int32_t* first, void* stream);
 
 /* ---- measurement ------------------------------------------------------------------ */
 /* Optional HIP-event timing of every kernel launch on the caller's stream, by kernel class

@@ -107,6 +107,11 @@ SIGNATURES = {
     "sml_topk_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
     "sml_topk_items": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
                                       c_void, c_void, c_void, c_void]),
+    "sml_user_rank_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "sml_user_rank": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64,
+                                     c_void, c_void, c_void, c_void, c_void, c_void]),
+    "sml_user_metrics": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,
+                                        c_void]),
     "sml_stream_create_cu_range": (ctypes.c_int, [ctypes.POINTER(c_void), ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "sml_stream_destroy": (ctypes.c_int, [c_void]),
     "sml_stream_wait_stream": (ctypes.c_int, [c_void, c_void]),

@@ -1719,6 +1719,46 @@ int sml_topk_items(sml_ctx* ctx, const float* w_user, const float* w_item, int64
     return SML_OK;
 }
 
+int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int64_t n_item) {
+    if (!ctx || n < 0 || n >= ((int64_t)1 << 31) || n_pos < 0 || n_pos >= ((int64_t)1 << 31) || n_item <= 0 ||
+        n_item >= ((int64_t)1 << 31))
+        return fail(SML_EINVAL, "sml_user_rank_scratch_bytes", "bad argument");
+    return n == 0 || n_pos == 0 ? 0 : sml_user_rank_scratch_size(n_pos);
+}
+
+int sml_user_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n,
+                  const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
+                  const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, void* stream) {
+    if (!retrieval_args_ok(ctx, n_item, seen_off, seen_items) || n < 0 || n >= ((int64_t)1 << 31) || n_pos < 0 ||
+        n_pos >= ((int64_t)1 << 31))
+        return fail(SML_EINVAL, "sml_user_rank", "bad argument (d must be 32/64, 0 < n_item < 2^31, 0 <= n, n_pos < 2^31, seen_off and seen_items both or neither)");
+    if (n == 0 || n_pos == 0) return SML_OK;
+    if (!w_user || !w_item || !users || !pos_off || !pos_items || !scratch || !above || !pos)
+        return fail(SML_EINVAL, "sml_user_rank", "null argument");
+    DevGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    ctx->prof.begin(PC_MISC, st);
+    HIPCHK(sml_launch_user_rank(ctx->d, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, scratch,
+                                above, pos, st));
+    ctx->prof.end(st);
+    return SML_OK;
+}
+
+int sml_user_metrics(sml_ctx* ctx, const int32_t* pos, const int64_t* pos_off, int64_t n, const int32_t* ks, int n_k,
+                     int32_t* hits, float* dcg, float* ap, int32_t* first, void* stream) {
+    bool ok = ctx && n >= 0 && n < ((int64_t)1 << 31) && ks && n_k >= 1 && n_k <= 8;
+    for (int q = 0; ok && q < n_k; ++q) ok = ks[q] >= 1;
+    if (!ok) return fail(SML_EINVAL, "sml_user_metrics", "bad argument (ks: 1 to 8 host values >= 1, 0 <= n < 2^31)");
+    if (n == 0) return SML_OK;
+    if (!pos || !pos_off || !hits || !dcg || !ap || !first) return fail(SML_EINVAL, "sml_user_metrics", "null argument");
+    DevGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    ctx->prof.begin(PC_MISC, st);
+    HIPCHK(sml_launch_user_metrics(pos, pos_off, n, ks, n_k, hits, dcg, ap, first, st));
+    ctx->prof.end(st);
+    return SML_OK;
+}
+
 int sml_comm_load(const char* path) {
     if (g_rccl.ok()) return SML_OK;
     if (!path) return fail(SML_EINVAL, "sml_comm_load", "null path");

@@ -20,6 +20,22 @@
 //                 register threshold (the K-th entry) filters candidates, so inserts are rare once a list is full.
 //   k_topk_merge  places each slice's candidates by counting, with binary searches, the better entries of the other
 //                 slices: every surviving candidate has a unique final position.
+//
+// Per-user ranking of held-out sets (sml_user_rank, sml_user_metrics):
+//   k_ur_thresholds  one thread per held-out entry: its user, its threshold S(u, p) by score_chain, whether p is in Seen(u)
+//   k_ur_merge       one pass of a segmented merge sort (run width w -> 2w inside every user's range): each entry's new
+//                    place is its place in its run plus a binary-searched count of the smaller keys of the other run.
+//                    Key order is `better` with NaN thresholds last, then the entry index: keys are distinct even when
+//                    a range repeats an item, so the places form a permutation of the range whatever the input.
+//   k_ur_count       the k_full_rank walk with 32 users per wave; every eligible item that is better than the user's
+//                    worst threshold lands in ONE bin: the number of thresholds better than or equal to it (binary search
+//                    over the sorted thresholds).  The score-only bound of `above` differs from it only when the item's
+//                    score ties a threshold; such items add a -1 / +1 pair to delta bins.  Users with at most kUrWin
+//                    non-NaN thresholds keep thresholds and bins in LDS; longer held-out sets are searched and counted
+//                    in global memory (L2-resident).  Bin 0 stays in a register.
+//   k_ur_finish      one workgroup per user: prefix sums over the bins give pos / above in sorted order, scattered back.
+//   k_ur_metrics     one workgroup per user: hit counts and `first` by LDS atomics, then dcg / ap summed by one thread
+//                    in ascending pos, read from a bitmap of the hit positions.
 #include <climits>
 #include <cmath>
 #include "sml_dev.h"
@@ -298,6 +314,342 @@ int topk_slices(int64_t n, int k, int64_t n_item, int* slice_tiles) {
     return s;
 }
 
+// ---- per-user ranking of held-out sets ------------------------------------------------------------------------------
+
+constexpr int kUrWin = 32;         // non-NaN thresholds per user kept in LDS; longer sets go through global memory
+constexpr int kUrWaves = 4;
+constexpr int kUrBlock = 256;      // threads of the per-user finishing / metric workgroups
+
+// sort order of a user's held-out entries: `better` on (threshold, id), NaN thresholds last (by id), then the entry
+// index x (unique), so that no two entries compare equal
+__device__ __forceinline__ bool ur_less(float s, int i, int x, float ts, int ti, int tx) {
+    const bool na = s != s, nb = ts != ts;
+    if (na != nb) return nb;
+    if (i == ti && (na || s == ts)) return x < tx;
+    return na ? i < ti : better(s, i, ts, ti);
+}
+
+// x with off[x] <= e < off[x + 1] (off non-decreasing, off[0] = 0 <= e < off[n])
+__device__ __forceinline__ int64_t ur_segment(const int64_t* __restrict__ off, int64_t n, int64_t e) {
+    int64_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo + 1) >> 1);
+        if (off[mid] <= e) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_ur_thresholds(const float* __restrict__ wu, const float* __restrict__ wi,
+                                                       const int64_t* __restrict__ users, int64_t n,
+                                                       const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
+                                                       int64_t n_pos, const int64_t* __restrict__ seen_off,
+                                                       const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
+                                                       float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
+                                                       int32_t* __restrict__ in_seen) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_pos) return;
+    const int64_t x = ur_segment(pos_off, n, e);
+    const int64_t u = users[x];
+    const int32_t p = pos_items[e];
+    int sn = 0;
+    if (seen_off) {
+        int64_t lo = seen_off[u], hi = seen_off[u + 1];
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (seen_items[mid] < p) lo = mid + 1; else hi = mid;
+        }
+        sn = lo < seen_off[u + 1] && seen_items[lo] == p;
+    }
+    seg[e] = (int32_t)x;
+    ks[e] = score_chain<D>(wu + u * D, wi + (int64_t)p * D);
+    ki[e] = p;
+    kx[e] = (int32_t)e;
+    in_seen[e] = sn;
+}
+
+// runs [a0, a0 + w) and [a0 + w, a0 + 2w) of every user's range -> one sorted run
+__global__ __launch_bounds__(256) void k_ur_merge(const int64_t* __restrict__ pos_off, const int32_t* __restrict__ seg,
+                                                  int64_t n_pos, int64_t w, const float* __restrict__ is,
+                                                  const int32_t* __restrict__ ii, const int32_t* __restrict__ ix,
+                                                  float* __restrict__ os, int32_t* __restrict__ oi, int32_t* __restrict__ ox) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_pos) return;
+    const int64_t x = seg[e];
+    const int64_t lo = pos_off[x], hi = pos_off[x + 1];
+    const int64_t a0 = lo + (e - lo) / (2 * w) * (2 * w);
+    const int64_t mid = a0 + w < hi ? a0 + w : hi;
+    const int64_t end = a0 + 2 * w < hi ? a0 + 2 * w : hi;
+    const float s = is[e];
+    const int32_t i = ii[e], xe = ix[e];
+    int64_t o;
+    if (e < mid) {
+        int64_t l = mid, h = end;          // keys of run B that are smaller: [mid, l)
+        while (l < h) {
+            const int64_t m = l + ((h - l) >> 1);
+            if (ur_less(is[m], ii[m], ix[m], s, i, xe)) l = m + 1; else h = m;
+        }
+        o = e + (l - mid);
+    } else {
+        int64_t l = a0, h = mid;
+        while (l < h) {
+            const int64_t m = l + ((h - l) >> 1);
+            if (ur_less(is[m], ii[m], ix[m], s, i, xe)) l = m + 1; else h = m;
+        }
+        o = a0 + (e - mid) + (l - a0);
+    }
+    os[o] = s;
+    oi[o] = i;
+    ox[o] = xe;
+}
+
+// place (s, i), an eligible item better than the user's worst threshold, among the mv sorted thresholds ts / ti (stride
+// st): k = #{thresholds better than or equal to it} < mv goes to pos bin k.  The above bin is k too unless s ties t_k;
+// then it is ka = #{thresholds >= s} > k, recorded as -1 at k and +1 at ka of the delta bins (bd).  Bins 0 stay in the
+// registers c0 / d0.
+__device__ __forceinline__ void ur_place(const float* ts, const int32_t* ti, int64_t st, int64_t mv, float s, int i, float t0s,
+                                         int t0i, int32_t* bp, int32_t* bd, int& c0, int& d0) {
+    int64_t k = 0;
+    if (!better(s, i, t0s, t0i)) {
+        int64_t l = 1, hh = mv - 1;        // t_0 is better or equal, t_{mv-1} is not
+        while (l < hh) {
+            const int64_t m = (l + hh) >> 1;
+            if (!better(s, i, ts[m * st], ti[m * st])) l = m + 1; else hh = m;
+        }
+        k = l;
+    }
+    const float tk = k ? ts[k * st] : t0s;
+    if (k == 0) ++c0; else atomicAdd(bp + k * st, 1);
+    if (!(s > tk)) {                       // s == t_k: thresholds k .. ka - 1 tie with s
+        int64_t l = k + 1, hh = mv;
+        while (l < hh) {
+            const int64_t m = (l + hh) >> 1;
+            if (!(s > ts[m * st])) l = m + 1; else hh = m;
+        }
+        if (k == 0) --d0; else atomicAdd(bd + k * st, -1);
+        if (l < mv) atomicAdd(bd + l * st, 1);
+    }
+}
+
+// ss / si: every user's thresholds and ids in ur_less order.  At sorted place b of user x, bin_p (zeroed) receives the
+// number of eligible items whose pos bound is b, and bin_d (zeroed) what turns those counts into the above bounds'
+template <int D>
+__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                            const int64_t* __restrict__ users, int64_t n,
+                                                            const int64_t* __restrict__ pos_off,
+                                                            const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                            int slices, int slice_tiles, const float* __restrict__ ss,
+                                                            const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
+                                                            int32_t* __restrict__ bin_d) {
+    __shared__ float l_s[kUrWaves][kUrWin * RT];
+    __shared__ int32_t l_i[kUrWaves][kUrWin * RT];
+    __shared__ int32_t l_p[kUrWaves][kUrWin * RT];
+    __shared__ int32_t l_d[kUrWaves][kUrWin * RT];
+    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31, wave = threadIdx.x >> 6;
+    const int slice = blockIdx.x % slices;
+    const int64_t x = ((int64_t)(blockIdx.x / slices) * kUrWaves + wave) * RT + j;
+    const bool valid = x < n;
+    const int64_t xx = valid ? x : n - 1;
+    const int64_t u = users[xx];
+    const int64_t lo = pos_off[xx];
+    int64_t mv = 0;                        // non-NaN thresholds (the NaN ones sort last)
+    {
+        int64_t l = 0, hh = valid ? pos_off[xx + 1] - lo : 0;
+        while (l < hh) {
+            const int64_t m = l + ((hh - l) >> 1);
+            if (ss[lo + m] == ss[lo + m]) l = m + 1; else hh = m;
+        }
+        mv = l;
+    }
+    // users with at most kUrWin thresholds: thresholds and bins in LDS column j; longer sets: the user's global range
+    const bool win = mv <= kUrWin;
+    for (int k = h; k < kUrWin; k += 2) {
+        l_s[wave][k * RT + j] = win && k < mv ? ss[lo + k] : 0.0f;
+        l_i[wave][k * RT + j] = win && k < mv ? si[lo + k] : 0;
+        l_p[wave][k * RT + j] = 0;
+        l_d[wave][k * RT + j] = 0;
+    }
+    __syncthreads();
+    const float t0s = mv ? ss[lo] : 0.0f, tws = mv ? ss[lo + mv - 1] : 0.0f;
+    const int t0i = mv ? si[lo] : 0, twi = mv ? si[lo + mv - 1] : 0;
+    int c0 = 0, d0 = 0;
+    const int64_t n_tiles = (n_item + RT - 1) / RT;
+    const int64_t t0 = (int64_t)slice * slice_tiles;
+    const int64_t t1 = t0 + slice_tiles < n_tiles ? t0 + slice_tiles : n_tiles;
+    if (t0 < t1) {
+        f32x4 b[D / 8];
+        load_half<D>(wu + u * D, h, b);
+        SeenCursor sc;
+        sc.init(seen_off, seen_items, u, t0 * RT);
+        f32x4 a[D / 8], an[D / 8];
+        int64_t ia = t0 * RT + j;
+        load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, h, a);
+        for (int64_t t = t0; t < t1; ++t) {
+            if (t + 1 < t1) {
+                ia = (t + 1) * RT + j;
+                load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, h, an);
+            }
+            const f32x16 acc = tile_scores<D>(a, b);
+            const int64_t base = t * RT;
+            const unsigned wd = sc.word(base);
+            unsigned live = 0;             // NaN scores fail `better`; an item not better than the worst threshold is in no bin
+            if (mv) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int r = row_of(q, h);
+                    live |= (unsigned)(!((wd >> r) & 1u) && base + r < n_item && better(acc[q], (int)(base + r), tws, twi)) << q;
+                }
+            }
+            if (live) {
+                if (win) {
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if ((live >> q) & 1u)
+                            ur_place(&l_s[wave][j], &l_i[wave][j], RT, mv, acc[q], (int)(base + row_of(q, h)), t0s, t0i,
+                                     &l_p[wave][j], &l_d[wave][j], c0, d0);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if ((live >> q) & 1u)
+                            ur_place(ss + lo, si + lo, 1, mv, acc[q], (int)(base + row_of(q, h)), t0s, t0i, bin_p + lo,
+                                     bin_d + lo, c0, d0);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < D / 8; ++q) a[q] = an[q];
+        }
+    }
+    c0 += __shfl_xor(c0, 32, 64);
+    d0 += __shfl_xor(d0, 32, 64);
+    if (valid && h == 0) {
+        if (c0) atomicAdd(bin_p + lo, c0);
+        if (d0) atomicAdd(bin_d + lo, d0);
+    }
+    __syncthreads();
+    if (valid && win) {
+        for (int k = 1 + h; k < mv; k += 2) {
+            const int32_t vp = l_p[wave][k * RT + j], vd = l_d[wave][k * RT + j];
+            if (vp) atomicAdd(bin_p + lo + k, vp);
+            if (vd) atomicAdd(bin_d + lo + k, vd);
+        }
+    }
+}
+
+// inclusive prefix sum of v over the workgroup (kUrBlock threads); *total = the sum of all
+__device__ __forceinline__ int64_t ur_block_scan(int64_t v, int64_t* sh, int64_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int64_t y = __shfl_up(v, o, 64);
+        if (lane >= o) v += y;
+    }
+    if (lane == 63) sh[wave] = v;
+    __syncthreads();
+    int64_t before = 0, all = 0;
+#pragma unroll
+    for (int q = 0; q < kUrBlock / 64; ++q) {
+        before += q < wave ? sh[q] : 0;
+        all += sh[q];
+    }
+    __syncthreads();
+    *total = all;
+    return v + before;
+}
+
+__global__ __launch_bounds__(kUrBlock) void k_ur_finish(const int64_t* __restrict__ pos_off, const float* __restrict__ ss,
+                                                        const int32_t* __restrict__ sx, const int32_t* __restrict__ in_seen,
+                                                        const int32_t* __restrict__ bin_p, const int32_t* __restrict__ bin_d,
+                                                        int32_t* __restrict__ above, int32_t* __restrict__ pos) {
+    __shared__ int64_t sh[2][kUrBlock / 64];
+    const int64_t x = blockIdx.x;
+    const int64_t lo = pos_off[x], m = pos_off[x + 1] - lo;
+    int64_t cp = 0, ca = 0;
+    for (int64_t c = 0; c < m; c += kUrBlock) {
+        const int64_t k = c + threadIdx.x;
+        const bool in = k < m;
+        int64_t tp, ta;
+        const int64_t ip = ur_block_scan(in ? bin_p[lo + k] : 0, sh[0], &tp);
+        const int64_t ia = ur_block_scan(in ? (int64_t)bin_p[lo + k] + bin_d[lo + k] : 0, sh[1], &ta);
+        if (in) {
+            const int32_t e = sx[lo + k];
+            const bool nan = ss[lo + k] != ss[lo + k];
+            above[e] = nan ? 0 : (int32_t)(ca + ia);
+            pos[e] = nan || in_seen[e] ? -1 : (int32_t)(cp + ip);
+        }
+        cp += tp;
+        ca += ta;
+    }
+}
+
+struct UrKs { int k[8]; };
+
+__global__ __launch_bounds__(kUrBlock) void k_ur_metrics(const int32_t* __restrict__ pos, const int64_t* __restrict__ pos_off,
+                                                         UrKs ks, int n_k, int32_t* __restrict__ hits, float* __restrict__ dcg,
+                                                         float* __restrict__ ap, int32_t* __restrict__ first) {
+    constexpr int kWords = 1024;           // bitmap window: 32,768 consecutive positions
+    __shared__ unsigned bm[kWords];
+    __shared__ int cnt[8];
+    __shared__ int fmin;
+    const int64_t x = blockIdx.x;
+    const int64_t lo = pos_off[x], m = pos_off[x + 1] - lo;
+    int kmax = 0;
+    for (int q = 0; q < n_k; ++q) kmax = ks.k[q] > kmax ? ks.k[q] : kmax;
+    if (threadIdx.x < 8) cnt[threadIdx.x] = 0;
+    if (threadIdx.x == 0) fmin = INT_MAX;
+    __syncthreads();
+    for (int64_t k = threadIdx.x; k < m; k += kUrBlock) {
+        const int p = pos[lo + k];
+        if (p < 0) continue;
+        atomicMin(&fmin, p);
+        for (int q = 0; q < n_k; ++q)
+            if (p < ks.k[q]) atomicAdd(&cnt[q], 1);
+    }
+    __syncthreads();
+    int total = 0;                         // hits at the largest K
+    for (int q = 0; q < n_k; ++q) total = ks.k[q] == kmax ? cnt[q] : total;
+    // thread 0 walks the distinct hit positions in ascending order; the sums at K are recorded when the walk reaches a
+    // position >= K, or after it.  With pos values unique in the range (as sml_user_rank writes them) jj reaches total
+    // and the walk ends early; a repeated value is one bit of the bitmap and is summed once.
+    float sd = 0.0f, sa = 0.0f;
+    int jj = 0;
+    unsigned done = 0;                     // bit q: dcg / ap at ks.k[q] written
+    for (int64_t v0 = 0; v0 < kmax && __syncthreads_or(threadIdx.x == 0 && jj < total); v0 += 32 * kWords) {
+        for (int w = threadIdx.x; w < kWords; w += kUrBlock) bm[w] = 0u;
+        __syncthreads();
+        for (int64_t k = threadIdx.x; k < m; k += kUrBlock) {
+            const int64_t p = pos[lo + k];
+            if (p >= v0 && p < v0 + 32 * kWords && p < kmax) atomicOr(&bm[(p - v0) >> 5], 1u << ((p - v0) & 31));
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 0; w < kWords && jj < total; ++w) {
+                unsigned bits = bm[w];
+                while (bits) {
+                    const int bit = __builtin_ctz(bits);
+                    bits &= bits - 1;
+                    const int64_t pi = v0 + 32 * w + bit;
+                    for (int q = 0; q < n_k; ++q)
+                        if (!((done >> q) & 1u) && pi >= ks.k[q]) {
+                            dcg[x * n_k + q] = sd;
+                            ap[x * n_k + q] = sa;
+                            done |= 1u << q;
+                        }
+                    const float pp = (float)pi;
+                    ++jj;
+                    sd += 1.0f / log2f(pp + 2.0f);
+                    sa += (float)jj / (pp + 1.0f);
+                }
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        for (int q = 0; q < n_k; ++q)
+            if (!((done >> q) & 1u)) { dcg[x * n_k + q] = sd; ap[x * n_k + q] = sa; }
+    }
+    if (threadIdx.x < n_k) hits[x * n_k + threadIdx.x] = cnt[threadIdx.x];
+    if (threadIdx.x == 0) first[x] = fmin == INT_MAX ? -1 : fmin;
+}
+
 }  // namespace
 
 hipError_t sml_launch_full_rank(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* rows, int64_t n, int n_cols,
@@ -340,5 +692,59 @@ hipError_t sml_launch_topk(int d, const float* wu, const float* wi, int64_t n_it
     if (e != hipSuccess) return e;
     const int64_t threads = n * slices * k;
     k_topk_merge<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(cs, ci, cn, n, k, slices, items, scores);
+    return hipGetLastError();
+}
+
+// scratch of sml_user_rank, 256-byte aligned pieces: seg, in_seen, 2 x (key score, key id, entry), bin_p, bin_d
+static int64_t ur_piece(int64_t n_pos) { return (n_pos * 4 + 255) / 256 * 256; }
+
+int64_t sml_user_rank_scratch_size(int64_t n_pos) { return 10 * ur_piece(n_pos); }
+
+hipError_t sml_launch_user_rank(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* users, int64_t n,
+                                const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
+                                const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, hipStream_t st) {
+    char* base = static_cast<char*>(scratch);
+    const int64_t pc = ur_piece(n_pos);
+    int32_t* seg = reinterpret_cast<int32_t*>(base);
+    int32_t* in_seen = reinterpret_cast<int32_t*>(base + pc);
+    float* ks[2] = {reinterpret_cast<float*>(base + 2 * pc), reinterpret_cast<float*>(base + 5 * pc)};
+    int32_t* ki[2] = {reinterpret_cast<int32_t*>(base + 3 * pc), reinterpret_cast<int32_t*>(base + 6 * pc)};
+    int32_t* kx[2] = {reinterpret_cast<int32_t*>(base + 4 * pc), reinterpret_cast<int32_t*>(base + 7 * pc)};
+    int32_t* bin_p = reinterpret_cast<int32_t*>(base + 8 * pc);
+    int32_t* bin_d = reinterpret_cast<int32_t*>(base + 9 * pc);
+    hipError_t e = hipMemsetAsync(bin_p, 0, 2 * pc, st);
+    if (e != hipSuccess) return e;
+    const dim3 eg((unsigned)((n_pos + 255) / 256)), eb(256);
+    if (d == 32)
+        k_ur_thresholds<32><<<eg, eb, 0, st>>>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks[0], ki[0], kx[0], in_seen);
+    else
+        k_ur_thresholds<64><<<eg, eb, 0, st>>>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks[0], ki[0], kx[0], in_seen);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    // a user's range is at most n_pos long: ceil(log2 n_pos) merge passes sort every range
+    int cur = 0;
+    for (int64_t w = 1; w < n_pos; w *= 2, cur ^= 1) {
+        k_ur_merge<<<eg, eb, 0, st>>>(pos_off, seg, n_pos, w, ks[cur], ki[cur], kx[cur], ks[cur ^ 1], ki[cur ^ 1], kx[cur ^ 1]);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    const int64_t groups = (n + RT * kUrWaves - 1) / (RT * kUrWaves);
+    int slices, slice_tiles;
+    plan_slices(groups, n_item, 8192, 64, &slices, &slice_tiles);
+    const dim3 grid((unsigned)(groups * slices)), block(64 * kUrWaves);
+    if (d == 32)
+        k_ur_count<32><<<grid, block, 0, st>>>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles,
+                                               ks[cur], ki[cur], bin_p, bin_d);
+    else
+        k_ur_count<64><<<grid, block, 0, st>>>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles,
+                                               ks[cur], ki[cur], bin_p, bin_d);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    k_ur_finish<<<dim3((unsigned)n), dim3(kUrBlock), 0, st>>>(pos_off, ks[cur], kx[cur], in_seen, bin_p, bin_d, above, pos);
+    return hipGetLastError();
+}
+
+hipError_t sml_launch_user_metrics(const int32_t* pos, const int64_t* pos_off, int64_t n, const int32_t* ks, int n_k,
+                                   int32_t* hits, float* dcg, float* ap, int32_t* first, hipStream_t st) {
+    UrKs k = {};
+    for (int q = 0; q < n_k; ++q) k.k[q] = ks[q];
+    k_ur_metrics<<<dim3((unsigned)n), dim3(kUrBlock), 0, st>>>(pos, pos_off, k, n_k, hits, dcg, ap, first);
     return hipGetLastError();
 }

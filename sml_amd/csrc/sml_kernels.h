@@ -422,3 +422,9 @@ int64_t sml_topk_scratch_size(int64_t n, int k, int64_t n_item);
 hipError_t sml_launch_topk(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* users, int64_t n, int k,
                            const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores,
                            hipStream_t st);
+int64_t sml_user_rank_scratch_size(int64_t n_pos);
+hipError_t sml_launch_user_rank(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* users, int64_t n,
+                                const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
+                                const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, hipStream_t st);
+hipError_t sml_launch_user_metrics(const int32_t* pos, const int64_t* pos_off, int64_t n, const int32_t* ks, int n_k,
+                                   int32_t* hits, float* dcg, float* ap, int32_t* first, hipStream_t st);

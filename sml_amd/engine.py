@@ -712,6 +712,67 @@ class HipEngine(object):
                   "sml_topk_items")
         return items.long(), scores
 
+    USER_RANK_SCRATCH_BYTES = 256 << 20  # held-out items of one sml_user_rank call are capped so its scratch fits this
+
+    def user_ranks(self, user_tab, item_tab, users, pos_off, pos_items, seen=None, ks=(20,)):
+        """Every user's held-out items ranked against the whole catalogue, and per-user metrics at each K in `ks`
+        (include/sml_hip.h, sml_user_rank / sml_user_metrics).  users int64 [n]; pos_off int64 [n + 1] and pos_items
+        int32 [n_pos]: users[x]'s held-out items, ascending and unique in [pos_off[x], pos_off[x + 1]).  Returns a dict:
+        above, pos int32 [n_pos]; hits int32, dcg, ap float32 [n, len(ks)]; first int32 [n]."""
+        wu, wi = self._table(user_tab), self._table(item_tab)
+        users = self._dev(users, torch.int64).reshape(-1)
+        off_h = np.asarray(pos_off.cpu() if torch.is_tensor(pos_off) else pos_off, dtype=np.int64).reshape(-1)
+        pos_items = self._dev(pos_items, torch.int32).reshape(-1)
+        n, n_pos = users.shape[0], pos_items.shape[0]
+        if off_h.shape[0] != n + 1 or off_h[0] != 0 or off_h[-1] != n_pos or (np.diff(off_h) < 0).any():
+            raise ValueError("pos_off must be non-decreasing [n + 1] from 0 to len(pos_items)")
+        ks_h = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
+        ks_p = ctypes.c_void_p(ks_h.ctypes.data)
+        off, seen_items = self._seen(seen)
+        n_k = ks_h.shape[0]
+        out = dict(above=torch.empty(n_pos, device=self.device, dtype=torch.int32),
+                   pos=torch.empty(n_pos, device=self.device, dtype=torch.int32),
+                   hits=torch.empty(n, n_k, device=self.device, dtype=torch.int32),
+                   dcg=torch.empty(n, n_k, device=self.device, dtype=torch.float32),
+                   ap=torch.empty(n, n_k, device=self.device, dtype=torch.float32),
+                   first=torch.empty(n, device=self.device, dtype=torch.int32))
+        if n == 0 or n_pos == 0:         # argument checks (d, n_item, Seen, ks) go through the library
+            check(self.lib.sml_user_rank(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], None, 0, None, None, 0, _ptr(off),
+                                         _ptr(seen_items), None, None, None, self._stream()), "sml_user_rank")
+            check(self.lib.sml_user_metrics(self._ctx, None, None, 0, ks_p, n_k, None, None, None, None, self._stream()),
+                  "sml_user_metrics")
+            if n:
+                out["hits"].zero_()
+                out["dcg"].zero_()
+                out["ap"].zero_()
+                out["first"].fill_(-1)
+            return out
+        per_item = max(1, int(self.lib.sml_user_rank_scratch_bytes(self._ctx, n, n_pos, wi.shape[0])) // n_pos)
+        cap = max(1, self.USER_RANK_SCRATCH_BYTES // per_item)
+        scratch = None
+        c0 = 0
+        while c0 < n:                    # chunks of whole users with at most `cap` held-out items (or one user)
+            c1 = max(c0 + 1, int(np.searchsorted(off_h, off_h[c0] + cap, side="right")) - 1)
+            c1 = min(c1, n)
+            e0, e1 = int(off_h[c0]), int(off_h[c1])
+            sub_off = self._dev(off_h[c0:c1 + 1] - e0, torch.int64)
+            m = c1 - c0
+            nbytes = int(self.lib.sml_user_rank_scratch_bytes(self._ctx, m, e1 - e0, wi.shape[0]))
+            if nbytes < 0:
+                check(-1, "sml_user_rank_scratch_bytes")
+            if scratch is None or scratch.numel() < nbytes:
+                scratch = torch.empty(max(nbytes, 1), device=self.device, dtype=torch.uint8)
+            check(self.lib.sml_user_rank(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, _ptr(sub_off),
+                                         _ptr(pos_items[e0:]), e1 - e0, _ptr(off), _ptr(seen_items), _ptr(scratch),
+                                         _ptr(out["above"][e0:]), _ptr(out["pos"][e0:]), self._stream()), "sml_user_rank")
+            # a chunk of empty sets reads no pos; it still passes a valid pointer (an empty slice's may be null)
+            pos_c = out["pos"][e0:] if e1 > e0 else out["pos"]
+            check(self.lib.sml_user_metrics(self._ctx, _ptr(pos_c), _ptr(sub_off), m, ks_p, n_k,
+                                            _ptr(out["hits"][c0:]), _ptr(out["dcg"][c0:]), _ptr(out["ap"][c0:]),
+                                            _ptr(out["first"][c0:]), self._stream()), "sml_user_metrics")
+            c0 = c1
+        return out
+
     # Evaluations never sit on the training stream.  eval_submit copies the two tables into a snapshot (one copy
     # kernel, a few tens of MB) on the CURRENT stream and queues the rank pass over the snapshot on the engine's side
     # stream; the training kernels that follow on the current stream -- which may overwrite the tables at once -- do

@@ -80,3 +80,62 @@ def test_model_full(model, test_set, seen=None, topK=10):
         ndcg += float(batch_ndcg)
         num_test += datas.shape[0]
     return hits / num_test, torch.tensor(np.float32(ndcg / num_test))
+
+
+def idcg(n):
+    """sum_{r < n} 1 / log2(r + 2) in float64, elementwise over an int array (the reference's IDCG, evalution_function.py)."""
+    n = np.asarray(n, dtype=np.int64)
+    c = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(int(n.max(initial=0))) + 2.0))])
+    return c[n]
+
+
+def user_metrics(out, old_user=None, old_item=None):
+    """Means over users of the per-user metrics of MFbasemode.test_users' result `out`, at each K of out["ks"]:
+
+      recall = hits / m;  precision = hits / K;  ndcg = dcg / IDCG(min(K, m));  ndcg_ref = dcg / IDCG(m) (the reference's
+      get_NDCG);  map = ap / min(K, m) (get_MAP);  mrr = 1 / (first + 1) when first < K, else 0 (get_MRR)
+
+    with m = |T(u)| > 0.  With old_user and old_item (id collections), `hit_shares` gives test_model_pre's split of the
+    hits at each K (reference evalution/evaluation2.py): shares of (old user, old item), (old user, new item),
+    (new user, old item), (new user, new item); all 0 when nothing hits."""
+    host = lambda t: np.asarray(t.cpu() if torch.is_tensor(t) else t)     # noqa: E731
+    pos_off = host(out["pos_off"]).astype(np.int64)
+    m = np.diff(pos_off).astype(np.float64)
+    hits, dcg, ap = (host(out[k]).astype(np.float64).reshape(m.shape[0], -1) for k in ("hits", "dcg", "ap"))
+    first = host(out["first"]).reshape(-1)
+    res = {"users": int(m.shape[0])}
+    for name in ("recall", "precision", "ndcg", "ndcg_ref", "map", "mrr"):
+        res[name] = {}
+    if old_user is not None and old_item is not None:
+        res["hit_shares"] = {}
+        pos = host(out["pos"])
+        u_of = np.repeat(np.asarray(out["users"], dtype=np.int64), np.diff(pos_off))
+        ou = np.isin(u_of, np.asarray(list(old_user) if isinstance(old_user, (set, frozenset)) else old_user))
+        oi = np.isin(np.asarray(out["pos_items"], dtype=np.int64),
+                     np.asarray(list(old_item) if isinstance(old_item, (set, frozenset)) else old_item))
+    for q, K in enumerate(out["ks"]):
+        mk = np.minimum(m, K)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            vals = {"recall": hits[:, q] / m, "precision": hits[:, q] / K, "ndcg": dcg[:, q] / idcg(mk),
+                    "ndcg_ref": dcg[:, q] / idcg(m), "map": ap[:, q] / mk,
+                    "mrr": np.where((first >= 0) & (first < K), 1.0 / (first + 1.0), 0.0)}
+        for name in ("recall", "precision", "ndcg", "ndcg_ref", "map", "mrr"):
+            res[name][K] = float(np.mean(vals[name])) if m.shape[0] else 0.0
+        if "hit_shares" in res:
+            h = (pos >= 0) & (pos < K)
+            c = [int((h & ou & oi).sum()), int((h & ou & ~oi).sum()), int((h & ~ou & oi).sum()), int((h & ~ou & ~oi).sum())]
+            tot = sum(c)
+            res["hit_shares"][K] = tuple(x / tot if tot else 0.0 for x in c)
+    return res
+
+
+def test_model_users(model, test_pairs, seen=None, topK=(20, 10, 5), old_user=None, old_item=None):
+    """All-ranking evaluation of a test period: every user's whole held-out set T(u) (the distinct (user, item) pairs of
+    test_pairs [n, >= 2]; further columns are ignored) placed in the user's ranked list over the entire catalogue minus
+    `seen` (MFbasemode.test_users), then Recall / Precision / NDCG / MAP / MRR @K averaged over the users with m > 0
+    (user_metrics).  Makes no RNG draw."""
+    from .retrieval import held_out
+    model.eval()
+    sets = held_out(test_pairs, model.user_num, model.item_num)
+    out = model.test_users(sets, topK=topK, exclude=seen)
+    return user_metrics(out, old_user, old_item)

@@ -91,6 +91,20 @@ class MFbasemode(nn.Module):
         batch_ndcg = torch.tensor(ndcg) if hits > 0 else 0
         return hits * 1.0, batch_ndcg, hit_rows
 
+    def test_users(self, held_out, topK=(20, 10, 5), exclude=None):
+        """Every user's whole held-out set ranked against the WHOLE catalogue at once (HipEngine.user_ranks), by the score
+        test() uses.  held_out: a sml_amd.retrieval.SeenItems (retrieval.held_out) or a (off, items) CSR over all users;
+        exclude as in recommend().  Returns a dict: users, pos_off, pos_items (the users with at least one held-out item
+        and their items, sml_amd.retrieval.nonempty_users), ks, and the engine's above / pos / hits / dcg / ap / first."""
+        from .retrieval import as_csr, nonempty_users
+        eng = _engine_for(self)
+        w = self.user_laten.weight
+        users, pos_off, pos_items = nonempty_users(held_out)
+        ks = tuple(int(k) for k in (topK if hasattr(topK, "__len__") else (topK,)))
+        out = eng.user_ranks(w.data, self.item_laten.weight.data, users, pos_off, pos_items, as_csr(exclude, w.device), ks)
+        out.update(users=users, pos_off=pos_off, pos_items=pos_items, ks=ks)
+        return out
+
     def set_parameters(self, user_weight, item_weight):
         # last column is the bias (model/MF.py:108-112)
         self.user_laten.weight.data.copy_(user_weight[:, 0:-1])

@@ -71,6 +71,25 @@ class SeenItems(object):
         return seen
 
 
+def held_out(pairs, n_user, n_item):
+    """T(u), the held-out items of every user of a test period: the (user, item) columns of `pairs` [m, >= 2] (further
+    columns, e.g. sampled negatives, are ignored) as a SeenItems -- a per-user ascending, duplicate-free CSR."""
+    pairs = np.asarray(pairs.cpu() if torch.is_tensor(pairs) else pairs)
+    return SeenItems(n_user, n_item).add(pairs[:, :2] if pairs.size else pairs)
+
+
+def nonempty_users(sets):
+    """(users int64 [n], pos_off int64 [n + 1], pos_items int32 [n_pos]) of the users with at least one item in `sets` (a
+    SeenItems or a (off, items) CSR over all users), ascending by user: what HipEngine.user_ranks takes."""
+    off, items = sets.host() if isinstance(sets, SeenItems) else \
+        (np.asarray(t.cpu() if torch.is_tensor(t) else t) for t in sets)
+    off = np.asarray(off, dtype=np.int64)
+    users = np.nonzero(np.diff(off) > 0)[0].astype(np.int64)
+    pos_off = np.zeros(len(users) + 1, dtype=np.int64)
+    np.cumsum(off[users + 1] - off[users], out=pos_off[1:])
+    return users, pos_off, np.asarray(items, dtype=np.int32)[off[0]:off[-1]]
+
+
 def as_csr(exclude, device):
     """exclude: None, a SeenItems, or a (seen_off, seen_items) pair -> what the engine's retrieval calls take."""
     if exclude is None:
