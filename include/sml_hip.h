@@ -516,6 +516,29 @@ int sml_sample_negatives(sml_ctx* ctx, const int64_t* users, int64_t n, const in
 int sml_device_epoch(sml_ctx* ctx, const int64_t* ui, const void* mat, int elem_bytes, int64_t row_stride, int64_t col, int64_t n,
                      uint64_t seed, int64_t* out3, void* stream);
 
+/* ---- SPMF rank-weighted sampling (reference model/baseline.py:448-503) ----------------- */
+/* sml_rank_weights replaces SPMF.compute_R_W_P (model/baseline.py:448-476): rows int64 [n,2] (user, item), 0 <= n < 2^31,
+ * d = 32 / 64 / 128.  score[r] = MFbasemode.forward's score of row r, the same bytes as sml_mf_forward's `score`.  The rows
+ * are ranked by score descending with a stable device radix sort: equal scores by row index ascending, -0.0 equal to
+ * +0.0, NaN before everything (as torch.argsort(descending=True, stable=True) places it).  order[k-1] (int32) = the row
+ * of rank k, rank[row] (int32) = its rank in 1..n, and p[row] = w / S with w = expf(__fdiv_rn((float)rank, (float)n))
+ * and S the fp32 rounding of a fixed-order float64 sum of all w: the same bytes whatever the launch shape.
+ * sml_rank_weights_scratch_bytes: bytes of `scratch` (256-byte aligned base; contents not needed afterwards), linear in
+ * n; < 0: bad argument.  Asynchronous. */
+int64_t sml_rank_weights_scratch_bytes(sml_ctx* ctx, int64_t n);
+int sml_rank_weights(sml_ctx* ctx, const float* w_user, const float* w_item, const int64_t* rows, int64_t n, void* scratch,
+                     float* score, int32_t* rank, int32_t* order, float* p, void* stream);
+/* sml_weighted_epoch: the device form of SPMF.sample_batch (model/baseline.py:489-503) for a whole epoch.  Element e of
+ * [0, n_out) draws u in [0, 1) from the counter-based stream keyed by (seed, e) and takes rank
+ * k = ceil(n * ln(1 + u (e - 1))) clamped to [1, n] -- the exact inverse of the rank-order CDF of w = exp(k / n) -- then
+ * out3[e] = (rows[r][0], rows[r][1], neg) with r = order[k-1] (as sml_rank_weights wrote it).  neg is drawn by
+ * sml_sample_negatives' rejection walk over item_all[0..pop) and the CSR user_ptr [n_users+1] / user_items (every user's
+ * items ascending); *failed (device int32, zeroed here) counts elements still rejected after 4096 draws.  The same
+ * distribution as the reference's numpy draws, NOT its random stream.  All pointers are device memory.  Asynchronous. */
+int sml_weighted_epoch(sml_ctx* ctx, const int64_t* rows, int64_t n, const int32_t* order, const int64_t* item_all, int64_t pop,
+                       const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t n_out, uint64_t seed,
+                       int64_t* out3, int32_t* failed, void* stream);
+
 /* ---- host helper: batch supply ------------------------------------------------------- */
 /* Sequential rejection sampling of offlineDataset_withsample.__getitem__ (reference
  * data/dataset.py:63-71) over a pre-drawn candidate stream, on the HOST (no GPU involved):

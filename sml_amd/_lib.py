@@ -156,6 +156,11 @@ SIGNATURES = {
                                c_void, ctypes.c_int]),
     "sml_host_resolve_negatives_csr": (ctypes.c_int, [c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void,
                                                       c_void, c_void, c_void]),
+    "sml_rank_weights_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64]),
+    "sml_rank_weights": (ctypes.c_int, [c_void, c_void, c_void, c_void, ctypes.c_int64, c_void, c_void, c_void, c_void, c_void,
+                                        c_void]),
+    "sml_weighted_epoch": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64,
+                                          c_void, ctypes.c_int64, ctypes.c_uint64, c_void, c_void, c_void]),
     "sml_selftest": (ctypes.c_int, [ctypes.c_int]),
 }
 

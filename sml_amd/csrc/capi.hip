@@ -2032,6 +2032,42 @@ int sml_device_epoch(sml_ctx* ctx, const int64_t* ui, const void* mat, int elem_
     return SML_OK;
 }
 
+int64_t sml_rank_weights_scratch_bytes(sml_ctx* ctx, int64_t n) {
+    if (!ctx || n < 0 || n >= ((int64_t)1 << 31)) return fail(SML_EINVAL, "sml_rank_weights_scratch_bytes", "bad argument");
+    return sml_rank_weights_scratch_size(n);
+}
+
+int sml_rank_weights(sml_ctx* ctx, const float* w_user, const float* w_item, const int64_t* rows, int64_t n, void* scratch,
+                     float* score, int32_t* rank, int32_t* order, float* p, void* stream) {
+    if (!ctx || n < 0 || n >= ((int64_t)1 << 31) || (ctx->d != 32 && ctx->d != 64 && ctx->d != 128))
+        return fail(SML_EINVAL, "sml_rank_weights", "bad argument (0 <= n < 2^31, d must be 32/64/128)");
+    if (n == 0) return SML_OK;
+    if (!w_user || !w_item || !rows || !scratch || !score || !rank || !order || !p) return fail(SML_EINVAL, "sml_rank_weights", "null argument");
+    DevGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    ctx->prof.begin(PC_MISC, st);
+    HIPCHK(sml_launch_rank_weights(ctx->d, w_user, w_item, rows, n, scratch, score, rank, order, p, st));
+    ctx->prof.end(st);
+    return SML_OK;
+}
+
+int sml_weighted_epoch(sml_ctx* ctx, const int64_t* rows, int64_t n, const int32_t* order, const int64_t* item_all, int64_t pop,
+                       const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t n_out, uint64_t seed,
+                       int64_t* out3, int32_t* failed, void* stream) {
+    if (!ctx || n <= 0 || n >= ((int64_t)1 << 31) || pop <= 0 || n_users < 0 || n_out < 0 || n_out >= ((int64_t)1 << 31))
+        return fail(SML_EINVAL, "sml_weighted_epoch", "bad argument (0 < n < 2^31, pop > 0, 0 <= n_out < 2^31)");
+    if (!rows || !order || !item_all || !user_ptr || !user_items || !out3 || !failed)
+        return fail(SML_EINVAL, "sml_weighted_epoch", "null argument");
+    DevGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(failed, 0, sizeof(int32_t), st));
+    if (n_out == 0) return SML_OK;
+    ctx->prof.begin(PC_MISC, st);
+    HIPCHK(sml_launch_weighted_epoch(rows, n, order, item_all, pop, user_ptr, n_users, user_items, n_out, seed, out3, failed, st));
+    ctx->prof.end(st);
+    return SML_OK;
+}
+
 int sml_host_resolve_negatives_csr(const int64_t* users, int64_t n, const int64_t* cand, int64_t m,
                                    const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t* negs,
                                    int64_t* consumed, int64_t* resolved) {

@@ -63,13 +63,6 @@ template <> struct RowVec<__half> {
     }
 };
 
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int off = LPR / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // The evaluation's lane-group sums on DPP (data-parallel primitives: the cross-lane move rides in the VALU
 // instruction) instead of ds_bpermute shuffles.  rocprofv3 counters put the rank kernels at two thirds VALU-bound
 // (293 M vector instructions per 75k x 1001 evaluation, 31 per candidate and lane group): so the candidates are
@@ -831,10 +824,9 @@ __global__ __launch_bounds__(256) void k_mf_forward(const float* __restrict__ wu
     float u[4], it[4];
     RowVec<float>::load(wu + user[t] * D + sub * 4, u);
     RowVec<float>::load(wi + item[t] * D + sub * 4, it);
-    float s = 0.f, uu = 0.f;
+    float s = mf_dot<LPR>(u, it), uu = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { s += u[k] * it[k]; uu += u[k] * u[k]; }
-    s = group_sum<LPR>(s);
+    for (int k = 0; k < 4; ++k) uu += u[k] * u[k];
     if (norm) s = s / sqrtf(group_sum<LPR>(uu));
     RowVec<float>::store(uemb + t * D + sub * 4, u);
     RowVec<float>::store(iemb + t * D + sub * 4, it);
@@ -1317,12 +1309,6 @@ __global__ __launch_bounds__(256) void k_evs_sum(const uint16_t* __restrict__ pa
 // one of the user's own items (data/dataset.py:63-71 as a distribution, not as a random-number stream).
 // Counter-based generator: element e of epoch `seed` always gets the same draws, whatever the launch shape.
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t splitmix64(uint64_t& s) {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ull);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
 __global__ __launch_bounds__(256) void k_sample_negatives(const int64_t* __restrict__ users, int64_t n,
                                                           const int64_t* __restrict__ item_all, int64_t pop,
                                                           const int64_t* __restrict__ user_ptr, int64_t n_users,
@@ -1330,22 +1316,8 @@ __global__ __launch_bounds__(256) void k_sample_negatives(const int64_t* __restr
                                                           int64_t* __restrict__ negs, int* __restrict__ failed) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
-    const int64_t u = users[e];
-    int64_t b = 0, t = 0;
-    if (u >= 0 && u < n_users) { b = user_ptr[u]; t = user_ptr[u + 1]; }
-    uint64_t st = seed ^ ((uint64_t)e * 0xd1342543de82ef95ull + 0x632be59bd9b4e019ull);
-    int64_t c = -1, cand = item_all[0];
-    for (int tries = 0; tries < 4096; ++tries) {
-        const uint64_t r = splitmix64(st);
-        cand = item_all[(int64_t)__umul64hi(r, (uint64_t)pop)];                    // uniform over [0, pop)
-        int64_t lo = b, hi = t;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (user_items[mid] < cand) lo = mid + 1; else hi = mid; }
-        if (!(lo < t && user_items[lo] == cand)) { c = cand; break; }
-    }
-    // a user who owns (almost) every item of the period: counted (the driver raises when it reads the counter), and
-    // the element still carries a VALID item index -- the last candidate -- so nothing downstream gathers row -1
-    if (c < 0) { atomicAdd(failed, 1); c = cand; }
-    negs[e] = c;
+    uint64_t st = neg_stream(seed, e);
+    negs[e] = draw_negative(st, users[e], item_all, pop, user_ptr, n_users, user_items, failed);
 }
 
 // One shuffled pass over a period's rows, assembled ON THE DEVICE (the device form of a DataLoader(shuffle=True) pass over

@@ -8,6 +8,59 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// ---- shared by mf_kernels.hip and spmf.hip ------------------------------------------------
+// Sum over the LPR adjacent lanes that own a row (xor butterfly, stride LPR/2 down to 1).
+template <int LPR>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int off = LPR / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// MFbasemode.forward's score (reference model/MF.py:34-43) with a row spread over LPR lanes, 4 dims per lane: the lane's
+// four products, each rounded, added in order to 0.f, then group_sum.  k_mf_forward and the SPMF rank weights (spmf.hip)
+// both score through this one chain, so their scores are the same bytes.  Contraction is OFF: left to itself the compiler
+// multiplies-then-adds in one kernel (packed multiplies) and fuses into fma in another, an ulp apart.
+template <int LPR>
+__device__ __forceinline__ float mf_dot(const float (&u)[4], const float (&it)[4]) {
+#pragma clang fp contract(off)
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += u[k] * it[k];
+    return group_sum<LPR>(s);
+}
+
+// Counter-based generator of the device batch supply: element e of a draw keyed by `seed` starts from
+// neg_stream(seed, e) and advances with splitmix64, whatever the launch shape.
+__device__ __forceinline__ uint64_t splitmix64(uint64_t& s) {
+    uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ uint64_t neg_stream(uint64_t seed, int64_t e) {
+    return seed ^ ((uint64_t)e * 0xd1342543de82ef95ull + 0x632be59bd9b4e019ull);
+}
+// One negative for user u: candidates uniform over item_all[0, pop), redrawn while the candidate is one of u's own items
+// (CSR user_ptr [n_users + 1] into ascending user_items), at most 4096 draws (reference data/dataset.py:63-71 and
+// model/baseline.py:496-501 as a distribution).  A user who owns (almost) every item is counted in *failed (the driver
+// raises when it reads the counter) and still gets a VALID item -- the last candidate -- so nothing gathers row -1.
+__device__ __forceinline__ int64_t draw_negative(uint64_t& st, int64_t u, const int64_t* __restrict__ item_all, int64_t pop,
+                                                 const int64_t* __restrict__ user_ptr, int64_t n_users,
+                                                 const int64_t* __restrict__ user_items, int* __restrict__ failed) {
+    int64_t b = 0, t = 0;
+    if (u >= 0 && u < n_users) { b = user_ptr[u]; t = user_ptr[u + 1]; }
+    int64_t cand = item_all[0];
+    for (int tries = 0; tries < 4096; ++tries) {
+        const uint64_t r = splitmix64(st);
+        cand = item_all[(int64_t)__umul64hi(r, (uint64_t)pop)];                    // uniform over [0, pop)
+        int64_t lo = b, hi = t;
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (user_items[mid] < cand) lo = mid + 1; else hi = mid; }
+        if (!(lo < t && user_items[lo] == cand)) return cand;
+    }
+    atomicAdd(failed, 1);
+    return cand;
+}
+
 #define SML_HID 512   // fc1 width                    (reference model/conv_transfer.py:33)
 #define SML_C1 10     // conv1 output channels        (model/conv_transfer.py:26-27)
 #define SML_C2 5      // conv2 output channels        (model/conv_transfer.py:29-30)

@@ -428,3 +428,10 @@ hipError_t sml_launch_user_rank(int d, const float* wu, const float* wi, int64_t
                                 const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, hipStream_t st);
 hipError_t sml_launch_user_metrics(const int32_t* pos, const int64_t* pos_off, int64_t n, const int32_t* ks, int n_k,
                                    int32_t* hits, float* dcg, float* ap, int32_t* first, hipStream_t st);
+// spmf.hip: SPMF rank weights and the rank-weighted device epoch (d = 32 / 64 / 128, n < 2^31)
+int64_t sml_rank_weights_scratch_size(int64_t n);
+hipError_t sml_launch_rank_weights(int d, const float* wu, const float* wi, const int64_t* rows, int64_t n, void* scratch,
+                                   float* score, int32_t* rank, int32_t* order, float* p, hipStream_t st);
+hipError_t sml_launch_weighted_epoch(const int64_t* rows, int64_t n, const int32_t* order, const int64_t* item_all, int64_t pop,
+                                     const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t n_out,
+                                     uint64_t seed, int64_t* out3, int* failed, hipStream_t st);

@@ -548,6 +548,44 @@ class HipEngine(object):
                                         ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(out), self._stream()), "sml_device_epoch")
         return out
 
+    # ------------------------------------------------------------------ SPMF rank-weighted sampling
+    def rank_weights(self, w_user, w_item, rows):
+        """SPMF.compute_R_W_P on the device (sml_rank_weights): rows int64 [N,2] -> (score f32 [N], rank int32 [N] in 1..N,
+        order int32 [N] with order[k-1] the row of rank k, p f32 [N]).  Rank 1 is the highest score; ties keep row order."""
+        wu, wi = self._table(w_user), self._table(w_item)
+        rows = self._dev(rows, torch.int64).reshape(-1, 2).contiguous()
+        n = rows.shape[0]
+        if n and (int(rows.min()) < 0 or int(rows[:, 0].max()) >= wu.shape[0] or int(rows[:, 1].max()) >= wi.shape[0]):
+            raise ValueError("rank_weights: a row's user or item is outside the tables")
+        score = torch.empty(n, device=self.device, dtype=torch.float32)
+        rank = torch.empty(n, device=self.device, dtype=torch.int32)
+        order = torch.empty(n, device=self.device, dtype=torch.int32)
+        p = torch.empty(n, device=self.device, dtype=torch.float32)
+        nbytes = int(self.lib.sml_rank_weights_scratch_bytes(self._ctx, n))
+        if nbytes < 0:
+            check(-1, "sml_rank_weights_scratch_bytes")
+        scratch = torch.empty(max(nbytes, 1), device=self.device, dtype=torch.uint8)
+        check(self.lib.sml_rank_weights(self._ctx, _ptr(wu), _ptr(wi), _ptr(rows), n, _ptr(scratch), _ptr(score), _ptr(rank),
+                                        _ptr(order), _ptr(p), self._stream()), "sml_rank_weights")
+        return score, rank, order, p
+
+    def weighted_epoch(self, rows, order, item_all, user_ptr, user_items, n_out, seed):
+        """int64 [n_out,3] device triples drawn with SPMF's rank weights (sml_weighted_epoch): rows int64 [N,2] and `order`
+        as rank_weights returned it; negatives by the rejection walk over item_all and the CSR user_ptr / user_items
+        (device int64).  Returns (triples, failed) with failed a device int32 [1]."""
+        rows = self._dev(rows, torch.int64).reshape(-1, 2).contiguous()
+        order = self._dev(order, torch.int32)
+        item_all, user_ptr, user_items = (self._dev(t, torch.int64) for t in (item_all, user_ptr, user_items))
+        if order.shape[0] != rows.shape[0]:
+            raise ValueError("weighted_epoch: order must have one entry per row")
+        out = torch.empty((int(n_out), 3), device=self.device, dtype=torch.int64)
+        failed = torch.zeros(1, device=self.device, dtype=torch.int32)
+        check(self.lib.sml_weighted_epoch(self._ctx, _ptr(rows), rows.shape[0], _ptr(order), _ptr(item_all), item_all.shape[0],
+                                          _ptr(user_ptr), user_ptr.shape[0] - 1, _ptr(user_items), int(n_out),
+                                          ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(out), _ptr(failed), self._stream()),
+              "sml_weighted_epoch")
+        return out, failed
+
     # ------------------------------------------------------------------ a2
     def mf_forward(self, w_user, w_item, user, item, norm=False):
         wu, wi = self._table(w_user), self._table(w_item)
