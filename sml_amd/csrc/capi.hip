@@ -1682,6 +1682,18 @@ int sml_eval_metrics(sml_ctx* ctx, const int32_t* rank, int64_t n, int topk, flo
 }
 
 // ---- full-catalogue retrieval (retrieval.hip) ----------------------------------------------------------------------
+// the tail of every entry point below: one launcher call (`launch`, which names the stream st) on the context's device,
+// timed in the PC_MISC profile class; a failure is reported under the launcher call's own text, as HIPCHK does
+#define RUN_MISC(ctx, stream, launch)          \
+    do {                                       \
+        DevGuard g((ctx)->device);             \
+        hipStream_t st = (hipStream_t)(stream); \
+        (ctx)->prof.begin(PC_MISC, st);        \
+        HIPCHK(launch);                        \
+        (ctx)->prof.end(st);                   \
+        return SML_OK;                         \
+    } while (0)
+
 static bool retrieval_args_ok(sml_ctx* ctx, int64_t n_item, const int64_t* seen_off, const int32_t* seen_items) {
     return ctx && (ctx->d == 32 || ctx->d == 64) && n_item > 0 && n_item < ((int64_t)1 << 31) && (!seen_off) == (!seen_items);
 }
@@ -1692,12 +1704,7 @@ int sml_full_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_
         return fail(SML_EINVAL, "sml_full_rank", "bad argument (d must be 32/64, 0 < n_item < 2^31, n_cols >= 2, seen_off and seen_items both or neither)");
     if (n == 0) return SML_OK;
     if (!w_user || !w_item || !rows || !rank) return fail(SML_EINVAL, "sml_full_rank", "null argument");
-    DevGuard g(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_MISC, st);
-    HIPCHK(sml_launch_full_rank(ctx->d, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, st));
-    ctx->prof.end(st);
-    return SML_OK;
+    RUN_MISC(ctx, stream, sml_launch_full_rank(ctx->d, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, st));
 }
 
 int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item) {
@@ -1711,12 +1718,7 @@ int sml_topk_items(sml_ctx* ctx, const float* w_user, const float* w_item, int64
         return fail(SML_EINVAL, "sml_topk_items", "bad argument (d must be 32/64, 1 <= k <= 128, 0 < n_item < 2^31, seen_off and seen_items both or neither)");
     if (n == 0) return SML_OK;
     if (!w_user || !w_item || !users || !scratch || !items || !scores) return fail(SML_EINVAL, "sml_topk_items", "null argument");
-    DevGuard g(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_MISC, st);
-    HIPCHK(sml_launch_topk(ctx->d, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, st));
-    ctx->prof.end(st);
-    return SML_OK;
+    RUN_MISC(ctx, stream, sml_launch_topk(ctx->d, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, st));
 }
 
 int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int64_t n_item) {
@@ -1735,13 +1737,8 @@ int sml_user_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_
     if (n == 0 || n_pos == 0) return SML_OK;
     if (!w_user || !w_item || !users || !pos_off || !pos_items || !scratch || !above || !pos)
         return fail(SML_EINVAL, "sml_user_rank", "null argument");
-    DevGuard g(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_MISC, st);
-    HIPCHK(sml_launch_user_rank(ctx->d, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, scratch,
-                                above, pos, st));
-    ctx->prof.end(st);
-    return SML_OK;
+    RUN_MISC(ctx, stream, sml_launch_user_rank(ctx->d, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off, seen_items,
+                                               scratch, above, pos, st));
 }
 
 int sml_user_metrics(sml_ctx* ctx, const int32_t* pos, const int64_t* pos_off, int64_t n, const int32_t* ks, int n_k,
@@ -1751,12 +1748,7 @@ int sml_user_metrics(sml_ctx* ctx, const int32_t* pos, const int64_t* pos_off, i
     if (!ok) return fail(SML_EINVAL, "sml_user_metrics", "bad argument (ks: 1 to 8 host values >= 1, 0 <= n < 2^31)");
     if (n == 0) return SML_OK;
     if (!pos || !pos_off || !hits || !dcg || !ap || !first) return fail(SML_EINVAL, "sml_user_metrics", "null argument");
-    DevGuard g(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_MISC, st);
-    HIPCHK(sml_launch_user_metrics(pos, pos_off, n, ks, n_k, hits, dcg, ap, first, st));
-    ctx->prof.end(st);
-    return SML_OK;
+    RUN_MISC(ctx, stream, sml_launch_user_metrics(pos, pos_off, n, ks, n_k, hits, dcg, ap, first, st));
 }
 
 int sml_comm_load(const char* path) {

@@ -10,14 +10,20 @@
 // tests/test_retrieval_gpu.py compares ranks, lists and score bits with an exact emulation of it.
 //
 // Grid: (32 * W users) x slices; slice = blockIdx % slices, so with slices a multiple of 8 an XCD walks 1/8 of the
-// item table.  Every wave owns 32 users and walks its slice tile by tile (32 items), loading the next tile's item rows
-// while the current tile's MFMAs run.  Seen items: a cursor per lane into the user's ascending CSR range yields the
-// exclusion bitmap of each 32-item tile in one register word (exact: ids, never scores).
+// item table (plan_grid on the host, lane_pos on the device).  Every wave owns 32 users.
 //
-//   k_full_rank   counts, per row, items scoring strictly above the positive; per-slice counts land with integer
-//                 atomicAdd (exact, order-free).
-//   k_topk_slice  keeps a sorted list of the K best (score desc, id asc) per (user, slice) in the wave's LDS; a
+// The walk, written once (walk_slice): a wave goes through its slice tile by tile (32 items), loading the next tile's
+// item rows while the current tile's MFMAs run; a cursor per lane into the user's ascending Seen range (CSR) yields the
+// exclusion bitmap of each tile in one register word (exact: ids, never scores).  Per tile the kernel's callable gets the
+// 16 scores of the lane, the tile's first item and a 16-bit mask of the scores that belong to a real, unseen item.  The
+// walk holds no workgroup barrier.  What a kernel does with a tile:
+//
+//   k_full_rank   counts the eligible items scoring strictly above the row's positive; per-slice counts land with
+//                 integer atomicAdd (exact, order-free).
+//   k_topk_slice  offers them to a sorted list of the K best (score desc, id asc) per (user, slice) in the wave's LDS; a
 //                 register threshold (the K-th entry) filters candidates, so inserts are rare once a list is full.
+//   k_ur_count    places them in the bins of the user's held-out thresholds (below).
+//
 //   k_topk_merge  places each slice's candidates by counting, with binary searches, the better entries of the other
 //                 slices: every surviving candidate has a unique final position.
 //
@@ -27,7 +33,7 @@
 //                    place is its place in its run plus a binary-searched count of the smaller keys of the other run.
 //                    Key order is `better` with NaN thresholds last, then the entry index: keys are distinct even when
 //                    a range repeats an item, so the places form a permutation of the range whatever the input.
-//   k_ur_count       the k_full_rank walk with 32 users per wave; every eligible item that is better than the user's
+//   k_ur_count       every eligible item of the walk that is better than the user's
 //                    worst threshold lands in ONE bin: the number of thresholds better than or equal to it (binary search
 //                    over the sorted thresholds).  The score-only bound of `above` differs from it only when the item's
 //                    score ties a threshold; such items add a -1 / +1 pair to delta bins.  Users with at most kUrWin
@@ -38,6 +44,7 @@
 //                    in ascending pos, read from a bitmap of the hit positions.
 #include <climits>
 #include <cmath>
+#include <type_traits>
 #include "sml_dev.h"
 #include "sml_kernels.h"
 #include "../../include/sml_hip.h"
@@ -80,8 +87,24 @@ __device__ __forceinline__ f32x16 tile_scores(const f32x4 (&a)[D / 8], const f32
 
 __device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// bit r of the result = bit row_of(r, h) of a tile's 32-item word, r = 0..15
+__device__ __forceinline__ unsigned lane_rows(unsigned word, int h) {
+    const unsigned x = word >> (4 * h);
+    return (x & 0xFu) | ((x >> 4) & 0xF0u) | ((x >> 8) & 0xF00u) | ((x >> 12) & 0xF000u);
+}
+
 // total order of the top-K lists: score descending, then item id ascending (NaN is never better than anything)
 __device__ __forceinline__ bool better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
+
+// first index of [lo, hi) at which pred is false, hi if there is none (pred holds on a prefix of the range)
+template <class I, class P>
+__device__ __forceinline__ I lower_bound(I lo, I hi, P pred) {
+    while (lo < hi) {
+        const I mid = lo + ((hi - lo) >> 1);
+        if (pred(mid)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
 
 // forward-only cursor over one user's ascending Seen range
 struct SeenCursor {
@@ -91,13 +114,8 @@ struct SeenCursor {
     __device__ void init(const int64_t* __restrict__ off, const int32_t* __restrict__ it, int64_t u, long long start) {
         items = it;
         if (!off) { cur = end = 0; nxt = LLONG_MAX; return; }
-        int64_t lo = off[u], hi = off[u + 1];
-        end = hi;
-        while (lo < hi) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (it[mid] < start) lo = mid + 1; else hi = mid;
-        }
-        cur = lo;
+        end = off[u + 1];
+        cur = lower_bound(off[u], end, [&](int64_t m) { return it[m] < start; });
         nxt = cur < end ? it[cur] : LLONG_MAX;
     }
     // bit b set <=> item base + b is in Seen; the cursor moves past the tile
@@ -112,49 +130,75 @@ struct SeenCursor {
     }
 };
 
+// a lane's place in the grid of (32 * waves users) x slices: lane half h, user column j, the wave, its item slice and its
+// row of the n users / test rows (rc: clamped to n - 1, so that lanes past the end read a real row)
+struct LanePos {
+    int h, j, wave, slice;
+    int64_t row, rc;
+    bool valid;
+};
+
+__device__ __forceinline__ LanePos lane_pos(int slices, int waves, int64_t n) {
+    LanePos lp;
+    const int lane = threadIdx.x & 63;
+    lp.h = lane >> 5;
+    lp.j = lane & 31;
+    lp.wave = threadIdx.x >> 6;
+    lp.slice = blockIdx.x % slices;
+    lp.row = ((int64_t)(blockIdx.x / slices) * waves + lp.wave) * RT + lp.j;
+    lp.valid = lp.row < n;
+    lp.rc = lp.valid ? lp.row : n - 1;
+    return lp;
+}
+
+// The catalogue walk of one wave: user u's scores against every 32-item tile of the lane's slice, next tile's item rows
+// in flight under the current tile's MFMAs.  tile(acc, base, elig) runs once per tile: acc[q] = S(u, base + row_of(q, h)),
+// bit q of elig set <=> that item exists (< n_item) and is not in Seen(u).  An empty slice loads nothing and calls nothing.
+template <int D, class Tile>
+__device__ __forceinline__ void walk_slice(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item, int64_t u,
+                                           const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                           const LanePos& lp, int slice_tiles, Tile&& tile) {
+    const int64_t n_tiles = (n_item + RT - 1) / RT;
+    const int64_t t0 = (int64_t)lp.slice * slice_tiles;
+    const int64_t t1 = t0 + slice_tiles < n_tiles ? t0 + slice_tiles : n_tiles;
+    if (t0 >= t1) return;
+    f32x4 b[D / 8];
+    load_half<D>(wu + u * D, lp.h, b);
+    SeenCursor sc;
+    sc.init(seen_off, seen_items, u, t0 * RT);
+    f32x4 a[D / 8], an[D / 8];
+    int64_t ia = t0 * RT + lp.j;
+    load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h, a);
+    for (int64_t t = t0; t < t1; ++t) {
+        if (t + 1 < t1) {
+            ia = (t + 1) * RT + lp.j;
+            load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h, an);
+        }
+        const f32x16 acc = tile_scores<D>(a, b);
+        const int64_t base = t * RT;
+        const int64_t left = n_item - base;              // >= 1; bit i of `real`: item base + i exists and is not in Seen
+        const unsigned real = ~sc.word(base) & (left < RT ? (1u << left) - 1u : ~0u);
+        tile(acc, base, lane_rows(real, lp.h));
+#pragma unroll
+        for (int q = 0; q < D / 8; ++q) a[q] = an[q];
+    }
+}
+
 template <int D>
 __global__ __launch_bounds__(256) void k_full_rank(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
                                                    const int64_t* __restrict__ rows, int64_t n, int n_cols,
                                                    const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
                                                    int slices, int slice_tiles, int32_t* __restrict__ rank) {
-    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
-    const int slice = blockIdx.x % slices;
-    const int64_t r = ((int64_t)(blockIdx.x / slices) * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RT + j;
-    const bool valid = r < n;
-    const int64_t rr = valid ? r : n - 1;
-    const int64_t u = rows[rr * n_cols], p = rows[rr * n_cols + 1];
-    const float* urow = wu + u * D;
-    f32x4 b[D / 8];
-    load_half<D>(urow, h, b);
-    const float thr = score_chain<D>(urow, wi + p * D);
-    const int64_t n_tiles = (n_item + RT - 1) / RT;
-    const int64_t t0 = (int64_t)slice * slice_tiles;
-    const int64_t t1 = t0 + slice_tiles < n_tiles ? t0 + slice_tiles : n_tiles;
-    if (t0 >= t1) return;
-    SeenCursor sc;
-    sc.init(seen_off, seen_items, u, t0 * RT);
-    f32x4 a[D / 8], an[D / 8];
-    int64_t ia = t0 * RT + j;
-    load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, h, a);
+    const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
+    const int64_t u = rows[lp.rc * n_cols], p = rows[lp.rc * n_cols + 1];
+    const float thr = score_chain<D>(wu + u * D, wi + p * D);
     int cnt = 0;
-    for (int64_t t = t0; t < t1; ++t) {
-        if (t + 1 < t1) {
-            ia = (t + 1) * RT + j;
-            load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, h, an);
-        }
-        const f32x16 acc = tile_scores<D>(a, b);
-        const int64_t base = t * RT;
-        const unsigned w = sc.word(base);
+    walk_slice<D>(wu, wi, n_item, u, seen_off, seen_items, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int i = row_of(q, h);
-            cnt += (acc[q] > thr) & !((w >> i) & 1u) & (base + i != p) & (base + i < n_item);
-        }
-#pragma unroll
-        for (int q = 0; q < D / 8; ++q) a[q] = an[q];
-    }
+        for (int q = 0; q < 16; ++q) cnt += (acc[q] > thr) & ((elig >> q) & 1u) & (base + row_of(q, lp.h) != p);
+    });
     cnt += __shfl_xor(cnt, 32, 64);
-    if (h == 0 && valid && cnt) atomicAdd(rank + r, cnt);
+    if (lp.h == 0 && lp.valid && cnt) atomicAdd(rank + lp.row, cnt);
 }
 
 // insert (s, i) into user j's list (k slots, column j of [k][32] arrays); cnt = live entries
@@ -186,71 +230,47 @@ __global__ __launch_bounds__(256) void k_topk_slice(const float* __restrict__ wu
                                                     int slices, int slice_tiles, float* __restrict__ cand_s,
                                                     int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n) {
     extern __shared__ float lds[];
-    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31, wave = threadIdx.x >> 6;
-    float* ls = lds + (size_t)wave * 2 * k * RT;
+    const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
+    const int h = lp.h, j = lp.j;
+    float* ls = lds + (size_t)lp.wave * 2 * k * RT;
     int* li = reinterpret_cast<int*>(ls + k * RT);
-    const int slice = blockIdx.x % slices;
-    const int64_t x = ((int64_t)(blockIdx.x / slices) * (blockDim.x >> 6) + wave) * RT + j;
-    const bool valid = x < n;
-    const int64_t u = users[valid ? x : n - 1];
-    f32x4 b[D / 8];
-    load_half<D>(wu + u * D, h, b);
-    const int64_t n_tiles = (n_item + RT - 1) / RT;
-    const int64_t t0 = (int64_t)slice * slice_tiles;
-    const int64_t t1 = t0 + slice_tiles < n_tiles ? t0 + slice_tiles : n_tiles;
+    const int64_t u = users[lp.rc];
     int cnt = 0;                          // live entries of user j's list (both lane halves keep it)
     float thr_s = -INFINITY;              // register copy of the K-th entry: lags the list, never ahead of it
     int thr_i = INT_MAX;
-    if (t0 < t1) {
-        SeenCursor sc;
-        sc.init(seen_off, seen_items, u, t0 * RT);
-        f32x4 a[D / 8], an[D / 8];
-        int64_t ia = t0 * RT + j;
-        load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, h, a);
-        for (int64_t t = t0; t < t1; ++t) {
-            if (t + 1 < t1) {
-                ia = (t + 1) * RT + j;
-                load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, h, an);
-            }
-            const f32x16 acc = tile_scores<D>(a, b);
-            const int64_t base = t * RT;
-            const unsigned w = sc.word(base);
-            unsigned pass = 0;
+    walk_slice<D>(wu, wi, n_item, u, seen_off, seen_items, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
+        unsigned pass = 0;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int i = row_of(q, h);
-                const bool ok = valid && !((w >> i) & 1u) && base + i < n_item && better(acc[q], (int)(base + i), thr_s, thr_i);
-                pass |= (unsigned)ok << q;
-            }
-            if (__any(pass != 0)) {
-                // the two lane halves hold different items of the same users: they insert one after the other
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    if (h == hh) {
-#pragma unroll
-                        for (int q = 0; q < 16; ++q)
-                            if ((pass >> q) & 1u) list_insert(ls, li, k, j, cnt, acc[q], (int)(base + row_of(q, h)));
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    cnt = __shfl(cnt, j + RT * hh, 64);
-                }
-                if (cnt == k) {
-                    thr_s = ls[(k - 1) * RT + j];
-                    thr_i = li[(k - 1) * RT + j];
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < D / 8; ++q) a[q] = an[q];
+        for (int q = 0; q < 16; ++q) {
+            const bool ok = lp.valid && ((elig >> q) & 1u) && better(acc[q], (int)(base + row_of(q, h)), thr_s, thr_i);
+            pass |= (unsigned)ok << q;
         }
-    }
-    if (!valid) return;
-    const int64_t o = (x * slices + slice) * k;
+        if (__any(pass != 0)) {
+            // the two lane halves hold different items of the same users: they insert one after the other
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                if (h == hh) {
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if ((pass >> q) & 1u) list_insert(ls, li, k, j, cnt, acc[q], (int)(base + row_of(q, h)));
+                }
+                __builtin_amdgcn_wave_barrier();
+                cnt = __shfl(cnt, j + RT * hh, 64);
+            }
+            if (cnt == k) {
+                thr_s = ls[(k - 1) * RT + j];
+                thr_i = li[(k - 1) * RT + j];
+            }
+        }
+    });
+    if (!lp.valid) return;                // an empty slice still writes its (empty) candidate slots and cand_n
+    const int64_t o = (lp.row * slices + lp.slice) * k;
     for (int q = h; q < k; q += 2) {
         const bool live = q < cnt;
         cand_s[o + q] = live ? ls[q * RT + j] : -INFINITY;
         cand_i[o + q] = live ? li[q * RT + j] : -1;
     }
-    if (h == 0) cand_n[x * slices + slice] = cnt;
+    if (h == 0) cand_n[lp.row * slices + lp.slice] = cnt;
 }
 
 // one thread per (user, slice, slot): the candidate's final position is its slot plus the number of strictly better
@@ -277,28 +297,32 @@ __global__ __launch_bounds__(256) void k_topk_merge(const float* __restrict__ ca
     for (int t = 0; t < slices && pos < k; ++t) {
         if (t == s) continue;
         const int64_t ot = (x * slices + t) * k;
-        int lo = 0, hi = cn[t];          // entries [0, lo) of slice t are better than the candidate
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (better(cand_s[ot + mid], cand_i[ot + mid], cs, ci)) lo = mid + 1; else hi = mid;
-        }
-        pos += lo;
+        // entries [0, lower bound) of slice t are better than the candidate
+        pos += lower_bound(0, cn[t], [&](int m) { return better(cand_s[ot + m], cand_i[ot + m], cs, ci); });
     }
     if (pos < k) { items[x * k + pos] = ci; scores[x * k + pos] = cs; }
 }
 
 constexpr int kRankWaves = 4;
 
-// slices (a multiple of 8, one XCD per residue) and tiles per slice for a grid of `groups` workgroup rows
-void plan_slices(int64_t groups, int64_t n_item, int64_t target_blocks, int max_mult, int* slices, int* slice_tiles) {
+// the grid of a catalogue walk over n users with `waves` waves per workgroup: `groups` workgroup rows x `slices` item
+// slices (a multiple of 8, one XCD per residue, about target_blocks workgroups in all) of slice_tiles tiles each
+struct SliceGrid {
+    int64_t groups;
+    int slices, slice_tiles;
+};
+
+SliceGrid plan_grid(int64_t n, int waves, int64_t n_item, int64_t target_blocks, int max_mult) {
+    const int64_t groups = (n + RT * waves - 1) / (RT * waves);
     const int64_t n_tiles = (n_item + RT - 1) / RT;
     int64_t m = (target_blocks + 8 * groups - 1) / (8 * groups);
     if (m < 1) m = 1;
     if (m > max_mult) m = max_mult;
     while (m > 1 && n_tiles / (8 * m) < 16) --m;      // keep at least 16 tiles per slice
-    *slices = (int)(8 * m);
-    *slice_tiles = (int)((n_tiles + 8 * m - 1) / (8 * m));
+    return {groups, (int)(8 * m), (int)((n_tiles + 8 * m - 1) / (8 * m))};
 }
+
+SliceGrid rank_grid(int64_t n, int waves, int64_t n_item) { return plan_grid(n, waves, n_item, 8192, 64); }
 
 int topk_waves(int k) {
     const int per_wave = 2 * k * RT * 4;
@@ -306,12 +330,13 @@ int topk_waves(int k) {
     return w > 4 ? 4 : w;
 }
 
-int topk_slices(int64_t n, int k, int64_t n_item, int* slice_tiles) {
-    int s, st;
-    const int64_t groups = (n + RT * topk_waves(k) - 1) / (RT * topk_waves(k));
-    plan_slices(groups, n_item, 2048, 4, &s, &st);
-    if (slice_tiles) *slice_tiles = st;
-    return s;
+SliceGrid topk_grid(int64_t n, int k, int64_t n_item) { return plan_grid(n, topk_waves(k), n_item, 2048, 4); }
+
+// the one place that turns the embedding width into a template argument: f(std::integral_constant<int, D>())
+template <class F>
+void with_width(int d, F&& f) {
+    if (d == 32) f(std::integral_constant<int, 32>());
+    else f(std::integral_constant<int, 64>());
 }
 
 // ---- per-user ranking of held-out sets ------------------------------------------------------------------------------
@@ -354,12 +379,9 @@ __global__ __launch_bounds__(256) void k_ur_thresholds(const float* __restrict__
     const int32_t p = pos_items[e];
     int sn = 0;
     if (seen_off) {
-        int64_t lo = seen_off[u], hi = seen_off[u + 1];
-        while (lo < hi) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (seen_items[mid] < p) lo = mid + 1; else hi = mid;
-        }
-        sn = lo < seen_off[u + 1] && seen_items[lo] == p;
+        const int64_t end = seen_off[u + 1];
+        const int64_t lo = lower_bound(seen_off[u], end, [&](int64_t m) { return seen_items[m] < p; });
+        sn = lo < end && seen_items[lo] == p;
     }
     seg[e] = (int32_t)x;
     ks[e] = score_chain<D>(wu + u * D, wi + (int64_t)p * D);
@@ -382,22 +404,9 @@ __global__ __launch_bounds__(256) void k_ur_merge(const int64_t* __restrict__ po
     const int64_t end = a0 + 2 * w < hi ? a0 + 2 * w : hi;
     const float s = is[e];
     const int32_t i = ii[e], xe = ix[e];
-    int64_t o;
-    if (e < mid) {
-        int64_t l = mid, h = end;          // keys of run B that are smaller: [mid, l)
-        while (l < h) {
-            const int64_t m = l + ((h - l) >> 1);
-            if (ur_less(is[m], ii[m], ix[m], s, i, xe)) l = m + 1; else h = m;
-        }
-        o = e + (l - mid);
-    } else {
-        int64_t l = a0, h = mid;
-        while (l < h) {
-            const int64_t m = l + ((h - l) >> 1);
-            if (ur_less(is[m], ii[m], ix[m], s, i, xe)) l = m + 1; else h = m;
-        }
-        o = a0 + (e - mid) + (l - a0);
-    }
+    const auto smaller = [&](int64_t m) { return ur_less(is[m], ii[m], ix[m], s, i, xe); };
+    // the entry's place in its own run plus the number of smaller keys of the other run
+    const int64_t o = e < mid ? e + (lower_bound(mid, end, smaller) - mid) : a0 + (e - mid) + (lower_bound(a0, mid, smaller) - a0);
     os[o] = s;
     oi[o] = i;
     ox[o] = xe;
@@ -411,21 +420,13 @@ __device__ __forceinline__ void ur_place(const float* ts, const int32_t* ti, int
                                          int t0i, int32_t* bp, int32_t* bd, int& c0, int& d0) {
     int64_t k = 0;
     if (!better(s, i, t0s, t0i)) {
-        int64_t l = 1, hh = mv - 1;        // t_0 is better or equal, t_{mv-1} is not
-        while (l < hh) {
-            const int64_t m = (l + hh) >> 1;
-            if (!better(s, i, ts[m * st], ti[m * st])) l = m + 1; else hh = m;
-        }
-        k = l;
+        // t_0 is better or equal, t_{mv-1} is not: neither is read
+        k = lower_bound<int64_t>(1, mv - 1, [&](int64_t m) { return !better(s, i, ts[m * st], ti[m * st]); });
     }
     const float tk = k ? ts[k * st] : t0s;
     if (k == 0) ++c0; else atomicAdd(bp + k * st, 1);
     if (!(s > tk)) {                       // s == t_k: thresholds k .. ka - 1 tie with s
-        int64_t l = k + 1, hh = mv;
-        while (l < hh) {
-            const int64_t m = (l + hh) >> 1;
-            if (!(s > ts[m * st])) l = m + 1; else hh = m;
-        }
+        const int64_t l = lower_bound(k + 1, mv, [&](int64_t m) { return !(s > ts[m * st]); });
         if (k == 0) --d0; else atomicAdd(bd + k * st, -1);
         if (l < mv) atomicAdd(bd + l * st, 1);
     }
@@ -445,22 +446,13 @@ __global__ __launch_bounds__(64 * kUrWaves) void k_ur_count(const float* __restr
     __shared__ int32_t l_i[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_p[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_d[kUrWaves][kUrWin * RT];
-    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31, wave = threadIdx.x >> 6;
-    const int slice = blockIdx.x % slices;
-    const int64_t x = ((int64_t)(blockIdx.x / slices) * kUrWaves + wave) * RT + j;
-    const bool valid = x < n;
-    const int64_t xx = valid ? x : n - 1;
-    const int64_t u = users[xx];
-    const int64_t lo = pos_off[xx];
-    int64_t mv = 0;                        // non-NaN thresholds (the NaN ones sort last)
-    {
-        int64_t l = 0, hh = valid ? pos_off[xx + 1] - lo : 0;
-        while (l < hh) {
-            const int64_t m = l + ((hh - l) >> 1);
-            if (ss[lo + m] == ss[lo + m]) l = m + 1; else hh = m;
-        }
-        mv = l;
-    }
+    const LanePos lp = lane_pos(slices, kUrWaves, n);
+    const int h = lp.h, j = lp.j, wave = lp.wave;
+    const bool valid = lp.valid;
+    const int64_t u = users[lp.rc];
+    const int64_t lo = pos_off[lp.rc];
+    // non-NaN thresholds (the NaN ones sort last)
+    const int64_t mv = lower_bound<int64_t>(0, valid ? pos_off[lp.rc + 1] - lo : 0, [&](int64_t m) { return ss[lo + m] == ss[lo + m]; });
     // users with at most kUrWin thresholds: thresholds and bins in LDS column j; longer sets: the user's global range
     const bool win = mv <= kUrWin;
     for (int k = h; k < kUrWin; k += 2) {
@@ -473,52 +465,27 @@ __global__ __launch_bounds__(64 * kUrWaves) void k_ur_count(const float* __restr
     const float t0s = mv ? ss[lo] : 0.0f, tws = mv ? ss[lo + mv - 1] : 0.0f;
     const int t0i = mv ? si[lo] : 0, twi = mv ? si[lo + mv - 1] : 0;
     int c0 = 0, d0 = 0;
-    const int64_t n_tiles = (n_item + RT - 1) / RT;
-    const int64_t t0 = (int64_t)slice * slice_tiles;
-    const int64_t t1 = t0 + slice_tiles < n_tiles ? t0 + slice_tiles : n_tiles;
-    if (t0 < t1) {
-        f32x4 b[D / 8];
-        load_half<D>(wu + u * D, h, b);
-        SeenCursor sc;
-        sc.init(seen_off, seen_items, u, t0 * RT);
-        f32x4 a[D / 8], an[D / 8];
-        int64_t ia = t0 * RT + j;
-        load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, h, a);
-        for (int64_t t = t0; t < t1; ++t) {
-            if (t + 1 < t1) {
-                ia = (t + 1) * RT + j;
-                load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, h, an);
-            }
-            const f32x16 acc = tile_scores<D>(a, b);
-            const int64_t base = t * RT;
-            const unsigned wd = sc.word(base);
-            unsigned live = 0;             // NaN scores fail `better`; an item not better than the worst threshold is in no bin
-            if (mv) {
+    walk_slice<D>(wu, wi, n_item, u, seen_off, seen_items, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
+        unsigned live = 0;                 // NaN scores fail `better`; an item not better than the worst threshold is in no bin
+        if (mv) {
 #pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int r = row_of(q, h);
-                    live |= (unsigned)(!((wd >> r) & 1u) && base + r < n_item && better(acc[q], (int)(base + r), tws, twi)) << q;
-                }
-            }
-            if (live) {
-                if (win) {
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        if ((live >> q) & 1u)
-                            ur_place(&l_s[wave][j], &l_i[wave][j], RT, mv, acc[q], (int)(base + row_of(q, h)), t0s, t0i,
-                                     &l_p[wave][j], &l_d[wave][j], c0, d0);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        if ((live >> q) & 1u)
-                            ur_place(ss + lo, si + lo, 1, mv, acc[q], (int)(base + row_of(q, h)), t0s, t0i, bin_p + lo,
-                                     bin_d + lo, c0, d0);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < D / 8; ++q) a[q] = an[q];
+            for (int q = 0; q < 16; ++q) live |= (unsigned)better(acc[q], (int)(base + row_of(q, h)), tws, twi) << q;
+            live &= elig;
         }
-    }
+        if (!live) return;
+        if (win) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if ((live >> q) & 1u)
+                    ur_place(&l_s[wave][j], &l_i[wave][j], RT, mv, acc[q], (int)(base + row_of(q, h)), t0s, t0i, &l_p[wave][j],
+                             &l_d[wave][j], c0, d0);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if ((live >> q) & 1u)
+                    ur_place(ss + lo, si + lo, 1, mv, acc[q], (int)(base + row_of(q, h)), t0s, t0i, bin_p + lo, bin_d + lo, c0, d0);
+        }
+    });
     c0 += __shfl_xor(c0, 32, 64);
     d0 += __shfl_xor(d0, 32, 64);
     if (valid && h == 0) {
@@ -656,38 +623,34 @@ hipError_t sml_launch_full_rank(int d, const float* wu, const float* wi, int64_t
                                 const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, hipStream_t st) {
     hipError_t e = hipMemsetAsync(rank, 0, n * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
-    const int64_t groups = (n + RT * kRankWaves - 1) / (RT * kRankWaves);
-    int slices, slice_tiles;
-    plan_slices(groups, n_item, 8192, 64, &slices, &slice_tiles);
-    const dim3 grid((unsigned)(groups * slices)), block(64 * kRankWaves);
-    if (d == 32)
-        k_full_rank<32><<<grid, block, 0, st>>>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank);
-    else
-        k_full_rank<64><<<grid, block, 0, st>>>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank);
+    const SliceGrid g = rank_grid(n, kRankWaves, n_item);
+    const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kRankWaves);
+    with_width(d, [&](auto dd) {
+        k_full_rank<decltype(dd)::value><<<grid, block, 0, st>>>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, g.slices,
+                                                                g.slice_tiles, rank);
+    });
     return hipGetLastError();
 }
 
 int64_t sml_topk_scratch_size(int64_t n, int k, int64_t n_item) {
-    const int64_t s = topk_slices(n, k, n_item, nullptr);
+    const int64_t s = topk_grid(n, k, n_item).slices;
     return n * s * (int64_t)k * 8 + n * s * 4;
 }
 
 hipError_t sml_launch_topk(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* users, int64_t n, int k,
                            const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores,
                            hipStream_t st) {
-    int slice_tiles;
-    const int slices = topk_slices(n, k, n_item, &slice_tiles);
-    const int waves = topk_waves(k);
-    const int64_t groups = (n + RT * waves - 1) / (RT * waves);
+    const SliceGrid g = topk_grid(n, k, n_item);
+    const int slices = g.slices, waves = topk_waves(k);
     float* cs = static_cast<float*>(scratch);
     int32_t* ci = reinterpret_cast<int32_t*>(cs + n * slices * k);
     int32_t* cn = ci + n * slices * k;
-    const dim3 grid((unsigned)(groups * slices)), block(64 * waves);
+    const dim3 grid((unsigned)(g.groups * slices)), block(64 * waves);
     const size_t lds = (size_t)waves * 2 * k * RT * 4;
-    if (d == 32)
-        k_topk_slice<32><<<grid, block, lds, st>>>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cs, ci, cn);
-    else
-        k_topk_slice<64><<<grid, block, lds, st>>>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cs, ci, cn);
+    with_width(d, [&](auto dd) {
+        k_topk_slice<decltype(dd)::value><<<grid, block, lds, st>>>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices,
+                                                                   g.slice_tiles, cs, ci, cn);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int64_t threads = n * slices * k;
@@ -715,10 +678,10 @@ hipError_t sml_launch_user_rank(int d, const float* wu, const float* wi, int64_t
     hipError_t e = hipMemsetAsync(bin_p, 0, 2 * pc, st);
     if (e != hipSuccess) return e;
     const dim3 eg((unsigned)((n_pos + 255) / 256)), eb(256);
-    if (d == 32)
-        k_ur_thresholds<32><<<eg, eb, 0, st>>>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks[0], ki[0], kx[0], in_seen);
-    else
-        k_ur_thresholds<64><<<eg, eb, 0, st>>>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks[0], ki[0], kx[0], in_seen);
+    with_width(d, [&](auto dd) {
+        k_ur_thresholds<decltype(dd)::value><<<eg, eb, 0, st>>>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg,
+                                                               ks[0], ki[0], kx[0], in_seen);
+    });
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // a user's range is at most n_pos long: ceil(log2 n_pos) merge passes sort every range
     int cur = 0;
@@ -726,16 +689,12 @@ hipError_t sml_launch_user_rank(int d, const float* wu, const float* wi, int64_t
         k_ur_merge<<<eg, eb, 0, st>>>(pos_off, seg, n_pos, w, ks[cur], ki[cur], kx[cur], ks[cur ^ 1], ki[cur ^ 1], kx[cur ^ 1]);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    const int64_t groups = (n + RT * kUrWaves - 1) / (RT * kUrWaves);
-    int slices, slice_tiles;
-    plan_slices(groups, n_item, 8192, 64, &slices, &slice_tiles);
-    const dim3 grid((unsigned)(groups * slices)), block(64 * kUrWaves);
-    if (d == 32)
-        k_ur_count<32><<<grid, block, 0, st>>>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles,
-                                               ks[cur], ki[cur], bin_p, bin_d);
-    else
-        k_ur_count<64><<<grid, block, 0, st>>>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles,
-                                               ks[cur], ki[cur], bin_p, bin_d);
+    const SliceGrid g = rank_grid(n, kUrWaves, n_item);
+    const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kUrWaves);
+    with_width(d, [&](auto dd) {
+        k_ur_count<decltype(dd)::value><<<grid, block, 0, st>>>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, g.slices,
+                                                               g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
+    });
     if ((e = hipGetLastError()) != hipSuccess) return e;
     k_ur_finish<<<dim3((unsigned)n), dim3(kUrBlock), 0, st>>>(pos_off, ks[cur], kx[cur], in_seen, bin_p, bin_d, above, pos);
     return hipGetLastError();

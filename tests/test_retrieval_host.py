@@ -261,7 +261,8 @@ def test_planner_mirror_reaches_the_named_geometry():
     with open(os.path.join(REPO, "sml_amd", "csrc", "retrieval.hip")) as f:
         src = f.read()
     for line in ("while (m > 1 && n_tiles / (8 * m) < 16) --m;", "return w > 4 ? 4 : w;",
-                 "plan_slices(groups, n_item, 2048, 4, &s, &st);", "plan_slices(groups, n_item, 8192, 64, &slices, &slice_tiles);",
+                 "const int64_t groups = (n + RT * waves - 1) / (RT * waves);",
+                 "return plan_grid(n, topk_waves(k), n_item, 2048, 4);", "return plan_grid(n, waves, n_item, 8192, 64);",
                  "const int per_wave = 2 * k * RT * 4;", "constexpr int kRankWaves = 4;"):
         assert line in src, line
     assert {F.topk_waves(k) for k in (1, 2, 63, 64, 65, 85, 86, 127, 128)} == {4, 3, 2}
