@@ -428,7 +428,8 @@ int sml_eval_metrics(sml_ctx* ctx, const int32_t* rank, int64_t n, int topk, flo
  * The order pairs dim s with dim s + d/2: acc = 0; for s = 0 .. d/2 - 1 { acc = fmaf(x[s], u[s], acc);
  * acc = fmaf(x[s + d/2], u[s + d/2], acc); } with u = w_user[u], x = w_item[i], each fmaf rounded once (round to
  * nearest even, subnormals kept).
- * d (the ctx's) must be 32 or 64; 0 < n_item < 2^31.  Seen(u), the items excluded for user u, is a CSR over users:
+ * d (the ctx's) must be 32 or 64 for these fp32 entry points (the _f16 entry points below also take 128);
+ * 0 < n_item < 2^31.  Seen(u), the items excluded for user u, is a CSR over users:
  * seen_off int64 [n_user + 1], seen_items int32 ascending and unique inside each user's range; both NULL = nothing
  * excluded, exactly one NULL is refused.  Exclusion is by item id, never by score.  Indices are trusted.
  *
@@ -467,6 +468,28 @@ int sml_user_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_
                   const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
                   const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos,
                   void* stream);
+/* The same three calls on HALF-PRECISION tables (IEEE binary16, row-major [rows, d], as sml_embed_loss_sgd_epoch trains
+ * them with elem_bytes = 2): sml_full_rank_f16, sml_topk_items_f16, sml_user_rank_f16.  d (the ctx's) must be 32, 64 or
+ * 128; fp32 tables at d = 128 stay refused by the entry points above.  Widening rule: every table entry is widened
+ * EXACTLY to fp32 (each fp16 value -- subnormals, +-0, +-inf and NaN included -- is an fp32 value) and S(u, i) is the
+ * fmaf chain defined above on the widened entries, accumulated in fp32: same dim order, each fmaf rounded once,
+ * subnormals kept.  No fp32 copy of a table is made; rows are read as packed halves.  At d = 32 and d = 64 every output
+ * equals, bit for bit, the output of the fp32 entry point on fp32 copies of the same tables; at d = 128 the same
+ * definition holds.  Everything else carries over verbatim: Seen and its rules, the NaN rules, the (score descending,
+ * id ascending) order, (-1, -inf) padding, rank / above / pos, 1 <= k <= 128, determinism, and the scratch sizes --
+ * sml_topk_scratch_bytes and sml_user_rank_scratch_bytes serve both element types.  scores stay float32.
+ * sml_user_metrics reads no table and serves both. */
+int sml_full_rank_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
+                      const int64_t* rows, int64_t n, int n_cols,
+                      const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, void* stream);
+int sml_topk_items_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
+                       const int64_t* users, int64_t n, int k,
+                       const int64_t* seen_off, const int32_t* seen_items,
+                       void* scratch, int32_t* items, float* scores, void* stream);
+int sml_user_rank_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
+                      const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
+                      const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos,
+                      void* stream);
 /* Per-user metrics from pos (as sml_user_rank writes it; any value < 0 is never a hit) over the ranges of pos_off,
  * n < 2^31.  ks: HOST int32 [n_k], 1 <= n_k <= 8, every K >= 1.  For user x with m = |T(x)| and each K (outputs [n, n_k], row-major):
  *   hits = #{p : 0 <= pos(p) < K};  dcg = sum over hits of 1/log2(pos + 2), fp32, summed in ascending pos;

@@ -110,6 +110,12 @@ SIGNATURES = {
     "sml_user_rank_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     "sml_user_rank": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64,
                                      c_void, c_void, c_void, c_void, c_void, c_void]),
+    "sml_full_rank_f16": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
+                                         c_void, c_void]),
+    "sml_topk_items_f16": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
+                                          c_void, c_void, c_void, c_void]),
+    "sml_user_rank_f16": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64,
+                                         c_void, c_void, c_void, c_void, c_void, c_void]),
     "sml_user_metrics": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,
                                         c_void]),
     "sml_stream_create_cu_range": (ctypes.c_int, [ctypes.POINTER(c_void), ctypes.c_int, ctypes.c_int, ctypes.c_int]),

@@ -1694,17 +1694,30 @@ int sml_eval_metrics(sml_ctx* ctx, const int32_t* rank, int64_t n, int topk, flo
         return SML_OK;                         \
     } while (0)
 
-static bool retrieval_args_ok(sml_ctx* ctx, int64_t n_item, const int64_t* seen_off, const int32_t* seen_items) {
-    return ctx && (ctx->d == 32 || ctx->d == 64) && n_item > 0 && n_item < ((int64_t)1 << 31) && (!seen_off) == (!seen_items);
+// elem_bytes: 4 for the fp32 entry points (d = 32 / 64), 2 for the _f16 ones (d = 32 / 64 / 128)
+static bool retrieval_args_ok(sml_ctx* ctx, int elem_bytes, int64_t n_item, const int64_t* seen_off, const int32_t* seen_items) {
+    return ctx && sml_retrieval_supports(ctx->d, elem_bytes) && n_item > 0 && n_item < ((int64_t)1 << 31) && (!seen_off) == (!seen_items);
+}
+
+// every table-reading entry point exists twice over one body: `what` names the caller, elem_bytes its tables
+static int full_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
+                          const int64_t* rows, int64_t n, int n_cols, const int64_t* seen_off, const int32_t* seen_items,
+                          int32_t* rank, void* stream) {
+    if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || n_cols < 2 || n < 0)
+        return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, n_cols >= 2, seen_off and seen_items both or neither)");
+    if (n == 0) return SML_OK;
+    if (!w_user || !w_item || !rows || !rank) return fail(SML_EINVAL, what, "null argument");
+    RUN_MISC(ctx, stream, sml_launch_full_rank(ctx->d, elem_bytes, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, st));
 }
 
 int sml_full_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* rows, int64_t n,
                   int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, void* stream) {
-    if (!retrieval_args_ok(ctx, n_item, seen_off, seen_items) || n_cols < 2 || n < 0)
-        return fail(SML_EINVAL, "sml_full_rank", "bad argument (d must be 32/64, 0 < n_item < 2^31, n_cols >= 2, seen_off and seen_items both or neither)");
-    if (n == 0) return SML_OK;
-    if (!w_user || !w_item || !rows || !rank) return fail(SML_EINVAL, "sml_full_rank", "null argument");
-    RUN_MISC(ctx, stream, sml_launch_full_rank(ctx->d, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, st));
+    return full_rank_impl("sml_full_rank", 4, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, stream);
+}
+
+int sml_full_rank_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* rows, int64_t n,
+                      int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, void* stream) {
+    return full_rank_impl("sml_full_rank_f16", 2, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, stream);
 }
 
 int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item) {
@@ -1712,13 +1725,24 @@ int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item) {
     return n == 0 ? 0 : sml_topk_scratch_size(n, k, n_item);
 }
 
+static int topk_items_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
+                           const int64_t* users, int64_t n, int k, const int64_t* seen_off, const int32_t* seen_items,
+                           void* scratch, int32_t* items, float* scores, void* stream) {
+    if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || k < 1 || k > 128 || n < 0)
+        return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 1 <= k <= 128, 0 < n_item < 2^31, seen_off and seen_items both or neither)");
+    if (n == 0) return SML_OK;
+    if (!w_user || !w_item || !users || !scratch || !items || !scores) return fail(SML_EINVAL, what, "null argument");
+    RUN_MISC(ctx, stream, sml_launch_topk(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, st));
+}
+
 int sml_topk_items(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
                    const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores, void* stream) {
-    if (!retrieval_args_ok(ctx, n_item, seen_off, seen_items) || k < 1 || k > 128 || n < 0)
-        return fail(SML_EINVAL, "sml_topk_items", "bad argument (d must be 32/64, 1 <= k <= 128, 0 < n_item < 2^31, seen_off and seen_items both or neither)");
-    if (n == 0) return SML_OK;
-    if (!w_user || !w_item || !users || !scratch || !items || !scores) return fail(SML_EINVAL, "sml_topk_items", "null argument");
-    RUN_MISC(ctx, stream, sml_launch_topk(ctx->d, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, st));
+    return topk_items_impl("sml_topk_items", 4, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, stream);
+}
+
+int sml_topk_items_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
+                       const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores, void* stream) {
+    return topk_items_impl("sml_topk_items_f16", 2, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, stream);
 }
 
 int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int64_t n_item) {
@@ -1728,17 +1752,32 @@ int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int6
     return n == 0 || n_pos == 0 ? 0 : sml_user_rank_scratch_size(n_pos);
 }
 
+static int user_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
+                          const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
+                          const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos,
+                          void* stream) {
+    if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || n < 0 || n >= ((int64_t)1 << 31) || n_pos < 0 ||
+        n_pos >= ((int64_t)1 << 31))
+        return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, 0 <= n, n_pos < 2^31, seen_off and seen_items both or neither)");
+    if (n == 0 || n_pos == 0) return SML_OK;
+    if (!w_user || !w_item || !users || !pos_off || !pos_items || !scratch || !above || !pos)
+        return fail(SML_EINVAL, what, "null argument");
+    RUN_MISC(ctx, stream, sml_launch_user_rank(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
+                                               seen_items, scratch, above, pos, st));
+}
+
 int sml_user_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n,
                   const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                   const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, void* stream) {
-    if (!retrieval_args_ok(ctx, n_item, seen_off, seen_items) || n < 0 || n >= ((int64_t)1 << 31) || n_pos < 0 ||
-        n_pos >= ((int64_t)1 << 31))
-        return fail(SML_EINVAL, "sml_user_rank", "bad argument (d must be 32/64, 0 < n_item < 2^31, 0 <= n, n_pos < 2^31, seen_off and seen_items both or neither)");
-    if (n == 0 || n_pos == 0) return SML_OK;
-    if (!w_user || !w_item || !users || !pos_off || !pos_items || !scratch || !above || !pos)
-        return fail(SML_EINVAL, "sml_user_rank", "null argument");
-    RUN_MISC(ctx, stream, sml_launch_user_rank(ctx->d, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off, seen_items,
-                                               scratch, above, pos, st));
+    return user_rank_impl("sml_user_rank", 4, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off, seen_items,
+                          scratch, above, pos, stream);
+}
+
+int sml_user_rank_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,
+                      const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
+                      const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, void* stream) {
+    return user_rank_impl("sml_user_rank_f16", 2, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
+                          seen_items, scratch, above, pos, stream);
 }
 
 int sml_user_metrics(sml_ctx* ctx, const int32_t* pos, const int64_t* pos_off, int64_t n, const int32_t* ks, int n_k,

@@ -9,6 +9,13 @@
 // order (dims 0, D/2, 1, D/2 + 1, ..., each fmaf rounded once, subnormals kept) is part of the contract in sml_hip.h;
 // tests/test_retrieval_gpu.py compares ranks, lists and score bits with an exact emulation of it.
 //
+// Element type: fp32 tables (D = 32 / 64) or fp16 tables (D = 32 / 64 / 128).  A half row travels and stays packed: a
+// lane half's D/2 dims are D/16 16-byte loads of eight halves, and the user row, the current and the next item tile sit
+// in registers that way (3 D/4 VGPRs instead of 3 D/2).  A half is widened to fp32 (exact: every fp16 value is an fp32
+// value) only where it feeds an fmaf or the fp32 MFMA, so S(u, i) on fp16 tables is the same chain on the widened entries
+// and equals the fp32 kernels' score of the widened tables bit for bit.  The element type is a parameter of the walk's
+// loads (HalfRow); the fp16 kernels are the k_*_h entry points over the same bodies.
+//
 // Grid: (32 * W users) x slices; slice = blockIdx % slices, so with slices a multiple of 8 an XCD walks 1/8 of the
 // item table (plan_grid on the host, lane_pos on the device).  Every wave owns 32 users.
 //
@@ -53,9 +60,12 @@ namespace {
 
 constexpr int RT = 32;         // items per score tile = users per wave
 
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
 // S(u, i) in the k order of tile_scores(): the device-side definition every retrieval kernel agrees with, bit for bit
-template <int D>
-__device__ __forceinline__ float score_chain(const float* __restrict__ u, const float* __restrict__ x) {
+// (T = _Float16: x[s] and u[s] convert to float, exactly, as fmaf's arguments)
+template <int D, class T>
+__device__ __forceinline__ float score_chain(const T* __restrict__ u, const T* __restrict__ x) {
     float acc = 0.0f;
 #pragma unroll
     for (int s = 0; s < D / 2; ++s) {
@@ -65,23 +75,48 @@ __device__ __forceinline__ float score_chain(const float* __restrict__ u, const 
     return acc;
 }
 
+// The D/2 dims a lane half owns of one table row, as its 16-byte loads bring them: at(s) = dim h D/2 + s as fp32
+template <int D, class T>
+struct HalfRow;
+
 template <int D>
-__device__ __forceinline__ void load_half(const float* __restrict__ row, int h, f32x4 (&f)[D / 8]) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(row + h * (D / 2));
+struct HalfRow<D, float> {
+    f32x4 f[D / 8];
+    __device__ __forceinline__ void load(const float* __restrict__ row, int h) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(row + h * (D / 2));
 #pragma unroll
-    for (int q = 0; q < D / 8; ++q) f[q] = p[q];
-}
+        for (int q = 0; q < D / 8; ++q) f[q] = p[q];
+    }
+    __device__ __forceinline__ float at(int s) const { return f[s >> 2][s & 3]; }
+    __device__ __forceinline__ void keep_packed() {}
+};
+
+// fp16 rows stay packed, eight dims per load and four VGPRs; a value is widened where it is used
+template <int D>
+struct HalfRow<D, _Float16> {
+    f16x8 f[D / 16];
+    __device__ __forceinline__ void load(const _Float16* __restrict__ row, int h) {
+        const f16x8* p = reinterpret_cast<const f16x8*>(row + h * (D / 2));
+#pragma unroll
+        for (int q = 0; q < D / 16; ++q) f[q] = p[q];
+    }
+    __device__ __forceinline__ float at(int s) const { return (float)f[s >> 3][s & 7]; }
+    // called on a row that outlives a loop: the widened copy of a loop-invariant row (D/2 more VGPRs) would otherwise be
+    // hoisted out of the loop and held beside the packed one
+    __device__ __forceinline__ void keep_packed() {
+#pragma unroll
+        for (int q = 0; q < D / 16; ++q) asm volatile("" : "+v"(f[q]));
+    }
+};
 
 // 32 items (A) x 32 users (B): acc[r] = S(user lane & 31, item row_of(r, lane >> 5))
-template <int D>
-__device__ __forceinline__ f32x16 tile_scores(const f32x4 (&a)[D / 8], const f32x4 (&b)[D / 8]) {
+template <int D, class T>
+__device__ __forceinline__ f32x16 tile_scores(const HalfRow<D, T>& a, const HalfRow<D, T>& b) {
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
 #pragma unroll
-    for (int q = 0; q < D / 8; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q][e], b[q][e], acc, 0, 0, 0);
+    for (int s = 0; s < D / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.at(s), b.at(s), acc, 0, 0, 0);
     return acc;
 }
 
@@ -154,41 +189,43 @@ __device__ __forceinline__ LanePos lane_pos(int slices, int waves, int64_t n) {
 // The catalogue walk of one wave: user u's scores against every 32-item tile of the lane's slice, next tile's item rows
 // in flight under the current tile's MFMAs.  tile(acc, base, elig) runs once per tile: acc[q] = S(u, base + row_of(q, h)),
 // bit q of elig set <=> that item exists (< n_item) and is not in Seen(u).  An empty slice loads nothing and calls nothing.
-template <int D, class Tile>
-__device__ __forceinline__ void walk_slice(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item, int64_t u,
+template <int D, class T, class Tile>
+__device__ __forceinline__ void walk_slice(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item, int64_t u,
                                            const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
                                            const LanePos& lp, int slice_tiles, Tile&& tile) {
     const int64_t n_tiles = (n_item + RT - 1) / RT;
     const int64_t t0 = (int64_t)lp.slice * slice_tiles;
     const int64_t t1 = t0 + slice_tiles < n_tiles ? t0 + slice_tiles : n_tiles;
     if (t0 >= t1) return;
-    f32x4 b[D / 8];
-    load_half<D>(wu + u * D, lp.h, b);
+    HalfRow<D, T> b;
+    b.load(wu + u * D, lp.h);
     SeenCursor sc;
     sc.init(seen_off, seen_items, u, t0 * RT);
-    f32x4 a[D / 8], an[D / 8];
+    HalfRow<D, T> a, an;
     int64_t ia = t0 * RT + lp.j;
-    load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h, a);
+    a.load(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h);
     for (int64_t t = t0; t < t1; ++t) {
         if (t + 1 < t1) {
             ia = (t + 1) * RT + lp.j;
-            load_half<D>(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h, an);
+            an.load(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h);
         }
-        const f32x16 acc = tile_scores<D>(a, b);
+        b.keep_packed();
+        const f32x16 acc = tile_scores<D, T>(a, b);
         const int64_t base = t * RT;
         const int64_t left = n_item - base;              // >= 1; bit i of `real`: item base + i exists and is not in Seen
         const unsigned real = ~sc.word(base) & (left < RT ? (1u << left) - 1u : ~0u);
         tile(acc, base, lane_rows(real, lp.h));
-#pragma unroll
-        for (int q = 0; q < D / 8; ++q) a[q] = an[q];
+        a = an;
     }
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void k_full_rank(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                   const int64_t* __restrict__ rows, int64_t n, int n_cols,
-                                                   const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                   int slices, int slice_tiles, int32_t* __restrict__ rank) {
+// The kernels below are bodies over the element type T; each has two __global__ entry points, k_x<D> on fp32 tables and
+// k_x_h<D> on fp16 tables.
+template <int D, class T>
+__device__ __forceinline__ void full_rank_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                               const int64_t* __restrict__ rows, int64_t n, int n_cols,
+                                               const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                               int slices, int slice_tiles, int32_t* __restrict__ rank) {
     const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
     const int64_t u = rows[lp.rc * n_cols], p = rows[lp.rc * n_cols + 1];
     const float thr = score_chain<D>(wu + u * D, wi + p * D);
@@ -199,6 +236,22 @@ __global__ __launch_bounds__(256) void k_full_rank(const float* __restrict__ wu,
     });
     cnt += __shfl_xor(cnt, 32, 64);
     if (lp.h == 0 && lp.valid && cnt) atomicAdd(rank + lp.row, cnt);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_full_rank(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                   const int64_t* __restrict__ rows, int64_t n, int n_cols,
+                                                   const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                   int slices, int slice_tiles, int32_t* __restrict__ rank) {
+    full_rank_body<D>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_full_rank_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
+                                                     const int64_t* __restrict__ rows, int64_t n, int n_cols,
+                                                     const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                     int slices, int slice_tiles, int32_t* __restrict__ rank) {
+    full_rank_body<D>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank);
 }
 
 // insert (s, i) into user j's list (k slots, column j of [k][32] arrays); cnt = live entries
@@ -223,12 +276,12 @@ __device__ __forceinline__ void list_insert(float* ls, int* li, int k, int j, in
 }
 
 // candidates of user x, slice s: cand_s / cand_i [(x * slices + s) * k + q], cand_n [x * slices + s]
-template <int D>
-__global__ __launch_bounds__(256) void k_topk_slice(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                    const int64_t* __restrict__ users, int64_t n, int k,
-                                                    const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                    int slices, int slice_tiles, float* __restrict__ cand_s,
-                                                    int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n) {
+template <int D, class T>
+__device__ __forceinline__ void topk_slice_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                                const int64_t* __restrict__ users, int64_t n, int k,
+                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                int slices, int slice_tiles, float* __restrict__ cand_s,
+                                                int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n) {
     extern __shared__ float lds[];
     const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
     const int h = lp.h, j = lp.j;
@@ -271,6 +324,24 @@ __global__ __launch_bounds__(256) void k_topk_slice(const float* __restrict__ wu
         cand_i[o + q] = live ? li[q * RT + j] : -1;
     }
     if (h == 0) cand_n[lp.row * slices + lp.slice] = cnt;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_topk_slice(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                    const int64_t* __restrict__ users, int64_t n, int k,
+                                                    const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                    int slices, int slice_tiles, float* __restrict__ cand_s,
+                                                    int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n) {
+    topk_slice_body<D>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_topk_slice_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
+                                                      const int64_t* __restrict__ users, int64_t n, int k,
+                                                      const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                      int slices, int slice_tiles, float* __restrict__ cand_s,
+                                                      int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n) {
+    topk_slice_body<D>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n);
 }
 
 // one thread per (user, slice, slot): the candidate's final position is its slot plus the number of strictly better
@@ -332,12 +403,34 @@ int topk_waves(int k) {
 
 SliceGrid topk_grid(int64_t n, int k, int64_t n_item) { return plan_grid(n, topk_waves(k), n_item, 2048, 4); }
 
-// the one place that turns the embedding width into a template argument: f(std::integral_constant<int, D>())
+// the one place that turns the embedding width and the element type into template arguments: f(D, wu, wi) with D a
+// std::integral_constant and the tables typed (fp32: d = 32 / 64; fp16, elem_bytes 2: d = 32 / 64 / 128).  false: a pair
+// the kernels do not exist for, nothing was called -- the launchers' refusal, and what sml_retrieval_supports asks
 template <class F>
-void with_width(int d, F&& f) {
-    if (d == 32) f(std::integral_constant<int, 32>());
-    else f(std::integral_constant<int, 64>());
+bool with_width(int d, int elem_bytes, const void* wu, const void* wi, F&& f) {
+    const auto typed = [&](auto dd, auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        f(dd, static_cast<const T*>(wu), static_cast<const T*>(wi));
+        return true;
+    };
+    if (elem_bytes == 4) {
+        if (d == 32) return typed(std::integral_constant<int, 32>(), (float*)nullptr);
+        if (d == 64) return typed(std::integral_constant<int, 64>(), (float*)nullptr);
+    } else if (elem_bytes == 2) {
+        if (d == 32) return typed(std::integral_constant<int, 32>(), (_Float16*)nullptr);
+        if (d == 64) return typed(std::integral_constant<int, 64>(), (_Float16*)nullptr);
+        if (d == 128) return typed(std::integral_constant<int, 128>(), (_Float16*)nullptr);
+    }
+    return false;
 }
+
+// inside with_width's callable: launch k_x<D> when the typed user table tu is fp32, k_x_h<D> when it is fp16.  (A macro
+// because only the taken branch may name its kernel: a function taking both kernels would instantiate k_x<128> on fp32.)
+#define LAUNCH_TYPED(name, D, tu, grid, block, lds, st, ...)                                                              \
+    do {                                                                                                                  \
+        if constexpr (std::is_same<decltype(tu), const float*>::value) name<D><<<grid, block, lds, st>>>(__VA_ARGS__);    \
+        else name##_h<D><<<grid, block, lds, st>>>(__VA_ARGS__);                                                          \
+    } while (0)
 
 // ---- per-user ranking of held-out sets ------------------------------------------------------------------------------
 
@@ -364,14 +457,14 @@ __device__ __forceinline__ int64_t ur_segment(const int64_t* __restrict__ off, i
     return lo;
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void k_ur_thresholds(const float* __restrict__ wu, const float* __restrict__ wi,
-                                                       const int64_t* __restrict__ users, int64_t n,
-                                                       const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
-                                                       int64_t n_pos, const int64_t* __restrict__ seen_off,
-                                                       const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
-                                                       float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
-                                                       int32_t* __restrict__ in_seen) {
+template <int D, class T>
+__device__ __forceinline__ void ur_thresholds_body(const T* __restrict__ wu, const T* __restrict__ wi,
+                                                   const int64_t* __restrict__ users, int64_t n,
+                                                   const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
+                                                   int64_t n_pos, const int64_t* __restrict__ seen_off,
+                                                   const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
+                                                   float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
+                                                   int32_t* __restrict__ in_seen) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_pos) return;
     const int64_t x = ur_segment(pos_off, n, e);
@@ -388,6 +481,28 @@ __global__ __launch_bounds__(256) void k_ur_thresholds(const float* __restrict__
     ki[e] = p;
     kx[e] = (int32_t)e;
     in_seen[e] = sn;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_ur_thresholds(const float* __restrict__ wu, const float* __restrict__ wi,
+                                                       const int64_t* __restrict__ users, int64_t n,
+                                                       const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
+                                                       int64_t n_pos, const int64_t* __restrict__ seen_off,
+                                                       const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
+                                                       float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
+                                                       int32_t* __restrict__ in_seen) {
+    ur_thresholds_body<D>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_ur_thresholds_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
+                                                         const int64_t* __restrict__ users, int64_t n,
+                                                         const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
+                                                         int64_t n_pos, const int64_t* __restrict__ seen_off,
+                                                         const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
+                                                         float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
+                                                         int32_t* __restrict__ in_seen) {
+    ur_thresholds_body<D>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen);
 }
 
 // runs [a0, a0 + w) and [a0 + w, a0 + 2w) of every user's range -> one sorted run
@@ -434,14 +549,13 @@ __device__ __forceinline__ void ur_place(const float* ts, const int32_t* ti, int
 
 // ss / si: every user's thresholds and ids in ur_less order.  At sorted place b of user x, bin_p (zeroed) receives the
 // number of eligible items whose pos bound is b, and bin_d (zeroed) what turns those counts into the above bounds'
-template <int D>
-__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                            const int64_t* __restrict__ users, int64_t n,
-                                                            const int64_t* __restrict__ pos_off,
-                                                            const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                            int slices, int slice_tiles, const float* __restrict__ ss,
-                                                            const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
-                                                            int32_t* __restrict__ bin_d) {
+template <int D, class T>
+__device__ __forceinline__ void ur_count_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                              const int64_t* __restrict__ users, int64_t n, const int64_t* __restrict__ pos_off,
+                                              const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                              int slices, int slice_tiles, const float* __restrict__ ss,
+                                              const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
+                                              int32_t* __restrict__ bin_d) {
     __shared__ float l_s[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_i[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_p[kUrWaves][kUrWin * RT];
@@ -500,6 +614,28 @@ __global__ __launch_bounds__(64 * kUrWaves) void k_ur_count(const float* __restr
             if (vd) atomicAdd(bin_d + lo + k, vd);
         }
     }
+}
+
+template <int D>
+__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                            const int64_t* __restrict__ users, int64_t n,
+                                                            const int64_t* __restrict__ pos_off,
+                                                            const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                            int slices, int slice_tiles, const float* __restrict__ ss,
+                                                            const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
+                                                            int32_t* __restrict__ bin_d) {
+    ur_count_body<D>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d);
+}
+
+template <int D>
+__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
+                                                              int64_t n_item, const int64_t* __restrict__ users, int64_t n,
+                                                              const int64_t* __restrict__ pos_off,
+                                                              const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                              int slices, int slice_tiles, const float* __restrict__ ss,
+                                                              const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
+                                                              int32_t* __restrict__ bin_d) {
+    ur_count_body<D>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d);
 }
 
 // inclusive prefix sum of v over the workgroup (kUrBlock threads); *total = the sum of all
@@ -619,16 +755,21 @@ __global__ __launch_bounds__(kUrBlock) void k_ur_metrics(const int32_t* __restri
 
 }  // namespace
 
-hipError_t sml_launch_full_rank(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* rows, int64_t n, int n_cols,
-                                const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, hipStream_t st) {
+bool sml_retrieval_supports(int d, int elem_bytes) {
+    return with_width(d, elem_bytes, nullptr, nullptr, [](auto, auto*, auto*) {});
+}
+
+hipError_t sml_launch_full_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* rows, int64_t n,
+                                int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, hipStream_t st) {
     hipError_t e = hipMemsetAsync(rank, 0, n * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
     const SliceGrid g = rank_grid(n, kRankWaves, n_item);
     const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kRankWaves);
-    with_width(d, [&](auto dd) {
-        k_full_rank<decltype(dd)::value><<<grid, block, 0, st>>>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, g.slices,
-                                                                g.slice_tiles, rank);
-    });
+    if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
+        LAUNCH_TYPED(k_full_rank, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, rows, n, n_cols, seen_off, seen_items,
+                     g.slices, g.slice_tiles, rank);
+    }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -637,8 +778,8 @@ int64_t sml_topk_scratch_size(int64_t n, int k, int64_t n_item) {
     return n * s * (int64_t)k * 8 + n * s * 4;
 }
 
-hipError_t sml_launch_topk(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* users, int64_t n, int k,
-                           const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores,
+hipError_t sml_launch_topk(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
+                           int k, const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores,
                            hipStream_t st) {
     const SliceGrid g = topk_grid(n, k, n_item);
     const int slices = g.slices, waves = topk_waves(k);
@@ -647,10 +788,11 @@ hipError_t sml_launch_topk(int d, const float* wu, const float* wi, int64_t n_it
     int32_t* cn = ci + n * slices * k;
     const dim3 grid((unsigned)(g.groups * slices)), block(64 * waves);
     const size_t lds = (size_t)waves * 2 * k * RT * 4;
-    with_width(d, [&](auto dd) {
-        k_topk_slice<decltype(dd)::value><<<grid, block, lds, st>>>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices,
-                                                                   g.slice_tiles, cs, ci, cn);
-    });
+    if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
+        LAUNCH_TYPED(k_topk_slice, decltype(dd)::value, tu, grid, block, lds, st, tu, ti, n_item, users, n, k, seen_off, seen_items,
+                     slices, g.slice_tiles, cs, ci, cn);
+    }))
+        return hipErrorInvalidValue;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int64_t threads = n * slices * k;
@@ -663,7 +805,7 @@ static int64_t ur_piece(int64_t n_pos) { return (n_pos * 4 + 255) / 256 * 256; }
 
 int64_t sml_user_rank_scratch_size(int64_t n_pos) { return 10 * ur_piece(n_pos); }
 
-hipError_t sml_launch_user_rank(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* users, int64_t n,
+hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
                                 const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                                 const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, hipStream_t st) {
     char* base = static_cast<char*>(scratch);
@@ -678,10 +820,11 @@ hipError_t sml_launch_user_rank(int d, const float* wu, const float* wi, int64_t
     hipError_t e = hipMemsetAsync(bin_p, 0, 2 * pc, st);
     if (e != hipSuccess) return e;
     const dim3 eg((unsigned)((n_pos + 255) / 256)), eb(256);
-    with_width(d, [&](auto dd) {
-        k_ur_thresholds<decltype(dd)::value><<<eg, eb, 0, st>>>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg,
-                                                               ks[0], ki[0], kx[0], in_seen);
-    });
+    if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
+        LAUNCH_TYPED(k_ur_thresholds, decltype(dd)::value, tu, eg, eb, 0, st, tu, ti, users, n, pos_off, pos_items, n_pos, seen_off,
+                     seen_items, seg, ks[0], ki[0], kx[0], in_seen);
+    }))
+        return hipErrorInvalidValue;
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // a user's range is at most n_pos long: ceil(log2 n_pos) merge passes sort every range
     int cur = 0;
@@ -691,10 +834,11 @@ hipError_t sml_launch_user_rank(int d, const float* wu, const float* wi, int64_t
     }
     const SliceGrid g = rank_grid(n, kUrWaves, n_item);
     const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kUrWaves);
-    with_width(d, [&](auto dd) {
-        k_ur_count<decltype(dd)::value><<<grid, block, 0, st>>>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, g.slices,
-                                                               g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
-    });
+    if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
+        LAUNCH_TYPED(k_ur_count, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, users, n, pos_off, seen_off, seen_items,
+                     g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
+    }))
+        return hipErrorInvalidValue;
     if ((e = hipGetLastError()) != hipSuccess) return e;
     k_ur_finish<<<dim3((unsigned)n), dim3(kUrBlock), 0, st>>>(pos_off, ks[cur], kx[cur], in_seen, bin_p, bin_d, above, pos);
     return hipGetLastError();

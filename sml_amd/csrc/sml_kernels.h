@@ -415,15 +415,17 @@ hipError_t sml_launch_sample_negatives(const int64_t* users, int64_t n, const in
 hipError_t sml_launch_device_epoch(const int64_t* ui, const void* mat, int elem_bytes, int64_t stride, int64_t col, int64_t n, uint64_t seed,
                                    int64_t* out3, hipStream_t st);
 hipError_t sml_launch_eval_metrics(const int32_t* rank, int64_t n, int topk, float* out, hipStream_t st);
-// retrieval.hip: full-catalogue rank and top-K (d = 32 / 64, n_item < 2^31)
-hipError_t sml_launch_full_rank(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* rows, int64_t n, int n_cols,
-                                const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, hipStream_t st);
+// retrieval.hip: full-catalogue rank and top-K (n_item < 2^31).  elem_bytes 4: fp32 tables, d = 32 / 64; elem_bytes 2: fp16
+// tables, d = 32 / 64 / 128 -- sml_retrieval_supports says which pairs exist; the launchers refuse the others
+bool sml_retrieval_supports(int d, int elem_bytes);
+hipError_t sml_launch_full_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* rows, int64_t n,
+                                int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, hipStream_t st);
 int64_t sml_topk_scratch_size(int64_t n, int k, int64_t n_item);
-hipError_t sml_launch_topk(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* users, int64_t n, int k,
-                           const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores,
+hipError_t sml_launch_topk(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
+                           int k, const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores,
                            hipStream_t st);
 int64_t sml_user_rank_scratch_size(int64_t n_pos);
-hipError_t sml_launch_user_rank(int d, const float* wu, const float* wi, int64_t n_item, const int64_t* users, int64_t n,
+hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
                                 const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                                 const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, hipStream_t st);
 hipError_t sml_launch_user_metrics(const int32_t* pos, const int64_t* pos_off, int64_t n, const int32_t* ks, int n_k,

@@ -711,31 +711,46 @@ class HipEngine(object):
             items = torch.zeros(1, device=self.device, dtype=torch.int32)
         return off, items
 
+    def _retrieval_tables(self, user_tab, item_tab):
+        """(user table, item table, entry-point suffix): both fp32 (the sml_* entry points) or both fp16 (sml_*_f16; the
+        rows are read as packed halves, no fp32 copy).  Which widths each element type has is the library's answer."""
+        if user_tab.dtype not in (torch.float32, torch.float16) or item_tab.dtype != user_tab.dtype:
+            raise ValueError("retrieval tables must both be fp32 or both fp16, got %s and %s" % (user_tab.dtype, item_tab.dtype))
+        for t in (user_tab, item_tab):
+            if t.device != self.device or t.dim() != 2 or not t.is_contiguous() or t.shape[-1] != self.d:
+                raise ValueError("expected a contiguous [rows,%d] tensor on %s, got %s on %s"
+                                 % (self.d, self.device, tuple(t.shape), t.device))
+        return user_tab, item_tab, "_f16" if user_tab.dtype == torch.float16 else ""
+
     def full_rank(self, user_tab, item_tab, rows, seen=None):
         """int32 [n]: per row (u, p, ...) the number of items i != p, not in Seen(u), scoring strictly above p over the
-        WHOLE item table (include/sml_hip.h, sml_full_rank).  seen = (seen_off int64 [n_user + 1], seen_items int32)."""
-        wu, wi = self._table(user_tab), self._table(item_tab)
+        WHOLE item table (include/sml_hip.h, sml_full_rank / sml_full_rank_f16: fp32 or fp16 tables).
+        seen = (seen_off int64 [n_user + 1], seen_items int32)."""
+        wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
+        call = getattr(self.lib, "sml_full_rank" + sfx)
         rows = self._dev(rows, torch.int64)
         n, c = rows.shape
         rank = torch.empty(n, device=self.device, dtype=torch.int32)
         if n == 0:
             return rank
         off, items = self._seen(seen)
-        check(self.lib.sml_full_rank(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(rows), n, c, _ptr(off), _ptr(items),
-                                     _ptr(rank), self._stream()), "sml_full_rank")
+        check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(rows), n, c, _ptr(off), _ptr(items), _ptr(rank), self._stream()),
+              "sml_full_rank" + sfx)
         return rank
 
     def topk_items(self, user_tab, item_tab, users, k, seen=None):
         """(int64 items [n, k], float32 scores [n, k]): each user's k best items not in Seen(u), score descending then id
-        ascending; missing slots are (-1, -inf) (include/sml_hip.h, sml_topk_items)."""
-        wu, wi = self._table(user_tab), self._table(item_tab)
+        ascending; missing slots are (-1, -inf) (include/sml_hip.h, sml_topk_items / sml_topk_items_f16: fp32 or fp16 tables)."""
+        wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
+        name = "sml_topk_items" + sfx
+        call = getattr(self.lib, name)
         users = self._dev(users, torch.int64).reshape(-1)
         n, k = users.shape[0], int(k)
         off, seen_items = self._seen(seen)
         total = int(self.lib.sml_topk_scratch_bytes(self._ctx, n, k, wi.shape[0]))
         if total < 0 or n == 0:          # argument checks (k, n_item) and the empty call go through the library
-            check(self.lib.sml_topk_items(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users), 0, k, _ptr(off),
-                                          _ptr(seen_items), None, None, None, self._stream()), "sml_topk_items")
+            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users), 0, k, _ptr(off), _ptr(seen_items), None, None, None,
+                       self._stream()), name)
         items = torch.empty(n, k, device=self.device, dtype=torch.int32)
         scores = torch.empty(n, k, device=self.device, dtype=torch.float32)
         chunk = n if total <= self.TOPK_SCRATCH_BYTES else max(1, int(n * self.TOPK_SCRATCH_BYTES // total))
@@ -745,19 +760,20 @@ class HipEngine(object):
             nbytes = int(self.lib.sml_topk_scratch_bytes(self._ctx, m, k, wi.shape[0]))
             if scratch is None or scratch.numel() < nbytes:
                 scratch = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
-            check(self.lib.sml_topk_items(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, k, _ptr(off),
-                                          _ptr(seen_items), _ptr(scratch), _ptr(items[c0:]), _ptr(scores[c0:]), self._stream()),
-                  "sml_topk_items")
+            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, k, _ptr(off), _ptr(seen_items), _ptr(scratch),
+                       _ptr(items[c0:]), _ptr(scores[c0:]), self._stream()), name)
         return items.long(), scores
 
     USER_RANK_SCRATCH_BYTES = 256 << 20  # held-out items of one sml_user_rank call are capped so its scratch fits this
 
     def user_ranks(self, user_tab, item_tab, users, pos_off, pos_items, seen=None, ks=(20,)):
         """Every user's held-out items ranked against the whole catalogue, and per-user metrics at each K in `ks`
-        (include/sml_hip.h, sml_user_rank / sml_user_metrics).  users int64 [n]; pos_off int64 [n + 1] and pos_items
+        (include/sml_hip.h, sml_user_rank / sml_user_rank_f16 / sml_user_metrics: fp32 or fp16 tables).  users int64 [n]; pos_off int64 [n + 1] and pos_items
         int32 [n_pos]: users[x]'s held-out items, ascending and unique in [pos_off[x], pos_off[x + 1]).  Returns a dict:
         above, pos int32 [n_pos]; hits int32, dcg, ap float32 [n, len(ks)]; first int32 [n]."""
-        wu, wi = self._table(user_tab), self._table(item_tab)
+        wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
+        name = "sml_user_rank" + sfx
+        call = getattr(self.lib, name)
         users = self._dev(users, torch.int64).reshape(-1)
         off_h = np.asarray(pos_off.cpu() if torch.is_tensor(pos_off) else pos_off, dtype=np.int64).reshape(-1)
         pos_items = self._dev(pos_items, torch.int32).reshape(-1)
@@ -775,8 +791,8 @@ class HipEngine(object):
                    ap=torch.empty(n, n_k, device=self.device, dtype=torch.float32),
                    first=torch.empty(n, device=self.device, dtype=torch.int32))
         if n == 0 or n_pos == 0:         # argument checks (d, n_item, Seen, ks) go through the library
-            check(self.lib.sml_user_rank(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], None, 0, None, None, 0, _ptr(off),
-                                         _ptr(seen_items), None, None, None, self._stream()), "sml_user_rank")
+            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], None, 0, None, None, 0, _ptr(off), _ptr(seen_items), None, None, None,
+                       self._stream()), name)
             check(self.lib.sml_user_metrics(self._ctx, None, None, 0, ks_p, n_k, None, None, None, None, self._stream()),
                   "sml_user_metrics")
             if n:
@@ -800,9 +816,9 @@ class HipEngine(object):
                 check(-1, "sml_user_rank_scratch_bytes")
             if scratch is None or scratch.numel() < nbytes:
                 scratch = torch.empty(max(nbytes, 1), device=self.device, dtype=torch.uint8)
-            check(self.lib.sml_user_rank(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, _ptr(sub_off),
-                                         _ptr(pos_items[e0:]), e1 - e0, _ptr(off), _ptr(seen_items), _ptr(scratch),
-                                         _ptr(out["above"][e0:]), _ptr(out["pos"][e0:]), self._stream()), "sml_user_rank")
+            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, _ptr(sub_off), _ptr(pos_items[e0:]), e1 - e0,
+                       _ptr(off), _ptr(seen_items), _ptr(scratch), _ptr(out["above"][e0:]), _ptr(out["pos"][e0:]), self._stream()),
+                  name)
             # a chunk of empty sets reads no pos; it still passes a valid pointer (an empty slice's may be null)
             pos_c = out["pos"][e0:] if e1 > e0 else out["pos"]
             check(self.lib.sml_user_metrics(self._ctx, _ptr(pos_c), _ptr(sub_off), m, ks_p, n_k,

@@ -14,7 +14,10 @@ CSRC = os.path.join(os.path.dirname(HERE), "sml_amd", "csrc")
 
 def demangle(names):
     try:
-        out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
+        # (_Float16 mangles as DF16_, which binutils' c++filt may not know yet; Dh, the older half type, demangles everywhere and
+        # only the kernel's name and template arguments are kept)
+        text = "\n".join(n.replace("DF16_", "Dh") for n in names)
+        out = subprocess.run(["c++filt"], input=text, capture_output=True, text=True).stdout.splitlines()
         return [re.sub(r"\(anonymous namespace\)::|^void ", "", o).split("(")[0] for o in out]
     except OSError:
         return names

@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""The fp32 retrieval entry points of the in-tree libsml_hip.so against ANOTHER build of the library (e.g. the previous
+commit's, built by hand into tools/_ab/), alternating in one process at the Yelp shape of tools/half_retrieval_probe.py:
+full_rank over 10,000 rows, topk_items K = 20 over all 60,000 users, user_ranks over the held-out sets, d = 32 and 64.
+Medians, minima and the interquartile spread of the alternated repetitions; outputs compared byte for byte.  The other
+build may be older than the header: only the symbols it exports are bound.
+usage: python tools/retrieval_ab.py <other.so> [--d 32,64] [--reps 20] [--out file.json]"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from half_retrieval_probe import I, K, KS, N_HELD, N_ROWS, U, alternate, same, stats    # noqa: E402
+from sml_amd import _lib, synth                                                         # noqa: E402
+from sml_amd.engine import HipEngine                                                    # noqa: E402
+from sml_amd.retrieval import SeenItems, held_out, nonempty_users                       # noqa: E402
+
+
+def load_other(path):
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
+    return lib
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("other")
+    ap.add_argument("--d", default="32,64")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    other = load_other(args.other)
+    seen = SeenItems(U, I)
+    for p in range(5):
+        train, _ = synth.sample_period(np.random.RandomState(2000 + p), 200000, U, I, neg=1)
+        seen.add(train)
+    _, test = synth.sample_period(np.random.RandomState(2010), N_ROWS, U, I, neg=1)
+    _, held = synth.sample_period(np.random.RandomState(2005), N_HELD, U, I, neg=1)
+    h_users, pos_off, pos_items = nonempty_users(held_out(held, U, I))
+    csr = seen.device(dev)
+    rows = torch.from_numpy(test[:, :2].copy()).to(dev)
+    users = torch.arange(U, device=dev)
+    result = {"tool": "retrieval_ab", "device": torch.cuda.get_device_name(dev), "other": os.path.basename(args.other), "U": U, "I": I,
+              "rows": N_ROWS, "k": K, "held_out_users": int(len(h_users)), "reps": args.reps, "dtype": "fp32", "by_d": {}}
+    for d in [int(x) for x in args.d.split(",")]:
+        g = torch.Generator().manual_seed(d)
+        wu = (torch.randn(U, d, generator=g) * 0.3).half().float().to(dev)       # the probe's tables, widened
+        wi = (torch.randn(I, d, generator=g) * 0.3).half().float().to(dev)
+        engs = {"tree": HipEngine(dev, d, 256), "other": HipEngine(dev, d, 256, lib=other)}
+        calls = {"full_rank": lambda e: e.full_rank(wu, wi, rows, csr),
+                 "topk_items": lambda e: e.topk_items(wu, wi, users, K, csr),
+                 "user_ranks": lambda e: e.user_ranks(wu, wi, h_users, pos_off, pos_items, csr, KS)}
+        res = {}
+        for name, fn in calls.items():
+            ta, tb, oa, ob = alternate(lambda: fn(engs["tree"]), lambda: fn(engs["other"]), args.reps, args.warmup, dev)
+            sa, sb = stats(ta), stats(tb)
+            res[name] = {"tree": sa, "other": sb, "tree_over_other": round(sa["ms"] / sb["ms"], 3), "same_bytes": same(oa, ob)}
+        result["by_d"][str(d)] = res
+        del engs
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
