@@ -26,6 +26,7 @@ int fail(int code, const char* what, const char* detail) {
     g_err = std::string(what) + ": " + (detail ? detail : "");
     return code;
 }
+template <typename T> T zeroed() { T x; memset(&x, 0, sizeof(x)); return x; }     // (memset: padding bytes too -- the structs travel as kernel arguments)
 #define HIPCHK(expr)                                                                  \
     do {                                                                              \
         hipError_t _e = (expr);                                                       \
@@ -142,6 +143,9 @@ struct Prof {
     }
     void release() { drain(); for (auto& e : ev) (void)hipEventDestroy(e); ev.clear(); }
 };
+// `body` (statements; every launch in it under its own HIPCHK) timed as ONE pair of profile class `cls` on stream `st` of `ctx`.
+// A failed launch returns from the function between the two: no end event is recorded on a failing stream (so no scope object).
+#define PROFILED(cls, ...) do { ctx->prof.begin(cls, st); __VA_ARGS__; ctx->prof.end(st); } while (0)
 
 }  // namespace
 
@@ -383,8 +387,8 @@ int bwd_split(int row_tiles) {
     return row_tiles <= 128 ? 1 : 0;
 }
 
-// slot layout of a batch: users at [0, B), items at [ioff, ioff + 2B), ioff = B rounded up to a
-// tile; both runs padded to whole tiles so the kernels store tile rows unconditionally
+// the transfer-net workspaces, sized for BatchSlots (below) of the largest batch: both runs padded to whole
+// tiles so the kernels store tile rows unconditionally
 int ensure_transfer_ws(sml_ctx* c, int B, bool tr_stage, hipStream_t st) {
     const size_t slots = (size_t)SML_R * (tiles_of(B) + tiles_of(2 * B)), d = (size_t)c->d;
     HIPCHK(c->out.ensure(slots * d * SML_FWD_NS));     // the training forward writes SML_FWD_NS partial planes
@@ -417,6 +421,118 @@ int ensure_pk(sml_ctx* c) {
 }
 float* pk_cur(const sml_ctx* c) { return c->pk.p + (size_t)c->pk_set * 2 * sml_pk_size(c->d); }
 float* pk_other(const sml_ctx* c) { return c->pk.p + (size_t)(1 - c->pk_set) * 2 * sml_pk_size(c->d); }
+
+// The slot layout of a batch of B triples, the same in EVERY transfer-net workspace: segment 0 (the user net) holds the
+// batch's B user rows at slots [0, B), segment 1 (the item net) its 2B item rows -- positives, then negatives -- at
+// [ioff, ioff + 2B), ioff = B rounded up to SML_R rows.  A workspace with k floats per row keeps slot s at p + s * k
+// (k = d: out, dout, dx, mrep, vrep; 3d: xin; SML_C2 * d: a1; SML_HID: z1, a2, dz1); segment s reads theta + s * net size
+// and the operand images pk + s * image size.  The launchers in transfer_net.hip pass segment 0's pointers as leading kernel
+// arguments and let the kernel REBUILD segment 1 from them by exactly this rule, so each of them (sml_launch_fwd,
+// sml_launch_mf_fwd_bx3, sml_launch_tr_bwd_head, sml_launch_tr_wgrad2; sml_launch_bwd for theta) refuses, with
+// hipErrorInvalidValue, the part it rebuilds when that was laid out otherwise.  This struct is the host's one statement of
+// the rule; a call site adds only what is its own.
+struct BatchSlots {
+    const sml_ctx* c; const float* theta;
+    int B, tiles0, tiles, ioff;      // workgroup tiles of segment 0 / of both; first item slot
+    BatchSlots(const sml_ctx* ctx, const float* theta_, int B_)
+        : c(ctx), theta(theta_), B(B_), tiles0(wg_tiles(B_, 1)), tiles(tiles0 + wg_tiles(2 * B_, 1)), ioff(SML_R * tiles_of(B_)) {}
+    int n_rows(int s) const { return s ? 2 * B : B; }
+    int64_t slot0(int s) const { return s ? ioff : 0; }
+    const float* net(int s) const { return theta + s * sml_net_size(c->d); }
+    const float* pk(int s) const { return pk_cur(c) + s * sml_pk_size(c->d); }
+    float* out(int s) const { return c->out.p + slot0(s) * c->d; }          float* dout(int s) const { return c->dout.p + slot0(s) * c->d; }
+    float* mrep(int s) const { return c->mrep.p + slot0(s) * c->d; }        float* vrep(int s) const { return c->vrep.p + slot0(s) * c->d; }
+    float* xin(int s) const { return c->xin.p + slot0(s) * 3 * c->d; }      float* a1(int s) const { return c->a1.p + slot0(s) * SML_C2 * c->d; }
+    float* z1(int s) const { return c->z1.p + slot0(s) * SML_HID; }         float* a2(int s) const { return c->a2.p + slot0(s) * SML_HID; }
+    float* dz1(int s) const { return c->dz1.p + slot0(s) * SML_HID; }       float* dx(int s, float* buf) const { return buf + slot0(s) * c->d; }   // (buf: the context's dx or an exchange's dx_local)
+    // what every forward / backward / weight-gradient segment of a training batch has in common
+    void fill(SmlSeg& g, int s, const int64_t* tri) const {
+        g.theta = net(s); g.pk = pk(s); g.tri = tri; g.B = B; g.is_item = s; g.n_rows = n_rows(s);
+        g.out = out(s); g.z1 = z1(s); g.xin = xin(s);
+    }
+    void fill(SmlBwdSeg& g, int s) const {
+        g.theta = net(s); g.pk = pk(s); g.dout = dout(s); g.is_item = s; g.z1 = z1(s); g.xin = xin(s); g.n_rows = n_rows(s);
+    }
+    void fill(SmlWgSeg& g, int s) const {
+        g.dz1 = dz1(s); g.a1 = a1(s); g.dout = dout(s); g.n_rows = n_rows(s); g.theta_net = net(s); g.pk_net = pk(s); g.xin = xin(s);
+    }
+    // ... and the two launch-argument blocks
+    void fill(SmlFwdArgs& f, int64_t out_pstride, int k2) const { f.tiles0 = tiles0; f.tiles_total = tiles; f.out_pstride = out_pstride; f.k2 = k2; }
+    void fill(SmlBwdArgs& w, int kind, int out_np, int64_t out_pstride) const {
+        w.tiles0 = tiles0; w.out_all = c->out.p; w.B = B; w.ioff = ioff; w.kind = kind; w.out_np = out_np; w.out_pstride = out_pstride;
+    }
+};
+
+// The batches of an epoch: a plan's [batch_off[b], batch_off[b + 1]) -- unequal, possibly empty, none longer than `batch`
+// (check_plan) -- or, without one, `batch` triples each and a ragged tail.
+struct BatchWalk {
+    const int64_t* triples; int64_t n; int batch; const sml_batch_plan* plan; int64_t nb;
+    BatchWalk(const int64_t* triples_, int64_t n_, int batch_, const sml_batch_plan* plan_ = nullptr)
+        : triples(triples_), n(n_), batch(batch_), plan(plan_), nb(plan_ ? plan_->n_batches : (n_ + batch_ - 1) / batch_) {}
+    int64_t off0(int64_t b) const { return plan ? plan->batch_off[b] : b * batch; }
+    int B(int64_t b) const { return plan ? (int)(plan->batch_off[b + 1] - off0(b)) : (int)((n - off0(b)) < batch ? (n - off0(b)) : batch); }
+    const int64_t* tri(int64_t b) const { return triples + off0(b) * 3; }
+    float scale(int64_t b, float dflt) const { return (plan && plan->loss_scale) ? plan->loss_scale[b] : dflt; }
+};
+int check_plan(const char* what, const sml_batch_plan* plan, int64_t n, int batch) {
+    if (plan->n_batches <= 0 || !plan->batch_off || plan->batch_off[0] != 0 || plan->batch_off[plan->n_batches] != n)
+        return fail(SML_EINVAL, what, "batch plan does not cover the triples");
+    for (int64_t b = 0; b < plan->n_batches; ++b)
+        if (plan->batch_off[b + 1] < plan->batch_off[b] || plan->batch_off[b + 1] - plan->batch_off[b] > batch)
+            return fail(SML_EINVAL, what, "a planned batch is longer than `batch`");
+    return SML_OK;
+}
+
+// argument rules the epoch drivers share (n = 0: the call has no epoch-length limit)
+int check_sizes(const sml_ctx* ctx, const char* what, int batch, int64_t n) {
+    if (batch > ctx->max_batch) return fail(SML_EINVAL, what, "batch exceeds ctx max_batch");
+    if (n > 0x3fffffff) return fail(SML_EINVAL, what, "epoch too long");
+    return SML_OK;
+}
+int check_loss_kind(const sml_ctx* ctx, const char* what, int kind) {
+    if (kind < 0 || kind > 3 || (ctx->variant == 1 ? (kind != SML_LOSS_BPR_UNIT && kind != SML_LOSS_BPR_NORM) : kind == SML_LOSS_BPR_UNIT))
+        return fail(SML_EINVAL, what, "loss_kind (variant 1 takes SML_LOSS_BPR_UNIT, or SML_LOSS_BPR_NORM for run_MF(norm=True); SML_LOSS_BPR_UNIT goes with variant 1 only)");
+    return SML_OK;
+}
+
+// run-list arguments.  Records mode: one record per sorted position, a batch's records at its place in the epoch ...
+SmlRunArgs run_args_records(const IndexSet& X, int64_t off0, int B) {
+    SmlRunArgs u = zeroed<SmlRunArgs>();
+    u.run_u = X.rec_u.p + off0; u.n_u = B; u.val_u = X.val_u2.p;
+    u.run_i = X.rec_i.p + 2 * off0; u.n_i = 2 * B; u.val_i = X.val_i2.p;
+    return u;
+}
+// ... compact mode: the duplicated-run lists of the whole epoch; the kernels slice out batch b themselves and stride over
+// it (how many runs a batch has is only known on the device)
+SmlRunArgs run_args_compact(const IndexSet& X, int64_t b) {
+    SmlRunArgs u = zeroed<SmlRunArgs>();
+    u.run_u = X.runs_u.p; u.run_i = X.runs_i.p; u.off_u = X.off_u.p; u.off_i = X.off_i.p; u.batch_index = (int)b;
+    u.val_u = X.val_u2.p; u.val_i = X.val_i2.p;
+    if (X.by_hand) { u.cnt_u = X.cnt_u.p; u.cnt_i = X.cnt_i.p; }
+    return u;
+}
+// ... and the Adam half of a row update at step `cur`: the rows continue from the replayed copies the gradient pass left
+// in xin / mrep / vrep (the user list's always; rep_i, rep_x_stride and rep_x_off are the caller's)
+void run_args_adam(SmlRunArgs& u, const sml_mf_tables* t, const sml_ctx* ctx, int cur, float lr) {
+    u.w_user = t->w_user; u.w_item = t->w_item;
+    u.m_user = t->m_user; u.v_user = t->v_user; u.m_item = t->m_item; u.v_item = t->v_item;
+    u.last_user = t->step_user; u.last_item = t->step_item; u.sched = ctx->sched.p; u.cur_step = cur; u.lr = lr; u.sched_len = replay_len(ctx, cur - 1);
+    u.rep_x = ctx->xin.p; u.rep_m = ctx->mrep.p; u.rep_v = ctx->vrep.p; u.rep_u = 1;
+}
+SmlThetaAdamArgs theta_adam_args(const sml_ctx* ctx, float* theta, float* m, float* v, float* grad, float weight_decay, const SmlSched& sc) {
+    SmlThetaAdamArgs ad = zeroed<SmlThetaAdamArgs>();
+    ad.theta = theta; ad.m = m; ad.v = v; ad.grad = grad; ad.pk = pk_cur(ctx);
+    ad.weight_decay = weight_decay; ad.step_size = sc.step_size; ad.bc2_sqrt = sc.bc2_sqrt;
+    return ad;
+}
+// the bare gradient pass of batch b into the context's dx rows, loss scale 1 (uniq, lr and another dx / scale: the caller's)
+SmlBareArgs bare_args_common(const sml_ctx* ctx, void* w_user, void* w_item, const BatchWalk& bw, int64_t b, int lstride, int kind,
+                             float lam_user, float lam_item) {
+    SmlBareArgs a = zeroed<SmlBareArgs>();
+    a.w_user = w_user; a.w_item = w_item; a.tri = bw.tri(b); a.B = bw.B(b); a.dx = ctx->dx.p;
+    a.loss_part = ctx->loss_part.p + b * lstride; a.kind = kind; a.lam_user = lam_user; a.lam_item = lam_item; a.scale = 1.0f;
+    return a;
+}
 
 int ceil_log2(int64_t x) { int b = 0; while (((int64_t)1 << b) < x) ++b; return b; }
 
@@ -488,8 +604,7 @@ int prep_epoch(IndexSet* c, const int64_t* tri, int64_t n, int batch, int pad_ti
     const int64_t n_items = (int64_t)nis * n;               // item occurrences of the epoch's lists (upper bound in modes 2 / 3)
     if (n_items > 0x7fffffff) return fail(SML_EINVAL, "index preparation", "too many item occurrences in one epoch");
     const bool has_users = mode != 3 && mode != 4, allruns_i = mode != 0;
-    SmlPrepArgs a;
-    memset(&a, 0, sizeof(a));
+    SmlPrepArgs a = zeroed<SmlPrepArgs>();
     a.tri = tri; a.n = n; a.batch = batch; a.nb = (int)nb; a.tpb = (batch + SML_PREP_TT - 1) / SML_PREP_TT;
     a.boff = plan ? plan->batch_off_dev : nullptr; a.pad_tiles = pad_tiles; a.records = dups ? 0 : 1;
     a.mode = mode; a.has_users = has_users ? 1 : 0; a.nis = nis;
@@ -741,7 +856,7 @@ int sml_theta_pack(sml_ctx* ctx, const float* theta, void* stream) {
     DevGuard g(ctx->device);
     int rc = ensure_pk(ctx); if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_PACK, st); HIPCHK(sml_launch_theta_pack(ctx->d, theta, pk_cur(ctx), st)); ctx->prof.end(st);
+    PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack(ctx->d, theta, pk_cur(ctx), st)));
     return SML_OK;
 }
 
@@ -757,23 +872,19 @@ int sml_transfer_forward(sml_ctx* ctx, const float* theta, int net, const float*
     const size_t bx3 = n_rows > 8192 && env_int("SML_FWD_BX3", 1) != 0 && env_int("SML_FWD_MT", 0) == 0 ? sml_bx3_bytes(ctx->d) : 0;
     if (bx3) {
         HIPCHK(ctx->pkx.ensure(bx3 / sizeof(float) + 4));
-        ctx->prof.begin(PC_PACK, st); HIPCHK(sml_launch_theta_pack_bx3(ctx->d, theta, ctx->pkx.p, st)); ctx->prof.end(st);
-        SmlFwdArgs a;
-        memset(&a, 0, sizeof(a));
+        PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack_bx3(ctx->d, theta, ctx->pkx.p, st)));
+        SmlFwdArgs a = zeroed<SmlFwdArgs>();
         SmlSeg& s = a.seg[0];
         s.theta = theta + (int64_t)net * sml_net_size(ctx->d);
         s.xt_tab = x_t; s.xh_tab = x_hat; s.n_rows = (int)n_rows; s.out = out;
         a.k2 = ctx->variant == 1; a.unit_rows = (ctx->variant == 1 && net == 0);
         a.tiles0 = wg_tiles((int)n_rows, 2);
         const char* pkx_net = reinterpret_cast<const char*>(ctx->pkx.p) + (size_t)net * (bx3 / 2);
-        ctx->prof.begin(ctx->side ? PC_FWD_SIDE : PC_FWD, st);
-        HIPCHK(sml_launch_fwd_bx3(ctx->d, a, pkx_net, a.tiles0, st, ctx->side));
-        ctx->prof.end(st);
+        PROFILED(ctx->side ? PC_FWD_SIDE : PC_FWD, HIPCHK(sml_launch_fwd_bx3(ctx->d, a, pkx_net, a.tiles0, st, ctx->side)));
         return SML_OK;
     }
-    ctx->prof.begin(PC_PACK, st); HIPCHK(sml_launch_theta_pack(ctx->d, theta, pk_cur(ctx), st)); ctx->prof.end(st);
-    SmlFwdArgs a;
-    memset(&a, 0, sizeof(a));
+    PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack(ctx->d, theta, pk_cur(ctx), st)));
+    SmlFwdArgs a = zeroed<SmlFwdArgs>();
     SmlSeg& s = a.seg[0];
     s.theta = theta + (int64_t)net * sml_net_size(ctx->d);
     s.pk = pk_cur(ctx) + (int64_t)net * sml_pk_size(ctx->d);
@@ -787,7 +898,7 @@ int sml_transfer_forward(sml_ctx* ctx, const float* theta, int net, const float*
     a.tiles0 = wg_tiles((int)n_rows, mt);
     a.seg[1] = s; a.seg[1].n_rows = 0;
     const bool side = ctx->side && mt == 2 && (ctx->d == 32 || ctx->d == 64);
-    ctx->prof.begin(side ? PC_FWD_SIDE : PC_FWD, st); HIPCHK(sml_launch_fwd(ctx->d, mt, 1, a, a.tiles0, st, side)); ctx->prof.end(st);
+    PROFILED(side ? PC_FWD_SIDE : PC_FWD, HIPCHK(sml_launch_fwd(ctx->d, mt, 1, a, a.tiles0, st, side)));
     return SML_OK;
 }
 
@@ -796,12 +907,11 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
                        const sml_mf_exchange* xchg, const sml_batch_plan* plan, void* stream) {
     if (!ctx || !theta || !t || !step || !batch_loss || batch <= 0 || (plan ? n < 0 : n <= 0) || (n > 0 && !triples))
         return fail(SML_EINVAL, "sml_mf_stage_epoch", "bad argument");
-    if (plan && (plan->n_batches <= 0 || !plan->batch_off || !plan->batch_off_dev || plan->batch_off[0] != 0 || plan->batch_off[plan->n_batches] != n))
-        return fail(SML_EINVAL, "sml_mf_stage_epoch", "batch plan does not cover the triples");
-    if (batch > ctx->max_batch) return fail(SML_EINVAL, "sml_mf_stage_epoch", "batch exceeds ctx max_batch");
-    if (n > 0x3fffffff) return fail(SML_EINVAL, "sml_mf_stage_epoch", "epoch too long");
-    if (loss_kind < 0 || loss_kind > 3 || (ctx->variant == 1 ? (loss_kind != SML_LOSS_BPR_UNIT && loss_kind != SML_LOSS_BPR_NORM) : loss_kind == SML_LOSS_BPR_UNIT))
-        return fail(SML_EINVAL, "sml_mf_stage_epoch", "loss_kind (variant 1 takes SML_LOSS_BPR_UNIT, or SML_LOSS_BPR_NORM for run_MF(norm=True); SML_LOSS_BPR_UNIT goes with variant 1 only)");
+    int rc;
+    if (plan && !plan->batch_off_dev) return fail(SML_EINVAL, "sml_mf_stage_epoch", "batch plan does not cover the triples");     // (the index preparation reads the offsets on the device)
+    if (plan && (rc = check_plan("sml_mf_stage_epoch", plan, n, batch))) return rc;
+    if ((rc = check_sizes(ctx, "sml_mf_stage_epoch", batch, n))) return rc;
+    if ((rc = check_loss_kind(ctx, "sml_mf_stage_epoch", loss_kind))) return rc;
     if (xchg && (xchg->world < 1 || !xchg->key_items || !xchg->val_items || !xchg->dx_local || !xchg->dx_items_all))
         return fail(SML_EINVAL, "sml_mf_stage_epoch", "incomplete exchange descriptor");
     const bool mf_peers = xchg && !xchg->hook && ctx->peer.world > 0;
@@ -815,11 +925,8 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const int d = ctx->d;
-    const int64_t nb = plan ? plan->n_batches : (n + batch - 1) / batch;
-    if (plan) for (int64_t b = 0; b < nb; ++b)
-        if (plan->batch_off[b + 1] < plan->batch_off[b] || plan->batch_off[b + 1] - plan->batch_off[b] > batch)
-            return fail(SML_EINVAL, "sml_mf_stage_epoch", "a planned batch is longer than `batch`");
-    int rc;
+    const BatchWalk bw(triples, n, batch, plan);
+    const int64_t nb = bw.nb;
     if ((rc = ensure_pk(ctx))) return rc;
     if ((rc = ensure_transfer_ws(ctx, batch, false, st))) return rc;
     if ((rc = ensure_sched(ctx, lr, *step + nb + 1, st))) return rc;
@@ -827,29 +934,29 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
     const int64_t out_pstride = (int64_t)SML_R * (tiles_of(batch) + tiles_of(2 * batch)) * d;
     const int fns = fwd_split(wg_tiles(batch, 1) + wg_tiles(2 * batch, 1)), bsplit = bwd_split(wg_tiles(batch, 1) + wg_tiles(2 * batch, 1));
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
-    ctx->prof.begin(PC_PACK, st); HIPCHK(sml_launch_theta_pack(d, theta, pk_cur(ctx), st)); ctx->prof.end(st);
+    PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack(d, theta, pk_cur(ctx), st)));
     // d = 32, one workgroup per row tile: the forward's fc1 / fc2 on bf16x3 products (k_mf_fwd_bx3; SML_MF_BX3=0: fp32 products);
     // theta is fixed during the MF stage: its bf16 planes are packed once per epoch
     const bool mf_bx3 = fns == 1 && sml_bx3_bytes(d) > 0 && env_int("SML_MF_BX3", 1) != 0;
     if (mf_bx3) {
         HIPCHK(ctx->pkx.ensure(sml_bx3_bytes(d) / sizeof(float) + 4));
-        ctx->prof.begin(PC_PACK, st); HIPCHK(sml_launch_theta_pack_bx3(d, theta, ctx->pkx.p, st)); ctx->prof.end(st);
+        PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack_bx3(d, theta, ctx->pkx.p, st)));
     }
     // One GPU, the one-workgroup-per-tile backward, a row inside one wavefront (d <= 64): the backward takes the row update itself
     // (SmlFusedUpdate; SML_MF_FUSED_UPDATE=0: the k_run_update launch, A/B tests) -- and, round 5, the net runs once per DISTINCT
     // row of the batch (SmlDense; SML_MF_DISTINCT=0: one pass per occurrence, A/B tests) when the lists allow it
     const bool can_fuse = !xchg && !bsplit && d <= 64 && ctx->adaptive_beta <= 0.0f && env_int("SML_MF_FUSED_UPDATE", 1) != 0;
     const bool want_dense = can_fuse && fns == 1 && env_int("SML_MF_DISTINCT", 1) != 0;
-    ctx->prof.begin(PC_SORT, st); rc = sort_epoch(&ctx->ix[0], triples, n, batch, 1, t->n_user, t->n_item, false, st, plan, nullptr, want_dense);
     const int64_t x_total = !xchg ? 0 : xchg->item_off ? xchg->item_off[nb] : (int64_t)xchg->world * 2 * n;
     const int64_t x_stride = !xchg ? 0 : xchg->slot_stride > 0 ? xchg->slot_stride : (int64_t)2 * batch;
     const bool x_by_hand = xchg && xchg->lists_unsorted != 0;
+    PROFILED(PC_SORT, {
+    rc = sort_epoch(&ctx->ix[0], triples, n, batch, 1, t->n_user, t->n_item, false, st, plan, nullptr, want_dense);
     if (!rc && xchg && x_total > 0 && x_by_hand) {
         // the job's item occurrences arrive batch-major and UNSORTED: every batch's run list by index_prep.hip (occurrence source 4:
         // one stream of explicit (key, value) pairs; records mode) -- no library sort anywhere on this path since round 5
         int64_t x_seg = (int64_t)xchg->world * 2 * batch;
-        sml_batch_plan px;
-        memset(&px, 0, sizeof(px));
+        sml_batch_plan px = zeroed<sml_batch_plan>();
         if (xchg->item_off) {
             std::vector<int32_t> off32((size_t)nb + 1);
             x_seg = 1;
@@ -868,9 +975,9 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
         HIPCHK(ctx->rec_x.ensure((size_t)x_total));
         HIPCHK(sml_launch_mark_runs(8, xchg->key_items, xchg->val_items, x_total, 32, ctx->rec_x.p, nullptr, nullptr, 0, 0, st));
     }
-    ctx->prof.end(st); if (rc) return rc;
+    });
+    if (rc) return rc;
     HIPCHK(hipMemsetAsync(ctx->loss_part.p, 0, (size_t)nb * lstride * sizeof(float), st));
-    const int64_t ns = sml_net_size(d), ps = sml_pk_size(d);
     float* dx_buf = xchg ? xchg->dx_local : ctx->dx.p;
     const bool dense = want_dense && ctx->ix[0].by_hand && ctx->ix[0].dense;
     const bool fused = can_fuse && !dense && ctx->ix[0].by_hand && ctx->ix[0].slot_stride > 0;
@@ -884,52 +991,33 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
         HIPCHK(hipMemsetAsync(ctx->run_arrive.p, 0, ((size_t)3 * ctx->max_batch + 8) * sizeof(int), st));
     }
     for (int64_t b = 0; b < nb; ++b) {
-        const int64_t off0 = plan ? plan->batch_off[b] : b * batch;
-        const int B = plan ? (int)(plan->batch_off[b + 1] - off0) : (int)((n - off0) < batch ? (n - off0) : batch);
-        const int64_t* tri = triples + off0 * 3;
+        const int64_t off0 = bw.off0(b); const int B = bw.B(b); const int64_t* tri = bw.tri(b);
         const int cur = (int)(*step + 1 + b);
-        SmlFwdArgs f;
-        memset(&f, 0, sizeof(f));
+        const BatchSlots L(ctx, theta, B);
+        const int tiles = L.tiles;
+        SmlFwdArgs f = zeroed<SmlFwdArgs>();
+        SmlBwdArgs w = zeroed<SmlBwdArgs>();
         for (int s = 0; s < 2; ++s) {
             SmlSeg& sg = f.seg[s];
-            sg.theta = theta + s * ns; sg.pk = pk_cur(ctx) + s * ps;
+            L.fill(sg, s, tri);
             sg.xt_tab = s ? t->last_item : t->last_user;
             sg.xh_tab = s ? t->w_item : t->w_user;
             sg.m_tab = s ? t->m_item : t->m_user; sg.v_tab = s ? t->v_item : t->v_user;
             sg.last_tab = s ? t->step_item : t->step_user;
-            sg.tri = tri; sg.B = B; sg.is_item = s; sg.n_rows = s ? 2 * B : B;
-            const int64_t slot0 = s ? (int64_t)SML_R * tiles_of(B) : 0;
-            sg.out = ctx->out.p + slot0 * d; sg.z1 = ctx->z1.p + slot0 * SML_HID; sg.xin = ctx->xin.p + slot0 * 3 * d;
-            sg.a1 = nullptr;
-            sg.mrep = ctx->mrep.p + slot0 * d; sg.vrep = ctx->vrep.p + slot0 * d;
+            sg.mrep = L.mrep(s); sg.vrep = L.vrep(s);
             if (dense) {        // scratch row k = distinct row k of this list (every tile's rows named by its header)
                 sg.n_rows = SML_TM * wg_tiles(sg.n_rows, 1);          // (whole tiles: a live row may sit past the batch's ragged end)
-                sg.drec = ctx->ix[0].dense_rec.p + b * ctx->ix[0].dense_stride + slot0;
-                sg.hdr = ctx->ix[0].tile_hdr.p + b * ctx->ix[0].tiles_cap + (s ? wg_tiles(B, 1) : 0);
+                sg.drec = ctx->ix[0].dense_rec.p + b * ctx->ix[0].dense_stride + L.slot0(s);
+                sg.hdr = ctx->ix[0].tile_hdr.p + b * ctx->ix[0].tiles_cap + (s ? L.tiles0 : 0);
             }
+            L.fill(w.seg[s], s);
+            w.seg[s].dx = L.dx(s, dx_buf);
         }
-        f.tiles0 = wg_tiles(B, 1); f.cur_step = cur; f.sched = ctx->sched.p; f.out_pstride = out_pstride; f.k2 = ctx->variant == 1;
-        f.sched_len = replay_len(ctx, cur - 1);
-        const int tiles = f.tiles0 + wg_tiles(2 * B, 1);
-        f.tiles_total = tiles;
-        ctx->prof.begin(PC_FWD, st);
-        if (mf_bx3) HIPCHK(sml_launch_mf_fwd_bx3(d, f, ctx->pkx.p, tiles, st));
-        else HIPCHK(sml_launch_fwd(d, 1, fns, f, tiles, st));
-        ctx->prof.end(st);
-        SmlBwdArgs w;
-        memset(&w, 0, sizeof(w));
-        for (int s = 0; s < 2; ++s) {
-            SmlBwdSeg& sg = w.seg[s];
-            const int64_t slot0 = s ? (int64_t)SML_R * tiles_of(B) : 0;
-            sg.theta = theta + s * ns; sg.pk = pk_cur(ctx) + s * ps;
-            sg.dout = ctx->dout.p + slot0 * d; sg.is_item = s; sg.z1 = ctx->z1.p + slot0 * SML_HID; sg.xin = ctx->xin.p + slot0 * 3 * d;
-            sg.dx = dx_buf + slot0 * d; sg.dz1 = nullptr; sg.n_rows = s ? 2 * B : B;
-        }
-        w.tiles0 = f.tiles0; w.l2 = l2; w.convg_part = nullptr;
-        w.out_all = ctx->out.p; w.B = B; w.ioff = SML_R * tiles_of(B); w.kind = loss_kind;
-        w.scale = (plan && plan->loss_scale) ? plan->loss_scale[b] : xchg ? xchg->loss_scale : 1.0f;
-        w.loss_part = ctx->loss_part.p + b * lstride;
-        w.out_np = fns; w.out_pstride = out_pstride;
+        L.fill(f, out_pstride, ctx->variant == 1);
+        f.cur_step = cur; f.sched = ctx->sched.p; f.sched_len = replay_len(ctx, cur - 1);
+        PROFILED(PC_FWD, if (mf_bx3) HIPCHK(sml_launch_mf_fwd_bx3(d, f, ctx->pkx.p, tiles, st)); else HIPCHK(sml_launch_fwd(d, 1, fns, f, tiles, st)));
+        L.fill(w, loss_kind, fns, out_pstride);
+        w.l2 = l2; w.scale = bw.scale(b, xchg ? xchg->loss_scale : 1.0f); w.loss_part = ctx->loss_part.p + b * lstride;
         if (dense) {
             w.dn.hdr = ctx->ix[0].tile_hdr.p + b * ctx->ix[0].tiles_cap;
             w.dn.ent = ctx->ix[0].tile_ent.p + b * ctx->ix[0].tiles_cap * SML_TILE_ENT;
@@ -961,18 +1049,13 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
             peer_step(ctx, 1, bwd_grid, &push_f, &poll_f);
             w.push = push_f; w.tiles_live = tiles;
         }
-        ctx->prof.begin(PC_BWD, st); HIPCHK(sml_launch_bwd(d, bsplit, w, bwd_grid, st)); ctx->prof.end(st);
+        PROFILED(PC_BWD, HIPCHK(sml_launch_bwd(d, bsplit, w, bwd_grid, st)));
         if (fused || dense) continue;         // (the backward stepped the rows)
         if (ctx->adaptive_beta > 0.0f) {      // --need_adaptive: the users' norm term joins their gradient rows and the batch's loss
-            ctx->prof.begin(PC_MISC, st);
-            HIPCHK(sml_launch_adaptive_users(d, ctx->xin.p, dx_buf, B, ctx->adaptive_beta, w.loss_part, st));
-            ctx->prof.end(st);
+            PROFILED(PC_MISC, HIPCHK(sml_launch_adaptive_users(d, ctx->xin.p, dx_buf, B, ctx->adaptive_beta, w.loss_part, st)));
         }
-        SmlRunArgs u;
-        memset(&u, 0, sizeof(u));
-        u.run_u = ctx->ix[0].rec_u.p + off0; u.n_u = B; u.val_u = ctx->ix[0].val_u2.p;
-        u.run_i = ctx->ix[0].rec_i.p + 2 * off0; u.n_i = 2 * B; u.val_i = ctx->ix[0].val_i2.p;
-        u.dx = dx_buf; u.dx_i = dx_buf; u.w_user = t->w_user; u.w_item = t->w_item;
+        SmlRunArgs u = run_args_records(ctx->ix[0], off0, B);
+        u.dx = dx_buf; u.dx_i = dx_buf;
         if (xchg) {
             // every rank contributes x_stride rows per batch (its 2*B item-gradient rows first: B may differ from rank
             // to rank and be zero); an empty local batch still joins the collective
@@ -982,22 +1065,20 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
             } else if (mf_peers) {
                 // one-shot: this rank's x_stride rows go straight into slot [parity][rank] of every rank's inbox; the row
                 // update starts once every rank's rows have landed here (the slots of one parity are the gathered buffer)
-                const int64_t ioff = (int64_t)SML_R * tiles_of(B);
                 SmlPeerPush push; SmlPeerPoll poll;
                 const int64_t x_push = xchg->push_rows > 0 ? xchg->push_rows : x_stride;     // (the same on every rank)
-                ctx->prof.begin(PC_MISC, st);
-                if (push_fused) poll = poll_f;                                               // (the backward pushed and signalled)
-                else {
-                    peer_step(ctx, 1, sml_peer_push_blocks(x_push * d), &push, &poll);
-                    HIPCHK(sml_launch_peer_push(dx_buf + ioff * d, x_push * d, push, st));
-                }
-                if (env_int("SML_PEER_WAIT_LAUNCH", 0)) HIPCHK(sml_launch_peer_wait(poll, st));      // (A/B: the wait as its own launch)
-                else u.wait = poll;                                                               // ... or at the head of the row update
-                ctx->prof.end(st);
+                PROFILED(PC_MISC, {
+                    if (push_fused) poll = poll_f;                                           // (the backward pushed and signalled)
+                    else {
+                        peer_step(ctx, 1, sml_peer_push_blocks(x_push * d), &push, &poll);
+                        HIPCHK(sml_launch_peer_push(L.dx(1, dx_buf), x_push * d, push, st));
+                    }
+                    if (env_int("SML_PEER_WAIT_LAUNCH", 0)) HIPCHK(sml_launch_peer_wait(poll, st));      // (A/B: the wait as its own launch)
+                    else u.wait = poll;                                                               // ... or at the head of the row update
+                });
                 gathered = poll.slot0;
             } else {
-                const int64_t ioff = (int64_t)SML_R * tiles_of(B);
-                NCCLCHK(g_rccl.AllGather(dx_buf + ioff * d, xchg->dx_items_all, (size_t)x_stride * d, ncclFloat, ctx->comm, st));
+                NCCLCHK(g_rccl.AllGather(L.dx(1, dx_buf), xchg->dx_items_all, (size_t)x_stride * d, ncclFloat, ctx->comm, st));
             }
             const int64_t x0 = xchg->item_off ? xchg->item_off[b] : (int64_t)xchg->world * 2 * b * batch;
             u.run_i = (x_by_hand ? ctx->ix[1].rec_i.p : ctx->rec_x.p) + x0;
@@ -1005,15 +1086,13 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
             u.n_i = xchg->item_off ? (int)(xchg->item_off[b + 1] - x0) : xchg->world * 2 * B;
             u.dx_i = gathered;
         }
-        u.m_user = t->m_user; u.v_user = t->v_user; u.m_item = t->m_item; u.v_item = t->v_item;
-        u.last_user = t->step_user; u.last_item = t->step_item; u.sched = ctx->sched.p; u.cur_step = cur; u.lr = lr; u.sched_len = replay_len(ctx, cur - 1);
+        run_args_adam(u, t, ctx, cur, lr);
         // rows continue from the forward's replayed copies (local scratch; the multi-GPU item list's slots index the
         // all-gathered buffer instead, so item rows are replayed from the table there)
-        u.rep_x = ctx->xin.p; u.rep_m = ctx->mrep.p; u.rep_v = ctx->vrep.p; u.rep_u = 1; u.rep_i = xchg ? 0 : 1;
-        u.rep_x_stride = 3 * d; u.rep_x_off = d;
-        ctx->prof.begin(PC_SEG_ADAM, st); HIPCHK(sml_launch_run_adam(d, u, (int64_t)u.n_u + u.n_i, st)); ctx->prof.end(st);
+        u.rep_i = xchg ? 0 : 1; u.rep_x_stride = 3 * d; u.rep_x_off = d;
+        PROFILED(PC_SEG_ADAM, HIPCHK(sml_launch_run_adam(d, u, (int64_t)u.n_u + u.n_i, st)));
     }
-    ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)); ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)));
     *step += nb;
     return SML_OK;
 }
@@ -1025,8 +1104,8 @@ int sml_mf_adam_flush(sml_ctx* ctx, const sml_mf_tables* t, float lr, int64_t st
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = ensure_sched(ctx, lr, step + 1, st))) return rc;
-    ctx->prof.begin(PC_FLUSH, st); HIPCHK(sml_launch_adam_flush(ctx->d, t->w_user, t->m_user, t->v_user, t->step_user, t->n_user, ctx->sched.p, (int)step, replay_len(ctx, step), st));
-    HIPCHK(sml_launch_adam_flush(ctx->d, t->w_item, t->m_item, t->v_item, t->step_item, t->n_item, ctx->sched.p, (int)step, replay_len(ctx, step), st)); ctx->prof.end(st);
+    PROFILED(PC_FLUSH, HIPCHK(sml_launch_adam_flush(ctx->d, t->w_user, t->m_user, t->v_user, t->step_user, t->n_user, ctx->sched.p, (int)step, replay_len(ctx, step), st));
+             HIPCHK(sml_launch_adam_flush(ctx->d, t->w_item, t->m_item, t->v_item, t->step_item, t->n_item, ctx->sched.p, (int)step, replay_len(ctx, step), st)));
     return SML_OK;
 }
 
@@ -1036,19 +1115,15 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
                        sml_grad_hook grad_hook, void* hook_user, const sml_batch_plan* plan, void* stream) {
     if (!ctx || !theta || !adam_m || !adam_v || !t || !step || !batch_loss || batch <= 0 || (plan ? n < 0 : n <= 0) || (n > 0 && !triples))
         return fail(SML_EINVAL, "sml_tr_stage_epoch", "bad argument");
-    if (plan && (plan->n_batches <= 0 || !plan->batch_off || plan->batch_off[0] != 0 || plan->batch_off[plan->n_batches] != n))
-        return fail(SML_EINVAL, "sml_tr_stage_epoch", "batch plan does not cover the triples");
-    if (batch > ctx->max_batch) return fail(SML_EINVAL, "sml_tr_stage_epoch", "batch exceeds ctx max_batch");
-    if (loss_kind < 0 || loss_kind > 3 || (ctx->variant == 1 ? (loss_kind != SML_LOSS_BPR_UNIT && loss_kind != SML_LOSS_BPR_NORM) : loss_kind == SML_LOSS_BPR_UNIT))
-        return fail(SML_EINVAL, "sml_tr_stage_epoch", "loss_kind (variant 1 takes SML_LOSS_BPR_UNIT, or SML_LOSS_BPR_NORM for run_MF(norm=True); SML_LOSS_BPR_UNIT goes with variant 1 only)");
+    int rc;
+    if (plan && (rc = check_plan("sml_tr_stage_epoch", plan, n, batch))) return rc;
+    if ((rc = check_sizes(ctx, "sml_tr_stage_epoch", batch, 0))) return rc;
+    if ((rc = check_loss_kind(ctx, "sml_tr_stage_epoch", loss_kind))) return rc;
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const int d = ctx->d;
-    const int64_t nb = plan ? plan->n_batches : (n + batch - 1) / batch;
-    if (plan) for (int64_t b = 0; b < nb; ++b)
-        if (plan->batch_off[b + 1] < plan->batch_off[b] || plan->batch_off[b + 1] - plan->batch_off[b] > batch)
-            return fail(SML_EINVAL, "sml_tr_stage_epoch", "a planned batch is longer than `batch`");
-    int rc;
+    const BatchWalk bw(triples, n, batch, plan);
+    const int64_t nb = bw.nb;
     if ((rc = ensure_pk(ctx))) return rc;
     if ((rc = ensure_transfer_ws(ctx, batch, true, st))) return rc;
     // --clip_grad (model/transfer.py:725-727): the flat gradient is completed, its norm taken, and the Adam launch scales it
@@ -1063,10 +1138,10 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
     const int lstride = (wg_tiles(batch, 1) + wg_tiles(2 * batch, 1)) * (d / 16 > 4 ? d / 16 : 4);
     const int64_t out_pstride = (int64_t)SML_R * (tiles_of(batch) + tiles_of(2 * batch)) * d;
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
-    ctx->prof.begin(PC_PACK, st); HIPCHK(sml_launch_theta_pack(d, theta, pk_cur(ctx), st)); ctx->prof.end(st);
+    PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack(d, theta, pk_cur(ctx), st)));
     HIPCHK(hipMemsetAsync(ctx->loss_part.p, 0, (size_t)nb * lstride * sizeof(float), st));
     HIPCHK(hipMemsetAsync(grad, 0, (size_t)2 * sml_net_size(d) * sizeof(float), st));
-    const int64_t ns = sml_net_size(d), ps = sml_pk_size(d);
+    const int64_t ns = sml_net_size(d);
     // Deferred conv step (one GPU, fused Adam, restructured step, hidden-split forward): the merged launch of every batch
     // but the epoch's last leaves the conv-gradient partials to the NEXT batch's forward, which adds them and steps the 190
     // conv parameters in its prologue (SmlFwdArgs).  SML_TR_DEFER=0: the merged launch's last tail workgroup does it.
@@ -1082,11 +1157,9 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
         HIPCHK(sml_launch_conv_state_init(d, theta, adam_m, adam_v, ctx->cstate.p, st));
     }
     for (int64_t b = 0; b < nb; ++b) {
-        const int64_t off0 = plan ? plan->batch_off[b] : b * batch;
-        const int B = plan ? (int)(plan->batch_off[b + 1] - off0) : (int)((n - off0) < batch ? (n - off0) : batch);
-        const int64_t* tri = triples + off0 * 3;
-        SmlFwdArgs f;
-        memset(&f, 0, sizeof(f));
+        const BatchSlots L(ctx, theta, bw.B(b));
+        const int tiles = L.tiles;
+        SmlFwdArgs f = zeroed<SmlFwdArgs>();
         if (defer) {
             const SmlSched scp = sched_entry((double)lr, *step + b);      // the PREVIOUS batch's step (b >= 1)
             f.cg_part = b > 0 ? ctx->convg.p : nullptr; f.cg_split = prev_split; f.cg_total = prev_total;
@@ -1094,109 +1167,89 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
             f.cs_theta = theta; f.cs_m = adam_m; f.cs_v = adam_v;
             f.cs_wd = weight_decay; f.cs_step_size = scp.step_size; f.cs_bc2_sqrt = scp.bc2_sqrt;
         }
+        SmlBwdArgs w = zeroed<SmlBwdArgs>();
+        SmlWgArgs wg = zeroed<SmlWgArgs>();
         for (int s = 0; s < 2; ++s) {
             SmlSeg& sg = f.seg[s];
-            sg.theta = theta + s * ns; sg.pk = pk_cur(ctx) + s * ps;
+            L.fill(sg, s, bw.tri(b));
             sg.xt_tab = s ? t->last_item : t->last_user;
             sg.xh_tab = s ? t->hat_item : t->hat_user;
-            sg.tri = tri; sg.B = B; sg.is_item = s; sg.n_rows = s ? 2 * B : B;
-            const int64_t slot0 = s ? (int64_t)SML_R * tiles_of(B) : 0;
-            sg.out = ctx->out.p + slot0 * d; sg.z1 = ctx->z1.p + slot0 * SML_HID; sg.xin = ctx->xin.p + slot0 * 3 * d;
-            sg.a1 = ctx->a1.p + slot0 * SML_C2 * d; sg.a2 = a2_recompute ? nullptr : ctx->a2.p + slot0 * SML_HID;
-        }
-        f.tiles0 = wg_tiles(B, 1); f.cur_step = 0; f.sched = nullptr; f.out_pstride = out_pstride; f.k2 = ctx->variant == 1;
-        const int tiles = f.tiles0 + wg_tiles(2 * B, 1);
-        f.tiles_total = tiles;
-        ctx->prof.begin(PC_FWD, st); HIPCHK(sml_launch_fwd(d, 1, fns, f, tiles, st)); ctx->prof.end(st);
-        SmlBwdArgs w;
-        memset(&w, 0, sizeof(w));
-        SmlWgArgs wg;
-        memset(&wg, 0, sizeof(wg));
-        for (int s = 0; s < 2; ++s) {
-            SmlBwdSeg& sg = w.seg[s];
-            const int64_t slot0 = s ? (int64_t)SML_R * tiles_of(B) : 0;
-            sg.theta = theta + s * ns; sg.pk = pk_cur(ctx) + s * ps;
-            sg.dout = ctx->dout.p + slot0 * d; sg.is_item = s; sg.z1 = ctx->z1.p + slot0 * SML_HID; sg.xin = ctx->xin.p + slot0 * 3 * d;
-            sg.dx = nullptr; sg.dz1 = ctx->dz1.p + slot0 * SML_HID; sg.n_rows = s ? 2 * B : B;
+            sg.a1 = L.a1(s); sg.a2 = a2_recompute ? nullptr : L.a2(s);
+            L.fill(w.seg[s], s);
+            w.seg[s].dz1 = L.dz1(s);
             SmlWgSeg& q = wg.seg[s];
-            q.dz1 = sg.dz1; q.a1 = ctx->a1.p + slot0 * SML_C2 * d; q.dout = sg.dout; q.a2 = a2_recompute ? sg.z1 : ctx->a2.p + slot0 * SML_HID;
+            L.fill(q, s);
+            q.a2 = a2_recompute ? L.z1(s) : L.a2(s);
             // (one GPU, Adam fused into the weight-gradient kernel, no gradient buffer asked for: the flat gradient is
             // not written at all -- 0.8 MB less for the launch to leave dirty in L2)
             const bool fused_only = !clip && !grad_hook && (ctx->comm == nullptr || ctx->peer.world > 0) && theta_grad == nullptr;
-            q.grad = fused_only ? nullptr : grad + s * ns; q.n_rows = sg.n_rows;
-            q.theta_net = sg.theta; q.pk_net = sg.pk; q.xin = sg.xin;
+            q.grad = fused_only ? nullptr : grad + s * ns;
         }
-        w.tiles0 = f.tiles0; w.l2 = 0.0f; w.convg_part = ctx->convg.p;
-        w.out_all = ctx->out.p; w.B = B; w.ioff = SML_R * tiles_of(B); w.kind = loss_kind;
-        w.scale = (plan && plan->loss_scale) ? plan->loss_scale[b] : loss_scale; w.loss_part = ctx->loss_part.p + b * lstride;
-        w.out_np = fns; w.out_pstride = out_pstride; w.tiles_total = tiles;
-        ctx->prof.begin(PC_BWD, st);
-        if (v2) HIPCHK(sml_launch_tr_bwd_head(d, w, tiles, st)); else HIPCHK(sml_launch_bwd(d, bsplit, w, tiles, st));
-        ctx->prof.end(st);
+        L.fill(f, out_pstride, ctx->variant == 1);
+        PROFILED(PC_FWD, HIPCHK(sml_launch_fwd(d, 1, fns, f, tiles, st)));
+        L.fill(w, loss_kind, fns, out_pstride);
+        w.convg_part = ctx->convg.p; w.tiles_total = tiles;
+        w.scale = bw.scale(b, loss_scale); w.loss_part = ctx->loss_part.p + b * lstride;
+        PROFILED(PC_BWD, if (v2) HIPCHK(sml_launch_tr_bwd_head(d, w, tiles, st)); else HIPCHK(sml_launch_bwd(d, bsplit, w, tiles, st)));
         const SmlSched sc = sched_entry((double)lr, *step + 1 + b);
         // (v2: tiles0 / tiles_total count ROW tiles, the first n_tail workgroups are the backward's tail)
         const int wcs = v2 ? 1 : cs;
         auto launch_wgrad = [&](const SmlWgArgs& g) { return v2 ? sml_launch_tr_wgrad2(d, g, st) : sml_launch_wgrad(d, g, st); };
-        wg.convg_part = ctx->convg.p; wg.tiles0 = f.tiles0 * wcs; wg.tiles_total = tiles * wcs;
+        wg.convg_part = ctx->convg.p; wg.tiles0 = L.tiles0 * wcs; wg.tiles_total = tiles * wcs;
         wg.n_tail = tiles * (d / 16) > 0 ? tiles * (d / 16) : 1; wg.convg_out = ctx->convg.p; wg.arrive = ctx->arrive.p;
         wg.defer_conv = (defer && b + 1 < nb) ? 1 : 0; wg.gelu_b = a2_recompute ? 1 : 0;
-        prev_split = f.tiles0 * (d / 16); prev_total = tiles * (d / 16);
+        prev_split = L.tiles0 * (d / 16); prev_total = tiles * (d / 16);
         const bool peers = !grad_hook && ctx->peer.world > 0;       // peer mappings attached: one-shot push / poll
         const bool native = !grad_hook && !peers && ctx->comm != nullptr;     // a communicator exists: exchange natively
         if (peers) {
             // the weight-gradient workgroups store their finished tiles into every rank's inbox; the Adam launch polls
             // this rank's counters and adds the slots in rank order
-            SmlThetaAdamArgs ad;
-            memset(&ad, 0, sizeof(ad));
+            SmlThetaAdamArgs ad = theta_adam_args(ctx, theta, adam_m, adam_v, grad, weight_decay, sc);
             peer_step(ctx, 0, v2 ? sml_wgrad2_pushers(d) : sml_wgrad_grid(d), &wg.peer, &ad.peer);
-            ctx->prof.begin(PC_WGRAD, st); HIPCHK(launch_wgrad(wg)); ctx->prof.end(st);
-            ad.theta = theta; ad.m = adam_m; ad.v = adam_v; ad.grad = grad; ad.pk = pk_cur(ctx);
-            ad.weight_decay = weight_decay; ad.step_size = sc.step_size; ad.bc2_sqrt = sc.bc2_sqrt;
+            PROFILED(PC_WGRAD, HIPCHK(launch_wgrad(wg)));
             // every workgroup of the Adam kernel polls the counters itself (SML_PEER_POLL_IN_ADAM=0: a one-wavefront
             // k_peer_wait launch ahead of it instead -- one launch more; same results)
             static const bool poll_in_adam = env_int("SML_PEER_POLL_IN_ADAM", 1) != 0;
-            ctx->prof.begin(PC_THETA_ADAM, st);
-            if (clip) {
-                // --clip_grad on the peer carrier: the rank-order sum of the slots is materialised once (k_peer_sum polls
-                // and adds exactly as the fused form would), its norm taken, and the plain Adam launch scales it -- every
-                // rank forms the same bits, so the replicas stay identical
-                HIPCHK(sml_launch_peer_sum(grad, 2 * ns, ad.peer, st, (int)ns));
-                HIPCHK(sml_launch_grad_sumsq(grad, 2 * ns, ctx->clip_sumsq.p, st));
-                ad.peer.world = 0;
-                ad.clip_sumsq = ctx->clip_sumsq.p; ad.clip_max_norm = ctx->clip_max_norm;
-            } else if (!poll_in_adam) { HIPCHK(sml_launch_peer_wait(ad.peer, st)); ad.peer.waited = 1; }
-            HIPCHK(sml_launch_theta_adam(d, ad, st));
-            ctx->prof.end(st);
+            PROFILED(PC_THETA_ADAM, {
+                if (clip) {
+                    // --clip_grad on the peer carrier: the rank-order sum of the slots is materialised once (k_peer_sum polls
+                    // and adds exactly as the fused form would), its norm taken, and the plain Adam launch scales it -- every
+                    // rank forms the same bits, so the replicas stay identical
+                    HIPCHK(sml_launch_peer_sum(grad, 2 * ns, ad.peer, st, (int)ns));
+                    HIPCHK(sml_launch_grad_sumsq(grad, 2 * ns, ctx->clip_sumsq.p, st));
+                    ad.peer.world = 0;
+                    ad.clip_sumsq = ctx->clip_sumsq.p; ad.clip_max_norm = ctx->clip_max_norm;
+                } else if (!poll_in_adam) { HIPCHK(sml_launch_peer_wait(ad.peer, st)); ad.peer.waited = 1; }
+                HIPCHK(sml_launch_theta_adam(d, ad, st));
+            });
         } else if (!grad_hook && !native && !clip) {
             // one GPU: the weight-gradient workgroups take the Adam step for the tiles they own
             // (v2: the refreshed images go to the OTHER set -- the launch's tail workgroups are reading this one)
             wg.theta = theta; wg.m = adam_m; wg.v = adam_v; wg.pk = v2 ? pk_other(ctx) : pk_cur(ctx);
             wg.weight_decay = weight_decay; wg.step_size = sc.step_size; wg.bc2_sqrt = sc.bc2_sqrt;
-            ctx->prof.begin(PC_WGRAD, st); HIPCHK(launch_wgrad(wg)); ctx->prof.end(st);
+            PROFILED(PC_WGRAD, HIPCHK(launch_wgrad(wg)));
             if (v2) ctx->pk_set ^= 1;
         } else {
             // the weight-gradient launch leaves the flat gradient complete (its conv workgroups sum the backward's
             // partials): all-reduce it, then one Adam launch
-            ctx->prof.begin(PC_WGRAD, st); HIPCHK(launch_wgrad(wg)); ctx->prof.end(st);
-            SmlThetaAdamArgs ad;
-            memset(&ad, 0, sizeof(ad));
-            ad.theta = theta; ad.m = adam_m; ad.v = adam_v; ad.grad = grad; ad.pk = pk_cur(ctx);
-            ad.weight_decay = weight_decay; ad.step_size = sc.step_size; ad.bc2_sqrt = sc.bc2_sqrt;
+            PROFILED(PC_WGRAD, HIPCHK(launch_wgrad(wg)));
+            SmlThetaAdamArgs ad = theta_adam_args(ctx, theta, adam_m, adam_v, grad, weight_decay, sc);
             if (native) {
                 NCCLCHK(g_rccl.AllReduce(grad, grad, (size_t)(2 * ns), ncclFloat, ncclSum, ctx->comm, st));
             } else if (grad_hook) {
                 const int hr = grad_hook(hook_user, grad, 2 * ns, b);
                 if (hr != 0) return fail(SML_ESTATE, "sml_tr_stage_epoch", "grad_hook failed");
             }
-            ctx->prof.begin(PC_THETA_ADAM, st);
-            if (clip) {        // (the norm of the job's gradient: after the exchange)
-                HIPCHK(sml_launch_grad_sumsq(grad, 2 * ns, ctx->clip_sumsq.p, st));
-                ad.clip_sumsq = ctx->clip_sumsq.p; ad.clip_max_norm = ctx->clip_max_norm;
-            }
-            HIPCHK(sml_launch_theta_adam(d, ad, st)); ctx->prof.end(st);
+            PROFILED(PC_THETA_ADAM, {
+                if (clip) {        // (the norm of the job's gradient: after the exchange)
+                    HIPCHK(sml_launch_grad_sumsq(grad, 2 * ns, ctx->clip_sumsq.p, st));
+                    ad.clip_sumsq = ctx->clip_sumsq.p; ad.clip_max_norm = ctx->clip_max_norm;
+                }
+                HIPCHK(sml_launch_theta_adam(d, ad, st));
+            });
         }
     }
-    ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)); ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)));
     *step += nb;
     return SML_OK;
 }
@@ -1206,18 +1259,18 @@ int sml_run_mf_grad(sml_ctx* ctx, const float* theta, const float* user_last, co
                     float* theta_grad, void* stream) {
     if (!ctx || !theta || !user_last || !user_hat || !item_last || !item_hat || !loss || B <= 0)
         return fail(SML_EINVAL, "sml_run_mf_grad", "bad argument");
-    if (B > ctx->max_batch) return fail(SML_EINVAL, "sml_run_mf_grad", "batch exceeds ctx max_batch");
-    if (loss_kind < 0 || loss_kind > 3 || (ctx->variant == 1 ? (loss_kind != SML_LOSS_BPR_UNIT && loss_kind != SML_LOSS_BPR_NORM) : loss_kind == SML_LOSS_BPR_UNIT))
-        return fail(SML_EINVAL, "sml_run_mf_grad", "loss_kind (variant 1 takes SML_LOSS_BPR_UNIT, or SML_LOSS_BPR_NORM for run_MF(norm=True); SML_LOSS_BPR_UNIT goes with variant 1 only)");
+    int rc;
+    if ((rc = check_sizes(ctx, "sml_run_mf_grad", B, 0))) return rc;
+    if ((rc = check_loss_kind(ctx, "sml_run_mf_grad", loss_kind))) return rc;
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const int d = ctx->d;
-    int rc;
     if ((rc = ensure_pk(ctx))) return rc;
     if ((rc = ensure_transfer_ws(ctx, B, true, st))) return rc;       // TR-stage saves (a1, a2, dz1, conv partials, flat gradient)
     if ((rc = ensure_transfer_ws(ctx, B, false, st))) return rc;      // + the MF stage's dx rows
-    const int64_t ns = sml_net_size(d), ps = sml_pk_size(d);
-    const int tiles0 = wg_tiles(B, 1), tiles = tiles0 + wg_tiles(2 * B, 1);
+    const int64_t ns = sml_net_size(d);
+    const BatchSlots L(ctx, theta, B);
+    const int tiles0 = L.tiles0, tiles = L.tiles;
     const int fns = fwd_split(tiles);
     const int lstride = tiles * (d / 16 > 4 ? d / 16 : 4);
     const int64_t out_pstride = (int64_t)SML_R * (tiles_of(B) + tiles_of(2 * B)) * d;
@@ -1225,32 +1278,24 @@ int sml_run_mf_grad(sml_ctx* ctx, const float* theta, const float* user_last, co
     HIPCHK(hipMemsetAsync(ctx->loss_part.p, 0, (size_t)2 * lstride * sizeof(float), st));
     HIPCHK(sml_launch_theta_pack(d, theta, pk_cur(ctx), st));
     // ---- forward over contiguous row blocks (identity indexing), with every save the two backward forms need
-    SmlFwdArgs f;
-    memset(&f, 0, sizeof(f));
-    SmlBwdArgs w;
-    memset(&w, 0, sizeof(w));
-    SmlWgArgs wg;
-    memset(&wg, 0, sizeof(wg));
+    SmlFwdArgs f = zeroed<SmlFwdArgs>();
+    SmlBwdArgs w = zeroed<SmlBwdArgs>();
+    SmlWgArgs wg = zeroed<SmlWgArgs>();
     float* grad = theta_grad ? theta_grad : ctx->grad.p;
     for (int s = 0; s < 2; ++s) {
-        const int64_t slot0 = s ? (int64_t)SML_R * tiles_of(B) : 0;
         SmlSeg& sg = f.seg[s];
-        sg.theta = theta + s * ns; sg.pk = pk_cur(ctx) + s * ps;
+        L.fill(sg, s, nullptr);
         sg.xt_tab = s ? item_last : user_last; sg.xh_tab = s ? item_hat : user_hat;
-        sg.tri = nullptr; sg.B = B; sg.is_item = s; sg.n_rows = s ? 2 * B : B;
-        sg.out = ctx->out.p + slot0 * d; sg.z1 = ctx->z1.p + slot0 * SML_HID; sg.xin = ctx->xin.p + slot0 * 3 * d;
-        sg.a1 = ctx->a1.p + slot0 * SML_C2 * d; sg.a2 = ctx->a2.p + slot0 * SML_HID;
-        SmlBwdSeg& bg = w.seg[s];
-        bg.theta = sg.theta; bg.pk = sg.pk; bg.dout = ctx->dout.p + slot0 * d; bg.is_item = s; bg.z1 = sg.z1; bg.xin = sg.xin;
-        bg.dx = ctx->dx.p + slot0 * d; bg.dz1 = ctx->dz1.p + slot0 * SML_HID; bg.n_rows = sg.n_rows;
-        SmlWgSeg& q = wg.seg[s];
-        q.dz1 = bg.dz1; q.a1 = sg.a1; q.dout = bg.dout; q.a2 = sg.a2; q.grad = grad + s * ns; q.n_rows = sg.n_rows;
-        q.theta_net = sg.theta; q.pk_net = sg.pk; q.xin = sg.xin;
+        sg.a1 = L.a1(s); sg.a2 = L.a2(s);
+        L.fill(w.seg[s], s);
+        w.seg[s].dx = L.dx(s, ctx->dx.p); w.seg[s].dz1 = L.dz1(s);
+        L.fill(wg.seg[s], s);
+        wg.seg[s].a2 = L.a2(s); wg.seg[s].grad = grad + s * ns;
     }
-    f.tiles0 = tiles0; f.out_pstride = out_pstride; f.k2 = ctx->variant == 1; f.tiles_total = tiles;
+    L.fill(f, out_pstride, ctx->variant == 1);
     HIPCHK(sml_launch_fwd(d, 1, fns, f, tiles, st));
-    w.tiles0 = tiles0; w.l2 = 0.0f; w.out_all = ctx->out.p; w.B = B; w.ioff = SML_R * tiles_of(B); w.kind = loss_kind; w.scale = 1.0f;
-    w.out_np = fns; w.out_pstride = out_pstride; w.tiles_total = tiles;
+    L.fill(w, loss_kind, fns, out_pstride);
+    w.scale = 1.0f; w.tiles_total = tiles;
     // ---- gradient w.r.t. the x_hat rows: the MF-stage backward (loss partials of this launch are the ones reported)
     if (d_user_hat || d_item_hat || !theta_grad) {
         w.convg_part = nullptr; w.loss_part = ctx->loss_part.p;
@@ -1258,8 +1303,7 @@ int sml_run_mf_grad(sml_ctx* ctx, const float* theta, const float* user_last, co
         wx.seg[0].dz1 = nullptr; wx.seg[1].dz1 = nullptr;
         HIPCHK(sml_launch_bwd(d, bwd_split(tiles), wx, tiles, st));
         if (d_user_hat) HIPCHK(hipMemcpyAsync(d_user_hat, ctx->dx.p, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (d_item_hat) HIPCHK(hipMemcpyAsync(d_item_hat, ctx->dx.p + (size_t)SML_R * tiles_of(B) * d, (size_t)2 * B * d * sizeof(float),
-                                              hipMemcpyDeviceToDevice, st));
+        if (d_item_hat) HIPCHK(hipMemcpyAsync(d_item_hat, L.dx(1, ctx->dx.p), (size_t)2 * B * d * sizeof(float), hipMemcpyDeviceToDevice, st));
         HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, 1, lstride, nullptr, loss, st));
     }
     // ---- gradient w.r.t. theta: backward head + weight-gradient launch WITHOUT the fused Adam (flat gradient only)
@@ -1281,8 +1325,7 @@ int sml_embed_loss_sgd_prepare(sml_ctx* ctx, const int64_t* triples, int64_t n, 
     if (!ctx || !triples || n <= 0 || batch <= 0 || (slot != 0 && slot != 1))
         return fail(SML_EINVAL, "sml_embed_loss_sgd_prepare", "bad argument");
     if (xchg && (xchg->world < 1 || !xchg->items_all)) return fail(SML_EINVAL, "sml_embed_loss_sgd_prepare", "incomplete exchange descriptor");
-    if (batch > ctx->max_batch) return fail(SML_EINVAL, "sml_embed_loss_sgd_prepare", "batch exceeds ctx max_batch");
-    if (n > 0x3fffffff) return fail(SML_EINVAL, "sml_embed_loss_sgd_prepare", "epoch too long");
+    { const int rc = check_sizes(ctx, "sml_embed_loss_sgd_prepare", batch, n); if (rc) return rc; }
     DevGuard g(ctx->device);
     return sort_epoch(&ctx->ix[slot], triples, n, batch, 0, n_user, n_item, true, (hipStream_t)stream, nullptr, xchg);
 }
@@ -1332,14 +1375,14 @@ int sml_embed_loss_sgd_epoch(sml_ctx* ctx, void* w_user, void* w_item, int64_t n
         return fail(SML_ESTATE, "sml_embed_loss_sgd_epoch", "exchange without a hook needs sml_comm_init with the same world size");
     if (dtype_bytes != 4 && dtype_bytes != 2) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch", "dtype_bytes must be 4 or 2");
     if (loss_kind != SML_LOSS_BCE && loss_kind != SML_LOSS_BPR) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch", "loss_kind");
-    if (batch > ctx->max_batch) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch", "batch exceeds ctx max_batch");
-    if (n > 0x3fffffff) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch", "epoch too long");
+    int rc;
+    if ((rc = check_sizes(ctx, "sml_embed_loss_sgd_epoch", batch, n))) return rc;
     if (prepared_slot < -1 || prepared_slot > 1) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch", "prepared_slot");
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const int d = ctx->d;
-    const int64_t nb = (n + batch - 1) / batch;
-    int rc;
+    const BatchWalk bw(triples, n, batch);
+    const int64_t nb = bw.nb;
     HIPCHK(ctx->dx.ensure((size_t)3 * batch * d));
     float* const dxb = xchg ? xchg->dx_local : ctx->dx.p;       // per-occurrence gradient rows of the batch in flight
     const int lpr = d * dtype_bytes / 16;
@@ -1347,7 +1390,7 @@ int sml_embed_loss_sgd_epoch(sml_ctx* ctx, void* w_user, void* w_item, int64_t n
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
     IndexSet* X = &ctx->ix[prepared_slot < 0 ? 0 : prepared_slot];
     if (prepared_slot < 0) {
-        ctx->prof.begin(PC_SORT, st); rc = sort_epoch(X, triples, n, batch, 0, n_user, n_item, true, st, nullptr, xchg); ctx->prof.end(st);
+        PROFILED(PC_SORT, rc = sort_epoch(X, triples, n, batch, 0, n_user, n_item, true, st, nullptr, xchg));
         if (rc) return rc;
     } else if (X->n != n || X->batch != batch || X->triples != triples || X->world != (xchg ? xchg->world : 1)) {
         return fail(SML_ESTATE, "sml_embed_loss_sgd_epoch", "index set was prepared for other triples");
@@ -1368,13 +1411,10 @@ int sml_embed_loss_sgd_epoch(sml_ctx* ctx, void* w_user, void* w_item, int64_t n
         HIPCHK(ctx->hot_part.ensure((size_t)hot_chunks * d));
     }
     for (int64_t b = 0; b < nb; ++b) {
-        const int B = (int)((n - b * batch) < batch ? (n - b * batch) : batch);
-        SmlBareArgs a;
-        memset(&a, 0, sizeof(a));
-        a.w_user = w_user; a.w_item = w_item; a.tri = triples + b * batch * 3; a.B = B; a.dx = dxb;
-        a.loss_part = ctx->loss_part.p + b * lstride; a.kind = loss_kind; a.lam_user = lam_user; a.lam_item = lam_item;
-        a.uniq = X->uniq.p + (size_t)3 * b * batch; a.lr = lr; a.scale = xchg ? xchg->loss_scale : 1.0f;
-        ctx->prof.begin(PC_BARE_GRAD, st); HIPCHK(sml_launch_bare_grad(d, dtype_bytes, a, nullptr, st)); ctx->prof.end(st);
+        const int B = bw.B(b);
+        SmlBareArgs a = bare_args_common(ctx, w_user, w_item, bw, b, lstride, loss_kind, lam_user, lam_item);
+        a.dx = dxb; a.uniq = X->uniq.p + (size_t)3 * b * batch; a.lr = lr; a.scale = xchg ? xchg->loss_scale : 1.0f;
+        PROFILED(PC_BARE_GRAD, HIPCHK(sml_launch_bare_grad(d, dtype_bytes, a, nullptr, st)));
         if (xchg) {     // every rank's item-gradient rows (slots [B, B + 2*batch) of dx; a ragged batch sends its tail along)
             if (xchg->hook) {
                 if (xchg->hook(xchg->hook_user, b) != 0) return fail(SML_ESTATE, "sml_embed_loss_sgd_epoch", "exchange hook failed");
@@ -1382,13 +1422,7 @@ int sml_embed_loss_sgd_epoch(sml_ctx* ctx, void* w_user, void* w_item, int64_t n
                 NCCLCHK(g_rccl.AllGather(dxb + (size_t)B * d, xchg->dx_items_all, (size_t)2 * batch * d, ncclFloat, ctx->comm, st));
             }
         }
-        SmlRunArgs u;
-        memset(&u, 0, sizeof(u));
-        // compacted duplicated-run lists of the whole epoch; the kernels slice out batch b themselves and
-        // stride over it (how many runs a batch has is only known on the device)
-        u.run_u = X->runs_u.p; u.run_i = X->runs_i.p; u.off_u = X->off_u.p; u.off_i = X->off_i.p; u.batch_index = (int)b;
-        u.val_u = X->val_u2.p; u.val_i = X->val_i2.p;
-        if (X->by_hand) { u.cnt_u = X->cnt_u.p; u.cnt_i = X->cnt_i.p; }
+        SmlRunArgs u = run_args_compact(*X, b);
         int64_t max_rec = xchg ? (int64_t)B / 2 + (int64_t)world * 2 * B : (int64_t)3 * B / 2;
         if (known && X->by_hand && !xchg && X->lists_nb == nb && env_int("SML_A3_KNOWN_LISTS", 1)) {
             // the prepared epoch's list slices are on the host: plain arguments, an exact grid
@@ -1406,10 +1440,10 @@ int sml_embed_loss_sgd_epoch(sml_ctx* ctx, void* w_user, void* w_item, int64_t n
         }
         // (grid: one lane group per possible record -- duplicated runs are at most every second occurrence; on several
         // GPUs every item run of the job's list is a record)
-        ctx->prof.begin(PC_SEG_SGD, st); HIPCHK(sml_launch_run_sgd(d, dtype_bytes, u, max_rec, st)); ctx->prof.end(st);
-        if (hot) { ctx->prof.begin(PC_PAIR_LOSS, st); HIPCHK(sml_launch_hot_apply(d, dtype_bytes, u, st)); ctx->prof.end(st); }
+        PROFILED(PC_SEG_SGD, HIPCHK(sml_launch_run_sgd(d, dtype_bytes, u, max_rec, st)));
+        if (hot) { PROFILED(PC_PAIR_LOSS, HIPCHK(sml_launch_hot_apply(d, dtype_bytes, u, st))); }
     }
-    ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)); ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)));
     return SML_OK;
 }
 
@@ -1420,7 +1454,8 @@ int sml_embed_loss_sgd_epoch_sharded(sml_ctx* ctx, void* w_user, int64_t n_user,
         return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch_sharded", "bad argument");
     if (dtype_bytes != 4 && dtype_bytes != 2) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch_sharded", "dtype_bytes must be 4 or 2");
     if (loss_kind != SML_LOSS_BCE && loss_kind != SML_LOSS_BPR) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch_sharded", "loss_kind");
-    if (batch > ctx->max_batch) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch_sharded", "batch exceeds ctx max_batch");
+    int rc;
+    if ((rc = check_sizes(ctx, "sml_embed_loss_sgd_epoch_sharded", batch, 0))) return rc;
     const int W = sh->world;
     if (ctx->peer.world <= 0 || ctx->peer.world != W || ctx->peer.rank != sh->rank)
         return fail(SML_ESTATE, "sml_embed_loss_sgd_epoch_sharded", "needs sml_peer_attach with the same world / rank");
@@ -1434,17 +1469,15 @@ int sml_embed_loss_sgd_epoch_sharded(sml_ctx* ctx, void* w_user, int64_t n_user,
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const int d = ctx->d, me = sh->rank;
-    const int64_t nb = (n + batch - 1) / batch, H = sh->head_rows;
-    int rc;
+    const BatchWalk bw(triples, n, batch);
+    const int64_t nb = bw.nb, H = sh->head_rows;
     HIPCHK(ctx->dx.ensure((size_t)3 * batch * d));
     const int lpr = d * dtype_bytes / 16;
     const int lstride = (int)(((int64_t)batch * lpr + 255) / 256);
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
     if (H > 0) HIPCHK(ctx->head_part.ensure((size_t)H * d));
     HIPCHK(ctx->ptr_tab.ensure(16));
-    ctx->prof.begin(PC_SORT, st);
-    rc = sort_epoch_sharded(&ctx->ix[0], &ctx->ix[1], triples, n, batch, n_user, sh, ctx->peer.rows_cap, st);
-    ctx->prof.end(st);
+    PROFILED(PC_SORT, rc = sort_epoch_sharded(&ctx->ix[0], &ctx->ix[1], triples, n, batch, n_user, sh, ctx->peer.rows_cap, st));
     if (rc) return rc;
     void* inboxes[8];
     for (int q = 0; q < 8; ++q) inboxes[q] = q < W ? ctx->peer.inbox[q] : nullptr;
@@ -1454,59 +1487,46 @@ int sml_embed_loss_sgd_epoch_sharded(sml_ctx* ctx, void* w_user, int64_t n_user,
     IndexSet* A = &ctx->ix[0];
     IndexSet* Bs = &ctx->ix[1];
     for (int64_t b = 0; b < nb; ++b) {
-        const int B = (int)((n - b * batch) < batch ? (n - b * batch) : batch);
+        const int B = bw.B(b);
         // (1) every owner has applied the previous batch (its shard rows are final; this parity's inbox slots are free)
-        if (ctx->peer.done_pending) { ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_peer_wait(ctx->peer.done_poll, st)); ctx->prof.end(st); }
+        if (ctx->peer.done_pending) { PROFILED(PC_MISC, HIPCHK(sml_launch_peer_wait(ctx->peer.done_poll, st))); }
         // (2) gradient pass: tail rows read from their owners, tail gradient rows stored into their owners' inboxes
-        SmlBareArgs a;
-        memset(&a, 0, sizeof(a));
+        SmlBareArgs a = bare_args_common(ctx, w_user, sh->w_item_head, bw, b, lstride, loss_kind, lam_user, lam_item);
         SmlPeerPoll rows_poll;
         int n_blocks = (int)(((int64_t)B * lpr + 255) / 256);
         peer_step(ctx, 1, n_blocks, &a.peer, &rows_poll);
-        a.w_user = w_user; a.w_item = sh->w_item_head; a.tri = triples + b * batch * 3; a.B = B; a.dx = ctx->dx.p;
-        a.loss_part = ctx->loss_part.p + b * lstride; a.kind = loss_kind; a.lam_user = lam_user; a.lam_item = lam_item;
         a.uniq = A->uniq.p + (size_t)3 * b * batch; a.lr = lr; a.scale = sh->loss_scale;
         a.shard_tab = reinterpret_cast<const void* const*>(ctx->ptr_tab.p);
         a.inbox_tab = reinterpret_cast<float* const*>(ctx->ptr_tab.p + 8);
         a.head_rows = H; a.shard_rows = sh->shard_rows;
         a.push_off = (long long)(a.peer.dst[me] - reinterpret_cast<float*>(ctx->peer.inbox[me]));     // the same offset inside every inbox
-        ctx->prof.begin(PC_BARE_GRAD, st); HIPCHK(sml_launch_bare_grad(d, dtype_bytes, a, nullptr, st)); ctx->prof.end(st);
+        PROFILED(PC_BARE_GRAD, HIPCHK(sml_launch_bare_grad(d, dtype_bytes, a, nullptr, st)));
         // (3) all ranks' gradient rows of this batch have landed here -> owner update of this rank's shard (+ its duplicated user rows)
-        ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_peer_wait(rows_poll, st)); ctx->prof.end(st);
-        SmlRunArgs u;
-        memset(&u, 0, sizeof(u));
-        u.run_u = A->runs_u.p; u.run_i = A->runs_i.p; u.off_u = A->off_u.p; u.off_i = A->off_i.p; u.batch_index = (int)b;
-        u.val_u = A->val_u2.p; u.val_i = A->val_i2.p;
-        if (A->by_hand) { u.cnt_u = A->cnt_u.p; u.cnt_i = A->cnt_i.p; }
+        PROFILED(PC_MISC, HIPCHK(sml_launch_peer_wait(rows_poll, st)));
+        SmlRunArgs u = run_args_compact(*A, b);
         u.dx = ctx->dx.p; u.dx_i = rows_poll.slot0; u.w_user = w_user; u.w_item = sh->item_shard[me]; u.lr = lr;
-        ctx->prof.begin(PC_SEG_SGD, st); HIPCHK(sml_launch_run_sgd(d, dtype_bytes, u, (int64_t)B / 2 + (int64_t)W * 2 * B, st)); ctx->prof.end(st);
+        PROFILED(PC_SEG_SGD, HIPCHK(sml_launch_run_sgd(d, dtype_bytes, u, (int64_t)B / 2 + (int64_t)W * 2 * B, st)));
         // (4) tell every rank: this owner is done with batch b
         {
             SmlPeerPush done_push;
             peer_step(ctx, 2, 1, &done_push, &ctx->peer.done_poll);
             ctx->peer.done_pending = true;
-            ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_peer_signal(done_push, st)); ctx->prof.end(st);
+            PROFILED(PC_MISC, HIPCHK(sml_launch_peer_signal(done_push, st)));
         }
         // (5) the replicated head: this rank's occurrences -> dense partial -> one-shot all-reduce -> identical update everywhere
         if (H > 0) {
             HIPCHK(hipMemsetAsync(ctx->head_part.p, 0, (size_t)H * d * sizeof(float), st));
-            SmlRunArgs hgt;
-            memset(&hgt, 0, sizeof(hgt));
-            hgt.run_u = Bs->runs_i.p; hgt.run_i = Bs->runs_i.p; hgt.off_u = Bs->off_u.p; hgt.off_i = Bs->off_i.p; hgt.batch_index = (int)b;
-            hgt.val_u = Bs->val_i2.p; hgt.val_i = Bs->val_i2.p;
-            if (Bs->by_hand) { hgt.cnt_u = Bs->cnt_u.p; hgt.cnt_i = Bs->cnt_i.p; }
+            SmlRunArgs hgt = run_args_compact(*Bs, b);
+            hgt.run_u = Bs->runs_i.p; hgt.val_u = Bs->val_i2.p;       // (list B has no users: both halves name the item list)
             hgt.dx = ctx->dx.p; hgt.dx_i = ctx->dx.p; hgt.w_user = ctx->head_part.p; hgt.w_item = ctx->head_part.p;
             hgt.lr = -1.0f;           // 0 - (-1) * sum = the sum itself, exactly
-            ctx->prof.begin(PC_SEG_SGD, st); HIPCHK(sml_launch_run_sgd(d, 4, hgt, (int64_t)2 * B, st)); ctx->prof.end(st);
+            PROFILED(PC_SEG_SGD, HIPCHK(sml_launch_run_sgd(d, 4, hgt, (int64_t)2 * B, st)));
             SmlPeerPush hp; SmlPeerPoll hq;
             peer_step(ctx, 0, sml_peer_push_blocks(H * d), &hp, &hq);
-            ctx->prof.begin(PC_MISC, st);
-            HIPCHK(sml_launch_peer_push(ctx->head_part.p, H * d, hp, st));
-            HIPCHK(sml_launch_head_apply(d, dtype_bytes, sh->w_item_head, H, lr, hq, st));
-            ctx->prof.end(st);
+            PROFILED(PC_MISC, HIPCHK(sml_launch_peer_push(ctx->head_part.p, H * d, hp, st)); HIPCHK(sml_launch_head_apply(d, dtype_bytes, sh->w_item_head, H, lr, hq, st)));
         }
     }
-    ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)); ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)));
     return SML_OK;
 }
 
@@ -1516,43 +1536,36 @@ int sml_embed_loss_adam_epoch(sml_ctx* ctx, const sml_mf_tables* t, const int64_
         !t->step_item || !triples || !step || !batch_loss || n <= 0 || batch <= 0)
         return fail(SML_EINVAL, "sml_embed_loss_adam_epoch", "bad argument");
     if (loss_kind != SML_LOSS_BCE && loss_kind != SML_LOSS_BPR) return fail(SML_EINVAL, "sml_embed_loss_adam_epoch", "loss_kind");
-    if (batch > ctx->max_batch) return fail(SML_EINVAL, "sml_embed_loss_adam_epoch", "batch exceeds ctx max_batch");
-    if (n > 0x3fffffff) return fail(SML_EINVAL, "sml_embed_loss_adam_epoch", "epoch too long");
+    int rc;
+    if ((rc = check_sizes(ctx, "sml_embed_loss_adam_epoch", batch, n))) return rc;
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const int d = ctx->d;
-    const int64_t nb = (n + batch - 1) / batch;
-    int rc;
+    const BatchWalk bw(triples, n, batch);
+    const int64_t nb = bw.nb;
     if ((rc = ensure_sched(ctx, lr, *step + nb + 1, st))) return rc;
     HIPCHK(ctx->dx.ensure((size_t)3 * batch * d));
     HIPCHK(ctx->xin.ensure((size_t)3 * batch * d)); HIPCHK(ctx->mrep.ensure((size_t)3 * batch * d)); HIPCHK(ctx->vrep.ensure((size_t)3 * batch * d));
     const int lstride = (int)(((int64_t)batch * (d / 4) + 255) / 256);
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
-    ctx->prof.begin(PC_SORT, st); rc = sort_epoch(&ctx->ix[0], triples, n, batch, 0, t->n_user, t->n_item, false, st); ctx->prof.end(st);
+    PROFILED(PC_SORT, rc = sort_epoch(&ctx->ix[0], triples, n, batch, 0, t->n_user, t->n_item, false, st));
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(ctx->loss_part.p, 0, (size_t)nb * lstride * sizeof(float), st));
     for (int64_t b = 0; b < nb; ++b) {
-        const int B = (int)((n - b * batch) < batch ? (n - b * batch) : batch);
+        const int B = bw.B(b);
         const int cur = (int)(*step + 1 + b);
-        SmlBareArgs a;
-        memset(&a, 0, sizeof(a));
-        a.w_user = t->w_user; a.w_item = t->w_item; a.tri = triples + b * batch * 3; a.B = B; a.dx = ctx->dx.p;
-        a.loss_part = ctx->loss_part.p + b * lstride; a.kind = loss_kind; a.lam_user = lam_user; a.lam_item = lam_item;
+        SmlBareArgs a = bare_args_common(ctx, t->w_user, t->w_item, bw, b, lstride, loss_kind, lam_user, lam_item);
         a.m_user = t->m_user; a.v_user = t->v_user; a.m_item = t->m_item; a.v_item = t->v_item;
         a.last_user = t->step_user; a.last_item = t->step_item; a.sched = ctx->sched.p; a.cur_step = cur;
-        a.xrep = ctx->xin.p; a.mrep = ctx->mrep.p; a.vrep = ctx->vrep.p; a.scale = 1.0f;
-        ctx->prof.begin(PC_BARE_GRAD, st); HIPCHK(sml_launch_bare_grad(d, 4, a, nullptr, st)); ctx->prof.end(st);
-        SmlRunArgs u;
-        memset(&u, 0, sizeof(u));
-        u.run_u = ctx->ix[0].rec_u.p + b * batch; u.n_u = B; u.val_u = ctx->ix[0].val_u2.p;
-        u.run_i = ctx->ix[0].rec_i.p + 2 * b * batch; u.n_i = 2 * B; u.val_i = ctx->ix[0].val_i2.p;
-        u.dx = ctx->dx.p; u.dx_i = ctx->dx.p; u.w_user = t->w_user; u.w_item = t->w_item;
-        u.m_user = t->m_user; u.v_user = t->v_user; u.m_item = t->m_item; u.v_item = t->v_item;
-        u.last_user = t->step_user; u.last_item = t->step_item; u.sched = ctx->sched.p; u.cur_step = cur; u.lr = lr; u.sched_len = replay_len(ctx, cur - 1);
-        u.rep_x = ctx->xin.p; u.rep_m = ctx->mrep.p; u.rep_v = ctx->vrep.p; u.rep_u = 1; u.rep_i = 1; u.rep_x_stride = d; u.rep_x_off = 0;
-        ctx->prof.begin(PC_SEG_ADAM, st); HIPCHK(sml_launch_run_adam(d, u, (int64_t)3 * B, st)); ctx->prof.end(st);
+        a.xrep = ctx->xin.p; a.mrep = ctx->mrep.p; a.vrep = ctx->vrep.p;
+        PROFILED(PC_BARE_GRAD, HIPCHK(sml_launch_bare_grad(d, 4, a, nullptr, st)));
+        SmlRunArgs u = run_args_records(ctx->ix[0], bw.off0(b), B);
+        u.dx = ctx->dx.p; u.dx_i = ctx->dx.p;
+        run_args_adam(u, t, ctx, cur, lr);
+        u.rep_i = 1; u.rep_x_stride = d; u.rep_x_off = 0;
+        PROFILED(PC_SEG_ADAM, HIPCHK(sml_launch_run_adam(d, u, (int64_t)3 * B, st)));
     }
-    ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)); ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, (int)nb, lstride, nullptr, batch_loss, st)));
     *step += nb;
     return SML_OK;
 }
@@ -1574,7 +1587,7 @@ int sml_eval_ranks(sml_ctx* ctx, const float* w_user, const float* w_item, const
         return fail(SML_EINVAL, "sml_eval_ranks", "bad argument");
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_EVAL_RANKS, st); HIPCHK(sml_launch_eval_ranks(ctx->d, w_user, w_item, rows, n, n_cols, rank, st)); ctx->prof.end(st);
+    PROFILED(PC_EVAL_RANKS, HIPCHK(sml_launch_eval_ranks(ctx->d, w_user, w_item, rows, n, n_cols, rank, st)));
     return SML_OK;
 }
 
@@ -1588,7 +1601,7 @@ int sml_eval_prepare(sml_ctx* ctx, const int64_t* rows, int64_t n, int n_cols, i
         return fail(SML_EINVAL, "sml_eval_prepare", "item table too large for the blocked evaluation (n_item * d * 4 > 2^32 bytes): use sml_eval_ranks");
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_eval_bucketize(rows, n, n_cols, n_item, rows_b, bucket_off, st)); ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_eval_bucketize(rows, n, n_cols, n_item, rows_b, bucket_off, st)));
     return SML_OK;
 }
 
@@ -1600,9 +1613,7 @@ int sml_eval_ranks_blocked(sml_ctx* ctx, const float* w_user, const float* w_ite
         return fail(SML_EINVAL, "sml_eval_ranks_blocked", "bad argument");
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_EVAL_RANKS, st);
-    HIPCHK(sml_launch_eval_ranks_bucketed(ctx->d, w_user, w_item, rows_b, bucket_off, n, n_cols, rank, max_workgroups, st));
-    ctx->prof.end(st);
+    PROFILED(PC_EVAL_RANKS, HIPCHK(sml_launch_eval_ranks_bucketed(ctx->d, w_user, w_item, rows_b, bucket_off, n, n_cols, rank, max_workgroups, st)));
     return SML_OK;
 }
 
@@ -1648,9 +1659,7 @@ int sml_eval_prepare_sliced(sml_ctx* ctx, const int64_t* rows, int64_t n, int n_
         return fail(SML_EINVAL, "sml_eval_prepare_sliced", "the sliced evaluation needs d = 32, n_item <= 2^20, at most 32767 candidates per row and fewer than 2^31 entries: use sml_eval_prepare");
     DevGuard dg(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_MISC, st);
-    HIPCHK(sml_launch_evs_prepare(rows, n, n_cols, g.ns, work, work + 4 * (int64_t)g.ns * g.n_mb, seg_off, entries, st));
-    ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_evs_prepare(rows, n, n_cols, g.ns, work, work + 4 * (int64_t)g.ns * g.n_mb, seg_off, entries, st)));
     return SML_OK;
 }
 int sml_eval_ranks_sliced(sml_ctx* ctx, const float* w_user, const float* w_item, const int64_t* rows, const uint32_t* entries,
@@ -1666,9 +1675,7 @@ int sml_eval_ranks_sliced(sml_ctx* ctx, const float* w_user, const float* w_item
     float* ug = reinterpret_cast<float*>(scratch);
     float* s0 = ug + n * ctx->d;
     uint16_t* partial = reinterpret_cast<uint16_t*>(s0 + g.n_pad);
-    ctx->prof.begin(PC_EVAL_RANKS, st);
-    HIPCHK(sml_launch_evs_ranks(ctx->d, w_user, w_item, rows, entries, seg_off, n, n_cols, n_item, g.ns, ug, s0, partial, rank, max_workgroups, st));
-    ctx->prof.end(st);
+    PROFILED(PC_EVAL_RANKS, HIPCHK(sml_launch_evs_ranks(ctx->d, w_user, w_item, rows, entries, seg_off, n, n_cols, n_item, g.ns, ug, s0, partial, rank, max_workgroups, st)));
     return SML_OK;
 }
 
@@ -1677,22 +1684,11 @@ int sml_eval_metrics(sml_ctx* ctx, const int32_t* rank, int64_t n, int topk, flo
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) { HIPCHK(hipMemsetAsync(out, 0, 2 * sizeof(float), st)); return SML_OK; }    // no rows: (0 hits, 0 ndcg)
-    ctx->prof.begin(PC_MISC, st); HIPCHK(sml_launch_eval_metrics(rank, n, topk, out, st)); ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_eval_metrics(rank, n, topk, out, st)));
     return SML_OK;
 }
 
 // ---- full-catalogue retrieval (retrieval.hip) ----------------------------------------------------------------------
-// the tail of every entry point below: one launcher call (`launch`, which names the stream st) on the context's device,
-// timed in the PC_MISC profile class; a failure is reported under the launcher call's own text, as HIPCHK does
-#define RUN_MISC(ctx, stream, launch)          \
-    do {                                       \
-        DevGuard g((ctx)->device);             \
-        hipStream_t st = (hipStream_t)(stream); \
-        (ctx)->prof.begin(PC_MISC, st);        \
-        HIPCHK(launch);                        \
-        (ctx)->prof.end(st);                   \
-        return SML_OK;                         \
-    } while (0)
 
 // elem_bytes: 4 for the fp32 entry points (d = 32 / 64), 2 for the _f16 ones (d = 32 / 64 / 128)
 static bool retrieval_args_ok(sml_ctx* ctx, int elem_bytes, int64_t n_item, const int64_t* seen_off, const int32_t* seen_items) {
@@ -1707,7 +1703,9 @@ static int full_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const 
         return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, n_cols >= 2, seen_off and seen_items both or neither)");
     if (n == 0) return SML_OK;
     if (!w_user || !w_item || !rows || !rank) return fail(SML_EINVAL, what, "null argument");
-    RUN_MISC(ctx, stream, sml_launch_full_rank(ctx->d, elem_bytes, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, st));
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_full_rank(ctx->d, elem_bytes, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, st)));
+    return SML_OK;
 }
 
 int sml_full_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* rows, int64_t n,
@@ -1732,7 +1730,9 @@ static int topk_items_impl(const char* what, int elem_bytes, sml_ctx* ctx, const
         return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 1 <= k <= 128, 0 < n_item < 2^31, seen_off and seen_items both or neither)");
     if (n == 0) return SML_OK;
     if (!w_user || !w_item || !users || !scratch || !items || !scores) return fail(SML_EINVAL, what, "null argument");
-    RUN_MISC(ctx, stream, sml_launch_topk(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, st));
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_topk(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, st)));
+    return SML_OK;
 }
 
 int sml_topk_items(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
@@ -1762,8 +1762,10 @@ static int user_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const 
     if (n == 0 || n_pos == 0) return SML_OK;
     if (!w_user || !w_item || !users || !pos_off || !pos_items || !scratch || !above || !pos)
         return fail(SML_EINVAL, what, "null argument");
-    RUN_MISC(ctx, stream, sml_launch_user_rank(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
-                                               seen_items, scratch, above, pos, st));
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_user_rank(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
+                                               seen_items, scratch, above, pos, st)));
+    return SML_OK;
 }
 
 int sml_user_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n,
@@ -1787,7 +1789,9 @@ int sml_user_metrics(sml_ctx* ctx, const int32_t* pos, const int64_t* pos_off, i
     if (!ok) return fail(SML_EINVAL, "sml_user_metrics", "bad argument (ks: 1 to 8 host values >= 1, 0 <= n < 2^31)");
     if (n == 0) return SML_OK;
     if (!pos || !pos_off || !hits || !dcg || !ap || !first) return fail(SML_EINVAL, "sml_user_metrics", "null argument");
-    RUN_MISC(ctx, stream, sml_launch_user_metrics(pos, pos_off, n, ks, n_k, hits, dcg, ap, first, st));
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_user_metrics(pos, pos_off, n, ks, n_k, hits, dcg, ap, first, st)));
+    return SML_OK;
 }
 
 int sml_comm_load(const char* path) {
@@ -2048,9 +2052,7 @@ int sml_sample_negatives(sml_ctx* ctx, const int64_t* users, int64_t n, const in
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(failed, 0, sizeof(int32_t), st));
-    ctx->prof.begin(PC_MISC, st);
-    HIPCHK(sml_launch_sample_negatives(users, n, item_all, pop, user_ptr, n_users, user_items, seed, negs, failed, st));
-    ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_sample_negatives(users, n, item_all, pop, user_ptr, n_users, user_items, seed, negs, failed, st)));
     return SML_OK;
 }
 
@@ -2076,9 +2078,7 @@ int sml_rank_weights(sml_ctx* ctx, const float* w_user, const float* w_item, con
     if (!w_user || !w_item || !rows || !scratch || !score || !rank || !order || !p) return fail(SML_EINVAL, "sml_rank_weights", "null argument");
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    ctx->prof.begin(PC_MISC, st);
-    HIPCHK(sml_launch_rank_weights(ctx->d, w_user, w_item, rows, n, scratch, score, rank, order, p, st));
-    ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_rank_weights(ctx->d, w_user, w_item, rows, n, scratch, score, rank, order, p, st)));
     return SML_OK;
 }
 
@@ -2093,9 +2093,7 @@ int sml_weighted_epoch(sml_ctx* ctx, const int64_t* rows, int64_t n, const int32
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(failed, 0, sizeof(int32_t), st));
     if (n_out == 0) return SML_OK;
-    ctx->prof.begin(PC_MISC, st);
-    HIPCHK(sml_launch_weighted_epoch(rows, n, order, item_all, pop, user_ptr, n_users, user_items, n_out, seed, out3, failed, st));
-    ctx->prof.end(st);
+    PROFILED(PC_MISC, HIPCHK(sml_launch_weighted_epoch(rows, n, order, item_all, pop, user_ptr, n_users, user_items, n_out, seed, out3, failed, st)));
     return SML_OK;
 }
 

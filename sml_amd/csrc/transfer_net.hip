@@ -2513,6 +2513,11 @@ int sml_wgrad_grid(int d);
 hipError_t sml_launch_tr_bwd_head(int d, const SmlBwdArgs& a, int tiles_total, hipStream_t st) {
     if (tiles_total <= 0) return hipSuccess;
     // (leading scalars = the struct's own fields; the kernel derives each segment's z1 / pk / n_rows from them: slot0 = ioff, pk + net * size)
+    // the layout the kernel's preloaded leading parameters stand for: refuse anything else loudly
+    const SmlBwdSeg& s0 = a.seg[0]; const SmlBwdSeg& s1 = a.seg[1];
+    if (s1.z1 != s0.z1 + (int64_t)a.ioff * SML_HID || s1.pk != s0.pk + sml_pk_size(d) || s0.n_rows != a.B || s1.n_rows != 2 * a.B ||
+        s0.is_item != 0 || s1.is_item != 1)
+        return hipErrorInvalidValue;
     SML_DISPATCH_D(d, k_tr_bwd_head<DD><<<dim3(((tiles_total + 1) / 2) * 8), dim3(512), 0, st>>>(a.out_all, a.seg[0].z1, a.seg[0].pk, (long long)a.out_pstride,
                                                                                                    a.B, a.ioff, a.tiles0, a.tiles_total, a.out_np, a));
     return hipGetLastError();

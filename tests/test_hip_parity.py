@@ -1930,20 +1930,15 @@ def test_tr_stage_with_clipped_gradient_norm_vs_oracle(d, B, max_norm):
 
 
 # ----------------------------------------------------------------------------- batch plans (the multi-GPU driver's batches)
-@pytest.mark.parametrize("d", [32, 64])
-def test_planned_batches_of_unequal_size_vs_oracle(d):
-    """sml_batch_plan: what a rank sees when global batches are split by user owner -- batches of unequal length, an
-    EMPTY one (the optimisers still step), per-batch loss scales -- through the MF and the TR stage, against the
-    oracle walking the same plan."""
-    torch.manual_seed(11 + d)
-    U, I = 150, 100
+def _planned_epochs_vs_oracle(d, U, I, sizes, scales, batch):
+    """One MF epoch, a flush and one TR epoch over the plan `sizes` / `scales`, on the library and on the oracle walking the
+    same plan: losses to 1e-4, tables and net to the G3 / G4 Adam bounds."""
     wu, wi = torch.randn(U, d) * 0.3, torch.randn(I, d) * 0.3
-    sizes = [40, 7, 0, 48, 1, 33]
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     n = int(off[-1])
     tri = torch.stack([torch.randint(0, U, (n,)), torch.randint(0, I, (n,)), torch.randint(0, I, (n,))], 1)
     tri[:6, 0] = 3
-    plan = dict(batch_off=off, loss_scale=np.array([0.625, 0.11, 0.0, 0.75, 1.0 / 64, 0.5], dtype=np.float32))
+    plan = dict(batch_off=off, loss_scale=np.array(scales, dtype=np.float32))
     sd, res = None, []
     for eng, dev in ((engine(d, 64), DEV), (O.OracleEngine(d), "cpu")):
         mf = make_mf(U, I, d, wu.numpy(), wi.numpy(), device=dev)
@@ -1953,20 +1948,37 @@ def test_planned_batches_of_unequal_size_vs_oracle(d):
         else:
             net.load_state_dict(sd)
         lu, li = (wu * 0.9).to(dev), (wi * 0.9).to(dev)
-        l_mf = eng.mf_stage_epoch(mf, net, lu, li, tri, 48, 0.01, 1e-6, plan=plan)
+        l_mf = eng.mf_stage_epoch(mf, net, lu, li, tri, batch, 0.01, 1e-6, plan=plan)
         eng.mf_flush(mf)
         hu, hi = mf.user_laten.weight.detach().clone(), mf.item_laten.weight.detach().clone()
-        l_tr = eng.tr_stage_epoch(net, lu, li, hu, hi, tri, 48, 1e-3, 1e-4, plan=plan)
+        l_tr = eng.tr_stage_epoch(net, lu, li, hu, hi, tri, batch, 1e-3, 1e-4, plan=plan)
         tonp = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
         res.append((tonp(l_mf), tonp(l_tr), tonp(hu), tonp(hi), {k: tonp(v) for k, v in net.state_dict().items()}, eng.mf_step, eng.tr_step))
     g, o = res
-    assert g[5] == o[5] == 6 and g[6] == o[6] == 6
+    nb = len(sizes)
+    assert g[5] == o[5] == nb and g[6] == o[6] == nb
     np.testing.assert_allclose(g[0], o[0], rtol=1e-4, atol=1e-9)
     np.testing.assert_allclose(g[1], o[1], rtol=1e-4, atol=1e-9)
-    adam_close(g[2], o[2], 0.01, 6)
-    adam_close(g[3], o[3], 0.01, 6)
+    adam_close(g[2], o[2], 0.01, nb)
+    adam_close(g[3], o[3], 0.01, nb)
     for k in o[4]:
-        adam_close(g[4][k], o[4][k], 1e-3, 6, frac=0.99)
+        adam_close(g[4][k], o[4][k], 1e-3, nb, frac=0.99)
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_planned_batches_of_unequal_size_vs_oracle(d):
+    """sml_batch_plan: what a rank sees when global batches are split by user owner -- batches of unequal length, an
+    EMPTY one (the optimisers still step), per-batch loss scales -- through the MF and the TR stage, against the
+    oracle walking the same plan."""
+    torch.manual_seed(11 + d)
+    _planned_epochs_vs_oracle(d, 150, 100, [40, 7, 0, 48, 1, 33], [0.625, 0.11, 0.0, 0.75, 1.0 / 64, 0.5], 48)
+
+
+def test_planned_batches_at_the_edges_of_the_batch_walk_vs_oracle():
+    """Every edge of the epoch drivers' batch walk in ONE plan (d = 32, batch = 64): a one-row batch, an EMPTY batch, a batch
+    one row past a 32-row tile, and a full batch -- MF and TR stage against the oracle, at the bounds of the plan test above."""
+    torch.manual_seed(43)
+    _planned_epochs_vs_oracle(32, 300, 200, [1, 0, 33, 64], [1.0 / 64, 0.0, 0.5, 1.0], 64)
 
 
 @pytest.mark.parametrize("comm", ["peer", "rccl"])
