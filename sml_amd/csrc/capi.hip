@@ -66,10 +66,16 @@ struct Graveyard {
     }
 } g_graveyard;
 
+// A device buffer that grows on demand.  Whoever declares one owns it: the destructor parks the pointer (never hipFree on the
+// spot, for the reasons above), so no owner keeps a list of its buffers to release -- and none can be copied by accident.
 template <typename T>
 struct Buf {
     T* p = nullptr;
     size_t cap = 0;   // elements
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { g_graveyard.park(p); }
     hipError_t ensure(size_t need) {
         if (need <= cap) return hipSuccess;
         if (p) { g_graveyard.park(p); p = nullptr; cap = 0; }
@@ -79,7 +85,6 @@ struct Buf {
         cap = want;
         return hipSuccess;
     }
-    void release() { g_graveyard.park(p); p = nullptr; cap = 0; }
 };
 
 bool d_ok(int d) { return d == 32 || d == 64 || d == 128; }
@@ -154,10 +159,9 @@ struct Prof {
 // else uint64 ((batch << 32) | row); the key buffers are sized for the wider form.
 struct IndexSet {
     Buf<uint64_t> key_u, key_u2, key_i, key_i2;
-    Buf<uint32_t> val_u, val_u2, val_i, val_i2;
+    Buf<uint32_t> val_u2, val_i2;      // values (slots) in sorted order
     Buf<SmlRun> rec_u, rec_i;          // one record per sorted position
     Buf<SmlRun> runs_u, runs_i;        // compacted: duplicated runs only (bare step)
-    Buf<uint32_t> heads_u, heads_i;    // sorted positions of the duplicated-run heads
     Buf<uint32_t> hot_list;            // [nb][hot_cap][3] hot runs of every batch (bare step, large batches)
     Buf<int> hot_count;                // [nb]
     int hot_cap = 0;                   // 0: the hot-row path is off for this epoch's batch size
@@ -169,15 +173,18 @@ struct IndexSet {
     Buf<SmlRun> dense_rec; Buf<int> dense_n; Buf<SmlTileHdr> tile_hdr; Buf<uint2> tile_ent, tile_spill; Buf<int> spill_cnt;
     bool dense = false; int tiles_cap = 0;
     Buf<int> off_u, off_i, n_sel;
-    // index_prep.hip (the by-hand preparation): tile histograms, bucket offsets / counts, run counts, oversized buckets
-    Buf<uint32_t> hist_u, hist_i, bko_u, bko_i, bkc_u, bkc_i, large, medium;
-    Buf<SmlRun> stage_u, stage_i;      // per-bucket stretches of run records before the compaction
+    // index_prep.hip (the by-hand preparation): tile histograms, bucket offsets, run counts, oversized buckets
+    Buf<uint32_t> hist_u, hist_i, bko_u, bko_i, large, medium;
     Buf<int> cnt_u, cnt_i;
     Buf<int> rank_viol;      // [0]: lanes the start-up probe found served out of lane order by a returning LDS atomic (wave_rank)
     bool rank_probed = false;
     bool by_hand = false;              // the lists were built by index_prep.hip: a batch's runs are off[b] .. off[b] + cnt[b]
+#ifdef SML_TEST_PREP_REFERENCE         // what only the library-sort reference (tests/csrc/prep_cub_reference.inc) uses
+    Buf<uint32_t> val_u, val_i;        // values in occurrence order, the sort's input
+    Buf<uint32_t> heads_u, heads_i;    // sorted positions of the duplicated-run heads
     Buf<char> cub_tmp;
     int key_bytes = 8, row_bits_u = 32, row_bits_i = 32;
+#endif
     int* viol_host = nullptr;          // pinned: entries emit_bucket found out of (row, value) order, ever (SmlPrepArgs.order_viol)
     hipEvent_t viol_ready = nullptr;
     int* max_len_host = nullptr;       // pinned: longest duplicated run of the prepared epoch (0 if none exceeds SML_HOT)
@@ -185,15 +192,7 @@ struct IndexSet {
     int64_t lists_host_nb = 0, lists_nb = 0;   // (capacity; batches of the prepared epoch, 0: not read back) batches' places in the run lists, read back with max_len (same event): the run kernel then needs no offset / count loads
     hipEvent_t ready = nullptr;        // recorded after the copy into max_len_host
     int64_t n = -1; int batch = 0; const void* triples = nullptr; int world = 1;   // what was prepared here
-    void release() {
-        key_u.release(); key_u2.release(); key_i.release(); key_i2.release();
-        val_u.release(); val_u2.release(); val_i.release(); val_i2.release();
-        rec_u.release(); rec_i.release(); runs_u.release(); runs_i.release();
-        hist_u.release(); hist_i.release(); bko_u.release(); bko_i.release(); bkc_u.release(); bkc_i.release(); large.release(); medium.release();
-        cnt_u.release(); cnt_i.release(); stage_u.release(); stage_i.release(); rank_viol.release();
-        dense_rec.release(); dense_n.release(); tile_hdr.release(); tile_ent.release(); tile_spill.release(); spill_cnt.release();
-        uniq.release(); slot_info.release(); heads_u.release(); heads_i.release(); hot_list.release(); hot_count.release(); off_u.release(); off_i.release(); n_sel.release();
-        cub_tmp.release();
+    void release() {                   // what is not a Buf: the pinned blocks and the events
         if (max_len_host) { g_graveyard.park_host(max_len_host); max_len_host = nullptr; }
         if (viol_host) { g_graveyard.park_host(viol_host); viol_host = nullptr; }
         if (viol_ready) { (void)hipEventDestroy(viol_ready); viol_ready = nullptr; }
@@ -227,7 +226,6 @@ struct sml_ctx {
     std::vector<SchedRetired> sched_retired;     // replaced schedule tables / their pinned sources, freed once idle
     hipEvent_t sched_ready = nullptr;            // behind the newest table's upload
     hipStream_t sched_stream = nullptr;
-    Buf<int32_t> dummy;
     Buf<SmlRun> rec_x;       // run records of the multi-GPU global item list (caller-sorted keys)
     Buf<int32_t> xoff;       // ... and, for lists the library builds itself, the batches' offsets in the occurrence stream
     ncclComm_t comm = nullptr;
@@ -252,17 +250,12 @@ struct sml_ctx {
     Buf<void*> ptr_tab;      // sharded bare step: [0..8) shard pointers, [8..16) inbox bases (device table, per-lane indexed)
     Prof prof;
 
-    void release_all() {
+    void release_all() {               // what is not a Buf (those park themselves when the context is deleted)
         prof.release();
-        out.release(); dout.release(); dx.release(); xin.release(); z1.release(); a1.release(); a2.release(); dz1.release();
-        mrep.release(); vrep.release();
-        pk.release(); pkx.release(); grad.release(); convg.release(); loss_part.release(); arrive.release(); run_arrive.release(); cstate.release();
         ix[0].release(); ix[1].release();
-        sched.release(); dummy.release(); rec_x.release(); xoff.release();
         for (auto& r : sched_retired) { g_graveyard.park(r.dev); g_graveyard.park_host(r.host); (void)hipEventDestroy(r.done); }
         sched_retired.clear();
         if (sched_ready) { (void)hipEventDestroy(sched_ready); sched_ready = nullptr; }
-        hot_first.release(); hot_part.release(); head_part.release(); ptr_tab.release();
         if (peer.err) { g_graveyard.park(peer.err); peer.err = nullptr; }
     }
 };
@@ -575,11 +568,17 @@ static bool prep_by_hand() {
     const char* e = getenv("SML_PREP");          // (read per call: the A/B test flips it inside one process)
     return !(e && !strcmp(e, "cub"));
 }
+// ... and the by-hand preparation's own debug switches, read once per preparation (per call: the A/B tests flip them inside one process)
+struct PrepSwitches {
+    bool nowave;     // SML_PREP_NOWAVE (set): no one-wavefront-per-bucket kernels (k_prep_wave, k_prep_count)
+    bool count;      // SML_PREP_COUNT=0 clears it: no counter-per-row kernel (k_prep_count)
+    bool ballot;     // SML_PREP_RANK=ballot: the ballot ranking whatever the start-up probe found
+    static PrepSwitches read() {
+        const char* rk = getenv("SML_PREP_RANK");
+        return {getenv("SML_PREP_NOWAVE") != nullptr, env_int("SML_PREP_COUNT", 1) != 0, rk && !strcmp(rk, "ballot")};
+    }
+};
 
-// The same lists as sort_epoch below, built by index_prep.hip (one GPU's own occurrences; no library code).
-// mode 0: this rank's own occurrences.  1: replicated items on several GPUs (bx: the item lists are the JOB's).
-// 2 / 3: the item-sharded step's lists A (users + the job's occurrences of the tail rows this rank owns) and B (this
-// rank's own occurrences of head rows; no users) -- sh, rows_cap.  See occ_of in index_prep.hip.
 // a completed read-back of the sorted-order violation count that is not zero: some earlier list of this index set was wrong
 int sort_order_check(IndexSet* c) {
     if (c->viol_host && c->viol_ready && hipEventQuery(c->viol_ready) == hipSuccess && *c->viol_host != 0) {
@@ -592,33 +591,91 @@ int sort_order_check(IndexSet* c) {
     }
     return SML_OK;
 }
-int prep_epoch(IndexSet* c, const int64_t* tri, int64_t n, int batch, int pad_tiles, int64_t n_user, int64_t n_item,
-               bool dups, hipStream_t st, const sml_batch_plan* plan, int mode = 0, const sml_bare_exchange* bx = nullptr,
-               const sml_bare_shard* sh = nullptr, int64_t rows_cap = 0, bool want_dense = false, const uint32_t* x_vals = nullptr) {
-    const int64_t nb = plan ? plan->n_batches : (n + batch - 1) / batch;
-    { const int vrc = sort_order_check(c); if (vrc) return vrc; }
-    c->by_hand = true; c->slot_stride = 0; c->dense_stride = 0; c->dense = false;
-    if (n == 0) { c->n = 0; c->batch = batch; c->triples = tri; return SML_OK; }
-    const int W = mode == 1 ? bx->world : (mode == 2 ? sh->world : 1);
-    const int nis = mode == 4 ? 1 : 2 * W;                  // item streams per tile (mode 4: one stream of explicit occurrences)
-    const int64_t n_items = (int64_t)nis * n;               // item occurrences of the epoch's lists (upper bound in modes 2 / 3)
-    if (n_items > 0x7fffffff) return fail(SML_EINVAL, "index preparation", "too many item occurrences in one epoch");
-    const bool has_users = mode != 3 && mode != 4, allruns_i = mode != 0;
-    SmlPrepArgs a = zeroed<SmlPrepArgs>();
-    a.tri = tri; a.n = n; a.batch = batch; a.nb = (int)nb; a.tpb = (batch + SML_PREP_TT - 1) / SML_PREP_TT;
-    a.boff = plan ? plan->batch_off_dev : nullptr; a.pad_tiles = pad_tiles; a.records = dups ? 0 : 1;
-    a.mode = mode; a.has_users = has_users ? 1 : 0; a.nis = nis;
-    if (mode == 1) { a.items_all = bx->items_all; a.val_q = (int64_t)2 * batch; }
-    if (mode == 2) { a.items_all = sh->items_all; a.val_q = rows_cap; }
-    if (mode == 4) { a.x_keys = reinterpret_cast<const uint64_t*>(tri); a.x_vals = x_vals; a.tri = nullptr; }
-    if (mode == 2 || mode == 3) { a.head_rows = sh->head_rows; a.shard_rows = sh->shard_rows; a.shard_rank = sh->rank; }
-    const int64_t ioff_max = pad_tiles ? ((int64_t)(batch + SML_R - 1) / SML_R) * SML_R : batch;
-    // values: users < batch; items < ioff + 2 * batch (own), < world * 2 * batch (mode 1), < world * rows_cap (mode 2), < 3 * batch (mode 3)
-    const int64_t max_val_i = mode == 1 ? (int64_t)W * 2 * batch : mode == 2 ? (int64_t)W * rows_cap : mode == 3 ? (int64_t)3 * batch
-                              : mode == 4 ? rows_cap : ioff_max + 2 * (int64_t)batch;        // (mode 4: rows_cap carries the largest value + 1)
-    const int64_t rows_i = mode == 2 ? sh->shard_rows : mode == 3 ? (sh->head_rows > 0 ? sh->head_rows : 1) : n_item;
-    int vb[2] = {ceil_log2(batch), ceil_log2(max_val_i)};
-    int lb[2], rb[2] = {n_user > 0 ? ceil_log2(n_user) : 32, rows_i > 0 ? ceil_log2(rows_i) : 32};
+
+// Where the occurrences of an epoch's index lists come from, and the slot layout their values address.  The five sources
+// (the enum's values are SmlPrepArgs.mode; see occ_of in index_prep.hip):
+//   OWN         this rank's own triples: users, and per triple two item streams (one GPU; no library code).
+//   REPLICATED  replicated items on several GPUs: the users are this rank's, the item lists the JOB's -- every rank's 2n item
+//               occurrences from the gathered item columns, rank q's values at q * 2 * batch.
+//   SHARD_TAIL  the item-sharded step's list A: this rank's users and the job's occurrences of the tail rows this rank owns,
+//               rank q's values at q * rows_cap (the rows of a peer slot).
+//   SHARD_HEAD  ... and its list B: this rank's own occurrences of head rows (summed into the dense partial); no users.
+//   PAIRS       one stream of explicit (key, value) item occurrences, batch-major (the MF stage's job-wide item lists on
+//               several GPUs); a "batch" is the longest list; no users, no triples.
+// Everything that depends on the source is decided HERE, once, by the five constructors; the preparation reads the fields.
+struct PrepSource {
+    enum Kind { OWN = 0, REPLICATED = 1, SHARD_TAIL = 2, SHARD_HEAD = 3, PAIRS = 4 };
+    Kind kind;
+    const int64_t* tri = nullptr;                                        // the triples (PAIRS: none)
+    const uint64_t* x_keys = nullptr; const uint32_t* x_vals = nullptr;  // PAIRS: the occurrences
+    const int64_t* items_all = nullptr; int64_t val_q = 0;               // gathered item columns of the job; value stride per rank
+    int64_t head_rows = 0, shard_rows = 0; int shard_rank = 0;           // the sharded step's item layout
+    int batch, pad_tiles;                // triples (PAIRS: occurrences) of a full batch; items start at a whole SML_R rows
+    int world = 1, nis = 2;              // ranks whose occurrences the item lists hold; item streams per tile
+    bool has_users = true, allruns_i = false;       // a user list; EVERY item run gets a record (the run kernel applies them all)
+    int64_t rows_u, rows_i;              // rows the entries' row bits must hold (0: unknown, 32 bits)
+    int64_t ioff_max, val_bound_i;       // first item slot of a full batch; item values stay below val_bound_i (users: below batch)
+    bool slot_info = false;              // records mode: every slot learns where its run's record is (and the distinct-row form may follow)
+    bool hot_rows = false;               // compact mode: long runs may be listed per batch for the hot-row kernels
+    bool list_readback = false;          // compact mode: the batches' run offsets and counts travel to the host
+    bool ascend_planned = true;          // a plan's lists still hold their values in ascending order
+    bool reusable = true;                // a later epoch call may take these lists for its own (IndexSet.n records the length)
+    const void* origin() const { return tri ? (const void*)tri : (const void*)x_keys; }     // what IndexSet.triples records
+
+    static PrepSource own(const int64_t* tri, int64_t n_user, int64_t n_item, int batch, int pad_tiles) {
+        PrepSource s(OWN, batch, pad_tiles, n_user, n_item);
+        s.tri = tri; s.val_bound_i = s.ioff_max + 2 * (int64_t)batch;
+        s.slot_info = s.hot_rows = s.list_readback = true;
+        return s;
+    }
+    static PrepSource replicated(const int64_t* tri, const sml_bare_exchange* bx, int64_t n_user, int64_t n_item, int batch, int pad_tiles) {
+        PrepSource s(REPLICATED, batch, pad_tiles, n_user, n_item);
+        s.tri = tri; s.items_all = bx->items_all; s.val_q = (int64_t)2 * batch;
+        s.world = bx->world; s.nis = 2 * bx->world; s.allruns_i = true; s.val_bound_i = (int64_t)bx->world * 2 * batch;
+        s.hot_rows = true;
+        return s;
+    }
+    static PrepSource shard_tail(const int64_t* tri, const sml_bare_shard* sh, int64_t rows_cap, int64_t n_user, int batch) {
+        PrepSource s(SHARD_TAIL, batch, 0, n_user, sh->shard_rows);
+        s.tri = tri; s.items_all = sh->items_all; s.val_q = rows_cap; s.shard(sh);
+        s.world = sh->world; s.nis = 2 * sh->world; s.allruns_i = true; s.val_bound_i = (int64_t)sh->world * rows_cap;
+        s.reusable = false;
+        return s;
+    }
+    static PrepSource shard_head(const int64_t* tri, const sml_bare_shard* sh, int64_t n_user, int batch) {
+        PrepSource s(SHARD_HEAD, batch, 0, n_user, sh->head_rows > 0 ? sh->head_rows : 1);     // (n_user: the entry width of list A)
+        s.tri = tri; s.shard(sh);
+        s.has_users = false; s.allruns_i = true; s.val_bound_i = (int64_t)3 * batch;
+        s.reusable = false;
+        return s;
+    }
+    static PrepSource pairs(const uint64_t* keys, const uint32_t* vals, int64_t value_bound, int64_t n_item, int longest) {
+        PrepSource s(PAIRS, longest, 0, 1, n_item);        // (no user table: no user row bits)
+        s.x_keys = keys; s.x_vals = vals;
+        s.nis = 1; s.has_users = false; s.allruns_i = true; s.val_bound_i = value_bound;
+        s.ascend_planned = false;        // (unequal batches: the driver's owner-split lists, values = slots by owner)
+        s.reusable = false;
+        return s;
+    }
+private:
+    PrepSource(Kind k, int batch_, int pad, int64_t ru, int64_t ri)
+        : kind(k), batch(batch_), pad_tiles(pad), rows_u(ru), rows_i(ri),
+          ioff_max(pad ? ((int64_t)(batch_ + SML_R - 1) / SML_R) * SML_R : batch_), val_bound_i(0) {}
+    void shard(const sml_bare_shard* sh) { head_rows = sh->head_rows; shard_rows = sh->shard_rows; shard_rank = sh->rank; }
+};
+
+// Job 1 of a preparation: the bit widths and the bucket geometry -- every scalar of the kernels' arguments; returns the entry
+// width in bytes.  Pure: no HIP call, no IndexSet.
+int prep_geometry(SmlPrepArgs& a, const PrepSource& s, int64_t n, int64_t nb, const sml_batch_plan* plan, bool dups, bool want_dense,
+                  const PrepSwitches& sw) {
+    const int batch = s.batch, nis = s.nis;
+    a.tri = s.tri; a.n = n; a.batch = batch; a.nb = (int)nb; a.tpb = (batch + SML_PREP_TT - 1) / SML_PREP_TT;
+    a.boff = plan ? plan->batch_off_dev : nullptr; a.pad_tiles = s.pad_tiles; a.records = dups ? 0 : 1;
+    a.mode = s.kind; a.has_users = s.has_users ? 1 : 0; a.nis = nis;
+    a.items_all = s.items_all; a.val_q = s.val_q; a.x_keys = s.x_keys; a.x_vals = s.x_vals;
+    a.head_rows = s.head_rows; a.shard_rows = s.shard_rows; a.shard_rank = s.shard_rank;
+    int vb[2] = {ceil_log2(batch), ceil_log2(s.val_bound_i)};
+    int lb[2], rb[2] = {s.rows_u > 0 ? ceil_log2(s.rows_u) : 32, s.rows_i > 0 ? ceil_log2(s.rows_i) : 32};
     for (int T = 0; T < 2; ++T) {
         const int64_t max_n = (int64_t)(T ? nis : 1) * batch;
         lb[T] = max_n <= SML_PREP_SMALL ? 0 : ceil_log2((max_n + 1023) / 1024);
@@ -629,117 +686,154 @@ int prep_epoch(IndexSet* c, const int64_t* tri, int64_t n, int batch, int pad_ti
     for (int T = 0; T < 2; ++T) if (rb[T] + vb[T] - 32 > 10) narrow = false;
     if (narrow) { for (int T = 0; T < 2; ++T) if (rb[T] + vb[T] - 32 > lb[T]) lb[T] = rb[T] + vb[T] - 32; }
     else vb[0] = vb[1] = 32;
-    Buf<uint32_t>* hist[2] = {&c->hist_u, &c->hist_i};
-    Buf<uint32_t>* bko[2] = {&c->bko_u, &c->bko_i};
-    HIPCHK(c->key_u.ensure((size_t)n + 1)); HIPCHK(c->key_u2.ensure((size_t)n + 1));
-    HIPCHK(c->key_i.ensure((size_t)n_items + 1)); HIPCHK(c->key_i2.ensure((size_t)n_items + 1));
-    HIPCHK(c->val_u2.ensure((size_t)n + 1)); HIPCHK(c->val_i2.ensure((size_t)n_items + 1));
-    HIPCHK(c->n_sel.ensure(4));
-    const size_t large_cap = (size_t)((n + n_items) / SML_PREP_SMALL) + 8;
-    HIPCHK(c->large.ensure(2 * large_cap));
-    const size_t runs_i_cap = (size_t)(allruns_i ? n_items : n) + 8;       // duplicated runs: at most every second occurrence
-    if (dups) {
-        HIPCHK(c->uniq.ensure((size_t)3 * nb * batch));
-        HIPCHK(c->runs_u.ensure((size_t)n / 2 + 8)); HIPCHK(c->runs_i.ensure(runs_i_cap));
-        HIPCHK(c->off_u.ensure((size_t)nb + 1)); HIPCHK(c->off_i.ensure((size_t)nb + 1));
-        HIPCHK(c->cnt_u.ensure((size_t)(nb + 1) * SML_PREP_CNT_STRIDE)); HIPCHK(c->cnt_i.ensure((size_t)(nb + 1) * SML_PREP_CNT_STRIDE));
-    } else {
-        HIPCHK(c->rec_u.ensure((size_t)n)); HIPCHK(c->rec_i.ensure((size_t)(n_items > 2 * n ? n_items : 2 * n)));
-        if (mode == 0) {          // every slot learns where its run's record is (the MF stage's fused row update)
-            c->slot_stride = ioff_max + 2 * (int64_t)batch;
-            HIPCHK(c->slot_info.ensure((size_t)nb * c->slot_stride));
-            a.slot_info = c->slot_info.p; a.slot_stride = c->slot_stride;
-            // distinct-row form: both lists must be ONE bucket each (the numbering is the bucket's), i.e. 2 * batch <= SML_PREP_SMALL
-            if (want_dense && pad_tiles && 2 * (int64_t)batch <= SML_PREP_SMALL) {
-                c->tiles_cap = wg_tiles(batch, 1) + wg_tiles(2 * batch, 1);
-                // records are addressed by SCRATCH ROW, which reaches the end of a list's last tile: whole tiles per list
-                c->dense_stride = ioff_max + (int64_t)SML_TM * wg_tiles(2 * batch, 1);
-                HIPCHK(c->dense_rec.ensure((size_t)nb * c->dense_stride)); HIPCHK(c->dense_n.ensure((size_t)2 * nb));
-                HIPCHK(c->tile_hdr.ensure((size_t)nb * c->tiles_cap)); HIPCHK(c->tile_ent.ensure((size_t)nb * c->tiles_cap * SML_TILE_ENT));
-                HIPCHK(c->tile_spill.ensure((size_t)nb * 3 * batch)); HIPCHK(c->spill_cnt.ensure((size_t)nb));
-                HIPCHK(hipMemsetAsync(c->spill_cnt.p, 0, (size_t)nb * sizeof(int), st));
-                a.dense = 1; a.dense_rec = c->dense_rec.p; a.dense_stride = c->dense_stride; a.dense_n = c->dense_n.p; a.tile_hdr = c->tile_hdr.p; a.tile_ent = c->tile_ent.p;
-                a.tile_spill = c->tile_spill.p; a.spill_cnt = c->spill_cnt.p; a.tiles_cap = c->tiles_cap;
-            }
-        }
-    }
     for (int T = 0; T < 2; ++T) {
         SmlPrepTable& t = a.t[T];
+        const int64_t per_bucket = ((int64_t)(T ? nis : 1) * batch) >> lb[T];
         t.lb = lb[T]; t.nbk = 1 << lb[T];
         t.hb = rb[T] > lb[T] ? rb[T] - lb[T] : 0; t.vb = vb[T];
         t.npass = (t.hb + 8) / 9; t.pbits = t.npass ? (t.hb + t.npass - 1) / t.npass : 0;
-        t.allruns = (T == 1 && allruns_i) ? 1 : 0; t.rshift = t.allruns ? 0 : 1;
+        t.allruns = (T == 1 && s.allruns_i) ? 1 : 0; t.rshift = t.allruns ? 0 : 1;
         t.lmul = T ? nis : 1;
-        t.ntile = T ? nis * a.tpb : (has_users ? a.tpb : 0);
-        t.wave = (dups && !t.allruns && ((int64_t)(T ? nis : 1) * batch >> t.lb) <= 256 && !getenv("SML_PREP_NOWAVE")) ? 1 : 0;
-        // few row bits left inside a bucket: a counter per row instead of a sort (k_prep_count; SML_PREP_COUNT=0: A/B tests)
-        if (dups && !t.allruns && t.nbk > 1 && (1 << t.hb) <= SML_PREP_CROWS && ((int64_t)(T ? nis : 1) * batch >> t.lb) <= 1024 &&
-            env_int("SML_PREP_COUNT", 1) != 0 && !getenv("SML_PREP_NOWAVE")) t.wave = 2;
-        HIPCHK(hist[T]->ensure((size_t)nb * (T ? nis : 1) * a.tpb * t.nbk));
-        HIPCHK(bko[T]->ensure((size_t)2 * nb * t.nbk));
-        t.hist = hist[T]->p; t.bk = reinterpret_cast<uint2*>(bko[T]->p); t.brc = nullptr;
-        t.ent = T ? (void*)c->key_i.p : (void*)c->key_u.p; t.ent2 = T ? (void*)c->key_i2.p : (void*)c->key_u2.p;
-        t.vals = T ? c->val_i2.p : c->val_u2.p;
-        if (dups) { t.runs_tmp = nullptr; t.runs = T ? c->runs_i.p : c->runs_u.p; t.run_off = T ? c->off_i.p : c->off_u.p; t.run_cnt = T ? c->cnt_i.p : c->cnt_u.p; }
-        else t.runs = T ? c->rec_i.p : c->rec_u.p;
+        t.ntile = T ? nis * a.tpb : (s.has_users ? a.tpb : 0);
+        const bool by_wave = dups && !t.allruns && !sw.nowave;
+        t.wave = (by_wave && per_bucket <= 256) ? 1 : 0;
+        // few row bits left inside a bucket: a counter per row instead of a sort (k_prep_count)
+        if (by_wave && t.nbk > 1 && (1 << t.hb) <= SML_PREP_CROWS && per_bucket <= 1024 && sw.count) t.wave = 2;
     }
-    a.large = c->large.p; a.n_large = c->n_sel.p + 3; a.large_cap = (int)large_cap;
-    HIPCHK(c->medium.ensure((size_t)2 * nb * (a.t[0].nbk + a.t[1].nbk) + 2));
-    a.medium = c->medium.p; a.n_medium = c->n_sel.p;
-    c->hot_cap = 0;
+    a.large_cap = (int)((n + (int64_t)nis * n) / SML_PREP_SMALL) + 8;
     if (dups) {
-        a.uniq = has_users ? c->uniq.p : nullptr; a.uniq_stride = (int64_t)3 * batch; a.max_len = c->n_sel.p + 2;
+        a.uniq_stride = (int64_t)3 * batch;
         const int64_t hot_cap64 = ((int64_t)batch + (int64_t)nis * batch) / SML_HOT + 8;
         const int hot_cap = (int)(hot_cap64 < 0x7fffffff ? hot_cap64 : 0x7fffffff);
-        c->hot_cap = (mode <= 1 && batch >= 4096 && hot_cap <= SML_HOT_MAXCAP) ? hot_cap : 0;      // (the sharded step has no hot-row path)
-        if (c->hot_cap) {
-            HIPCHK(c->hot_list.ensure((size_t)nb * c->hot_cap * 3)); HIPCHK(c->hot_count.ensure((size_t)nb));
-            a.hot_list = c->hot_list.p; a.hot_count = c->hot_count.p; a.hot_cap = c->hot_cap;
+        a.hot_cap = (s.hot_rows && batch >= 4096 && hot_cap <= SML_HOT_MAXCAP) ? hot_cap : 0;
+    } else if (s.slot_info) {
+        a.slot_stride = s.ioff_max + 2 * (int64_t)batch;
+        // distinct-row form: both lists must be ONE bucket each (the numbering is the bucket's), i.e. 2 * batch <= SML_PREP_SMALL.
+        // Where wide rows forced more buckets all the same, the buffers are still laid out (dense_stride, tiles_cap) and the
+        // per-occurrence form runs (dense = 0).
+        if (want_dense && s.pad_tiles && 2 * (int64_t)batch <= SML_PREP_SMALL) {
+            a.tiles_cap = wg_tiles(batch, 1) + wg_tiles(2 * batch, 1);
+            // records are addressed by SCRATCH ROW, which reaches the end of a list's last tile: whole tiles per list
+            a.dense_stride = s.ioff_max + (int64_t)SML_TM * wg_tiles(2 * batch, 1);
+            a.dense = (a.t[0].nbk == 1 && a.t[1].nbk == 1) ? 1 : 0;
         }
     }
-    // stable ranks from one returning LDS atomic per occurrence -- only where this device hands them out in lane order:
-    // measured once per index set, on the stream, ahead of its first preparation (no host wait: the kernels read the count)
-    if (!c->rank_probed) {
-        HIPCHK(c->rank_viol.ensure(4));
-        HIPCHK(hipMemsetAsync(c->rank_viol.p, 0, 4 * sizeof(int), st));
-        HIPCHK(sml_launch_rank_probe(c->rank_viol.p, st));
-        c->rank_probed = true;
+    a.vals_ascend = (!plan || s.ascend_planned) ? 1 : 0;
+    return narrow ? 4 : 8;
+}
+
+// Job 2: the buffers of index set `c` sized for that geometry, and their pointers in the kernels' arguments.  (Its one stream
+// operation clears the spill counters of the distinct-row form.)
+int prep_buffers(IndexSet* c, SmlPrepArgs& a, const PrepSource& s, bool dups, const PrepSwitches& sw, hipStream_t st) {
+    const size_t n = (size_t)a.n, n_items = (size_t)s.nis * n, nb = (size_t)a.nb, batch = (size_t)a.batch;
+    HIPCHK(c->key_u.ensure(n + 1)); HIPCHK(c->key_u2.ensure(n + 1));
+    HIPCHK(c->key_i.ensure(n_items + 1)); HIPCHK(c->key_i2.ensure(n_items + 1));
+    HIPCHK(c->val_u2.ensure(n + 1)); HIPCHK(c->val_i2.ensure(n_items + 1));
+    HIPCHK(c->n_sel.ensure(4));
+    HIPCHK(c->large.ensure(2 * (size_t)a.large_cap));
+    c->slot_stride = a.slot_stride; c->dense_stride = a.dense_stride; c->dense = a.dense != 0; c->hot_cap = a.hot_cap;
+    if (dups) {
+        HIPCHK(c->uniq.ensure(3 * nb * batch));
+        HIPCHK(c->runs_u.ensure(n / 2 + 8)); HIPCHK(c->runs_i.ensure((s.allruns_i ? n_items : n) + 8));      // duplicated runs: at most every second occurrence
+        HIPCHK(c->off_u.ensure(nb + 1)); HIPCHK(c->off_i.ensure(nb + 1));
+        HIPCHK(c->cnt_u.ensure((nb + 1) * SML_PREP_CNT_STRIDE)); HIPCHK(c->cnt_i.ensure((nb + 1) * SML_PREP_CNT_STRIDE));
+        a.uniq = s.has_users ? c->uniq.p : nullptr; a.max_len = c->n_sel.p + 2;
+        if (a.hot_cap) {
+            HIPCHK(c->hot_list.ensure(nb * a.hot_cap * 3)); HIPCHK(c->hot_count.ensure(nb));
+            a.hot_list = c->hot_list.p; a.hot_count = c->hot_count.p;
+        }
+    } else {
+        HIPCHK(c->rec_u.ensure(n)); HIPCHK(c->rec_i.ensure(n_items > 2 * n ? n_items : 2 * n));
+        if (a.slot_stride) { HIPCHK(c->slot_info.ensure(nb * a.slot_stride)); a.slot_info = c->slot_info.p; }
+        if (a.dense_stride) {
+            c->tiles_cap = a.tiles_cap;
+            HIPCHK(c->dense_rec.ensure(nb * a.dense_stride)); HIPCHK(c->dense_n.ensure(2 * nb));
+            HIPCHK(c->tile_hdr.ensure(nb * a.tiles_cap)); HIPCHK(c->tile_ent.ensure(nb * a.tiles_cap * SML_TILE_ENT));
+            HIPCHK(c->tile_spill.ensure(nb * 3 * batch)); HIPCHK(c->spill_cnt.ensure(nb));
+            HIPCHK(hipMemsetAsync(c->spill_cnt.p, 0, nb * sizeof(int), st));
+            a.dense_rec = c->dense_rec.p; a.dense_n = c->dense_n.p; a.tile_hdr = c->tile_hdr.p; a.tile_ent = c->tile_ent.p;
+            a.tile_spill = c->tile_spill.p; a.spill_cnt = c->spill_cnt.p;
+        }
     }
-    { const char* rk = getenv("SML_PREP_RANK"); a.rank_viol = (rk && !strcmp(rk, "ballot")) ? nullptr : c->rank_viol.p; }
+    Buf<uint32_t>* hist[2] = {&c->hist_u, &c->hist_i};
+    Buf<uint32_t>* bko[2] = {&c->bko_u, &c->bko_i};
+    for (int T = 0; T < 2; ++T) {
+        SmlPrepTable& t = a.t[T];
+        HIPCHK(hist[T]->ensure(nb * t.lmul * a.tpb * t.nbk));
+        HIPCHK(bko[T]->ensure(2 * nb * t.nbk));
+        t.hist = hist[T]->p; t.bk = reinterpret_cast<uint2*>(bko[T]->p);
+        t.ent = T ? (void*)c->key_i.p : (void*)c->key_u.p; t.ent2 = T ? (void*)c->key_i2.p : (void*)c->key_u2.p;
+        t.vals = T ? c->val_i2.p : c->val_u2.p;
+        if (dups) { t.runs = T ? c->runs_i.p : c->runs_u.p; t.run_off = T ? c->off_i.p : c->off_u.p; t.run_cnt = T ? c->cnt_i.p : c->cnt_u.p; }
+        else t.runs = T ? c->rec_i.p : c->rec_u.p;
+    }
+    a.large = c->large.p; a.n_large = c->n_sel.p + 3;
+    HIPCHK(c->medium.ensure(2 * nb * (a.t[0].nbk + a.t[1].nbk) + 2));
+    a.medium = c->medium.p; a.n_medium = c->n_sel.p;
+    // stable ranks from one returning LDS atomic per occurrence -- only where this device hands them out in lane order (the
+    // start-up probe's count, which the kernels read)
+    HIPCHK(c->rank_viol.ensure(4));
+    a.rank_viol = sw.ballot ? nullptr : c->rank_viol.p;
     a.order_viol = c->rank_viol.p + 1;             // (word 1 of the probe's block: zeroed with it, never reset)
-    a.vals_ascend = (mode != 4 || plan == nullptr) ? 1 : 0;      // (source 4 with unequal batches: the driver's owner-split lists, values = slots by owner)
-    if (a.dense && !(a.t[0].nbk == 1 && a.t[1].nbk == 1)) a.dense = 0;       // (wide rows forced more buckets: per-occurrence form)
-    c->dense = a.dense != 0;
-    HIPCHK(sml_launch_prep(a, narrow ? 4 : 8, st));
+    return SML_OK;
+}
+
+// Job 3: what travels back to the host behind a preparation, into pinned blocks, each behind an event the epoch calls QUERY
+// (they never wait for one).
+int prep_readbacks(IndexSet* c, int64_t nb, bool dups, bool lists, hipStream_t st) {
     // the sorted-order invariant's violation count travels to the host behind every preparation (4 bytes); the NEXT call that
     // finds a completed copy with a non-zero count fails: a list was built wrong (sort_order_check)
     if (!c->viol_host) { HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->viol_host), 4 * sizeof(int), hipHostMallocDefault)); memset(c->viol_host, 0, 4 * sizeof(int)); }
     if (!c->viol_ready) HIPCHK(hipEventCreateWithFlags(&c->viol_ready, hipEventDisableTiming));
     HIPCHK(hipMemcpyAsync(c->viol_host, c->rank_viol.p + 1, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(c->viol_ready, st));
-    if (dups) {
-        if (!c->max_len_host) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->max_len_host), sizeof(int), hipHostMallocDefault));
-        if (!c->ready) HIPCHK(hipEventCreateWithFlags(&c->ready, hipEventDisableTiming));
-        HIPCHK(hipMemcpyAsync(c->max_len_host, c->n_sel.p + 2, sizeof(int), hipMemcpyDeviceToHost, st));
-        // the batches' run-list offsets and counts travel too (a few KB; epochs of up to 4,096 batches): an epoch prepared ahead
-        // launches its run kernels with the slices as plain arguments
-        if (mode == 0 && nb <= 4096) {
-            if (c->lists_host_nb < nb) {
-                if (c->lists_host) g_graveyard.park_host(c->lists_host);
-                c->lists_host = nullptr; c->lists_host_nb = 0;
-                HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->lists_host), (size_t)(2 * (nb + 1) + 2 * nb * SML_PREP_CNT_STRIDE) * sizeof(int), hipHostMallocDefault));
-                c->lists_host_nb = nb;
-            }
-            int* h = c->lists_host;
-            HIPCHK(hipMemcpyAsync(h, c->off_u.p, (size_t)(nb + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(h + (nb + 1), c->off_i.p, (size_t)(nb + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(h + 2 * (nb + 1), c->cnt_u.p, (size_t)nb * SML_PREP_CNT_STRIDE * sizeof(int), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(h + 2 * (nb + 1) + nb * SML_PREP_CNT_STRIDE, c->cnt_i.p, (size_t)nb * SML_PREP_CNT_STRIDE * sizeof(int), hipMemcpyDeviceToHost, st));
-            c->lists_nb = nb;
-        } else c->lists_nb = 0;
-        HIPCHK(hipEventRecord(c->ready, st));
+    if (!dups) return SML_OK;
+    // the longest run of the epoch: an epoch KNOWN to have no hot rows skips the hot-row kernels altogether
+    if (!c->max_len_host) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->max_len_host), sizeof(int), hipHostMallocDefault));
+    if (!c->ready) HIPCHK(hipEventCreateWithFlags(&c->ready, hipEventDisableTiming));
+    HIPCHK(hipMemcpyAsync(c->max_len_host, c->n_sel.p + 2, sizeof(int), hipMemcpyDeviceToHost, st));
+    // the batches' run-list offsets and counts travel too (a few KB; epochs of up to 4,096 batches): an epoch prepared ahead
+    // launches its run kernels with the slices as plain arguments
+    c->lists_nb = 0;
+    if (lists && nb <= 4096) {
+        if (c->lists_host_nb < nb) {
+            if (c->lists_host) g_graveyard.park_host(c->lists_host);
+            c->lists_host = nullptr; c->lists_host_nb = 0;
+            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->lists_host), (size_t)(2 * (nb + 1) + 2 * nb * SML_PREP_CNT_STRIDE) * sizeof(int), hipHostMallocDefault));
+            c->lists_host_nb = nb;
+        }
+        int* h = c->lists_host;
+        HIPCHK(hipMemcpyAsync(h, c->off_u.p, (size_t)(nb + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h + (nb + 1), c->off_i.p, (size_t)(nb + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h + 2 * (nb + 1), c->cnt_u.p, (size_t)nb * SML_PREP_CNT_STRIDE * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h + 2 * (nb + 1) + nb * SML_PREP_CNT_STRIDE, c->cnt_i.p, (size_t)nb * SML_PREP_CNT_STRIDE * sizeof(int), hipMemcpyDeviceToHost, st));
+        c->lists_nb = nb;
     }
-    c->n = mode >= 2 ? -1 : n; c->batch = batch; c->triples = tri; c->world = W;
+    HIPCHK(hipEventRecord(c->ready, st));
+    return SML_OK;
+}
+
+// The index lists of `n` triples (PAIRS: occurrences) from source `s` into index set `c`, by index_prep.hip: per batch the
+// occurrences sorted by row (stable), run records (dups: compact records of the duplicated runs + "row occurs once" marks; else
+// one record per sorted position), all queued on `st`.
+int prep_epoch(IndexSet* c, const PrepSource& s, int64_t n, const sml_batch_plan* plan, bool dups, bool want_dense, hipStream_t st) {
+    const int64_t nb = plan ? plan->n_batches : (n + s.batch - 1) / s.batch;
+    int rc = sort_order_check(c); if (rc) return rc;
+    c->by_hand = true; c->slot_stride = 0; c->dense_stride = 0; c->dense = false;
+    if (n == 0) { c->n = 0; c->batch = s.batch; c->triples = s.origin(); return SML_OK; }
+    if ((int64_t)s.nis * n > 0x7fffffff) return fail(SML_EINVAL, "index preparation", "too many item occurrences in one epoch");
+    const PrepSwitches sw = PrepSwitches::read();
+    SmlPrepArgs a = zeroed<SmlPrepArgs>();
+    const int ent_bytes = prep_geometry(a, s, n, nb, plan, dups, want_dense, sw);
+    if ((rc = prep_buffers(c, a, s, dups, sw, st))) return rc;
+    if (!c->rank_probed) {       // measured once per index set, on the stream, ahead of its first preparation (no host wait)
+        HIPCHK(hipMemsetAsync(c->rank_viol.p, 0, 4 * sizeof(int), st));
+        HIPCHK(sml_launch_rank_probe(c->rank_viol.p, st));
+        c->rank_probed = true;
+    }
+    HIPCHK(sml_launch_prep(a, ent_bytes, st));
+    if ((rc = prep_readbacks(c, nb, dups, s.list_readback, st))) return rc;
+    c->n = s.reusable ? n : -1; c->batch = s.batch; c->triples = s.origin(); c->world = s.world;
     return SML_OK;
 }
 
@@ -747,18 +841,23 @@ int prep_epoch(IndexSet* c, const int64_t* tri, int64_t n, int batch, int pad_ti
 #include "../../tests/csrc/prep_cub_reference.inc"
 #endif
 
-// The index lists of an epoch: per batch the occurrences sorted by row (stable), run records, "row occurs once" marks -- all by
-// index_prep.hip (prep_epoch).  SML_PREP=cub asks for the library-sort REFERENCE implementation instead: that lives under
-// tests/csrc and is compiled only into the test build of this library (tests/build_reference.py, -DSML_TEST_PREP_REFERENCE);
-// the product has no library sort and says so.
+// SML_PREP=cub asks for the library-sort REFERENCE implementation of the lists instead: that lives under tests/csrc and is
+// compiled only into the test build of this library (tests/build_reference.py, -DSML_TEST_PREP_REFERENCE); the product has no
+// library sort and says so.
+int no_prep_reference() {
+    return fail(SML_ESTATE, "index preparation", "SML_PREP=cub: the library-sort reference is test infrastructure (tests/build_reference.py), not in this library");
+}
+
+// The index lists of an epoch of one GPU's triples (prep_epoch).  bx (bare step on several GPUs): the item lists are the JOB's.
 int sort_epoch(IndexSet* c, const int64_t* tri, int64_t n, int batch, int pad_tiles, int64_t n_user, int64_t n_item,
                bool dups, hipStream_t st, const sml_batch_plan* plan = nullptr, const sml_bare_exchange* bx = nullptr, bool want_dense = false) {
-    // bx (bare step on several GPUs): the item lists are the JOB's -- every rank's 2n item occurrences
-    if (prep_by_hand()) return prep_epoch(c, tri, n, batch, pad_tiles, n_user, n_item, dups, st, plan, bx ? 1 : 0, bx, nullptr, 0, want_dense);
+    if (prep_by_hand())
+        return prep_epoch(c, bx ? PrepSource::replicated(tri, bx, n_user, n_item, batch, pad_tiles) : PrepSource::own(tri, n_user, n_item, batch, pad_tiles),
+                          n, plan, dups, want_dense, st);
 #ifdef SML_TEST_PREP_REFERENCE
     return sort_epoch_reference(c, tri, n, batch, pad_tiles, n_user, n_item, dups, st, plan, bx);
 #else
-    return fail(SML_ESTATE, "index preparation", "SML_PREP=cub: the library-sort reference is test infrastructure (tests/build_reference.py), not in this library");
+    return no_prep_reference();
 #endif
 }
 
@@ -768,14 +867,14 @@ int sort_epoch(IndexSet* c, const int64_t* tri, int64_t n, int batch, int pad_ti
 int sort_epoch_sharded(IndexSet* A, IndexSet* Bset, const int64_t* tri, int64_t n, int batch, int64_t n_user, const sml_bare_shard* sh,
                        int64_t rows_cap, hipStream_t st) {
     if (prep_by_hand()) {
-        int rc = prep_epoch(A, tri, n, batch, 0, n_user, 0, true, st, nullptr, 2, nullptr, sh, rows_cap);
-        if (!rc && sh->head_rows > 0) rc = prep_epoch(Bset, tri, n, batch, 0, n_user, 0, true, st, nullptr, 3, nullptr, sh, rows_cap);
+        int rc = prep_epoch(A, PrepSource::shard_tail(tri, sh, rows_cap, n_user, batch), n, nullptr, true, false, st);
+        if (!rc && sh->head_rows > 0) rc = prep_epoch(Bset, PrepSource::shard_head(tri, sh, n_user, batch), n, nullptr, true, false, st);
         return rc;
     }
 #ifdef SML_TEST_PREP_REFERENCE
     return sort_epoch_sharded_reference(A, Bset, tri, n, batch, n_user, sh, rows_cap, st);
 #else
-    return fail(SML_ESTATE, "index preparation", "SML_PREP=cub: the library-sort reference is test infrastructure (tests/build_reference.py), not in this library");
+    return no_prep_reference();
 #endif
 }
 
@@ -969,8 +1068,8 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
             px.n_batches = nb; px.batch_off_dev = ctx->xoff.p;
         }
         if (x_seg > 0x3fffffff) return fail(SML_EINVAL, "sml_mf_stage_epoch", "a batch's job-wide item list is too long");
-        rc = prep_epoch(&ctx->ix[1], reinterpret_cast<const int64_t*>(xchg->key_items), x_total, (int)x_seg, 0, 1, t->n_item, false, st,
-                        xchg->item_off ? &px : nullptr, 4, nullptr, nullptr, (int64_t)xchg->world * x_stride, false, xchg->val_items);
+        rc = prep_epoch(&ctx->ix[1], PrepSource::pairs(xchg->key_items, xchg->val_items, (int64_t)xchg->world * x_stride, t->n_item, (int)x_seg),
+                        x_total, xchg->item_off ? &px : nullptr, false, false, st);
     } else if (!rc && xchg && x_total > 0) {   // ... or run records over the caller's sorted keys
         HIPCHK(ctx->rec_x.ensure((size_t)x_total));
         HIPCHK(sml_launch_mark_runs(8, xchg->key_items, xchg->val_items, x_total, 32, ctx->rec_x.p, nullptr, nullptr, 0, 0, st));
