@@ -490,6 +490,59 @@ int sml_user_rank_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int6
                       const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
                       const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos,
                       void* stream);
+/* ITEM FILTER: the same six calls restricted to a subset of the catalogue, the same subset for every user.
+ * allow uint32 [sml_item_filter_words(n_item) = ceil(n_item / 32)], device memory: bit (i & 31) of word (i >> 5) is set
+ * exactly when item i may appear.  Bits at positions >= n_item of the last word are ignored, whatever they hold.
+ * allow == NULL: no filter -- the call IS the unfiltered entry point (sml_full_rank is sml_full_rank_filtered with
+ * allow = NULL, and so on).  An item is eligible when it is below n_item, not in Seen(u) and allowed (and, where the
+ * unfiltered rule says so, scores no NaN).  Each _filtered entry point takes the argument list of its unfiltered form with
+ * `allow` inserted after seen_items; each _f16 twin has the list of its fp32 form.  Scratch sizes do not depend on the
+ * filter (sml_topk_scratch_bytes, sml_user_rank_scratch_bytes).
+ * Defining identity: for any Seen and any filter A, every output of a filtered call -- rank; items, scores and their
+ * (-1, -inf) padding; above, pos and, through sml_user_metrics, hits, dcg, ap and first -- equals byte for byte the output
+ * of the unfiltered call with Seen'(u) = Seen(u) united with ([0, n_item) minus A) for every user.  In particular:
+ *   sml_full_rank_filtered   rank[r] = #{allowed i != p, not in Seen(u), S(u,i) > S(u,p)}.  p itself is never excluded: a
+ *                            positive that is not allowed still gets its rank among the allowed items.
+ *   sml_topk_items_filtered  lists hold allowed items only; fewer than k eligible items leave (-1, -inf) padding, and a
+ *                            filter that allows nothing leaves nothing else.
+ *   sml_user_rank_filtered   a held-out p that is not allowed is treated exactly like one in Seen(u): pos = -1, above =
+ *                            #{eligible i : S(u,i) > S(u,p)}, and p is no eligible item for the user's other entries.
+ *                            With nothing allowed every pos is -1 and every above 0.
+ * The fp16 statements above carry over: at d = 32 / 64 a filtered _f16 call equals the filtered fp32 call on fp32 copies
+ * of the tables bit for bit; d = 128 exists for fp16 tables only.
+ * Cost: a 32-item tile of the walk whose word allows no item below n_item is skipped by the whole wave (its item rows are
+ * not read and not scored), so a call costs what its non-empty tiles cost. */
+int sml_full_rank_filtered(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item,
+                           const int64_t* rows, int64_t n, int n_cols,
+                           const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int32_t* rank, void* stream);
+int sml_topk_items_filtered(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item,
+                            const int64_t* users, int64_t n, int k,
+                            const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow,
+                            void* scratch, int32_t* items, float* scores, void* stream);
+int sml_user_rank_filtered(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item,
+                           const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
+                           const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above,
+                           int32_t* pos, void* stream);
+int sml_full_rank_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
+                               const int64_t* rows, int64_t n, int n_cols,
+                               const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int32_t* rank, void* stream);
+int sml_topk_items_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
+                                const int64_t* users, int64_t n, int k,
+                                const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow,
+                                void* scratch, int32_t* items, float* scores, void* stream);
+int sml_user_rank_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
+                               const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
+                               const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch,
+                               int32_t* above, int32_t* pos, void* stream);
+/* Words of an item filter over n_item items: ceil(n_item / 32); < 0: bad argument (0 < n_item < 2^31). */
+int64_t sml_item_filter_words(int64_t n_item);
+/* Build a filter on the device: words [sml_item_filter_words(n_item)] allows exactly the items of ids int32 [n_ids]
+ * (device memory; duplicates allowed, n_ids = 0 allowed) or, with invert = 1, every item of [0, n_item) EXCEPT them (a
+ * deny-list).  The tail bits of the last word are written 0.  Bits are set with atomic OR / AND: the same words whatever
+ * the order.  ids must lie in [0, n_item); on the device they are trusted like every other index (a host-side caller
+ * checks them: HipEngine.item_filter_from_ids does). */
+int sml_item_filter_from_ids(sml_ctx* ctx, const int32_t* ids, int64_t n_ids, int64_t n_item, int invert, uint32_t* words,
+                             void* stream);
 /* Per-user metrics from pos (as sml_user_rank writes it; any value < 0 is never a hit) over the ranges of pos_off,
  * n < 2^31.  ks: HOST int32 [n_k], 1 <= n_k <= 8, every K >= 1.  For user x with m = |T(x)| and each K (outputs [n, n_k], row-major):
  *   hits = #{p : 0 <= pos(p) < K};  dcg = sum over hits of 1/log2(pos + 2), fp32, summed in ascending pos;

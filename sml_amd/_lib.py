@@ -116,6 +116,20 @@ SIGNATURES = {
                                           c_void, c_void, c_void, c_void]),
     "sml_user_rank_f16": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64,
                                          c_void, c_void, c_void, c_void, c_void, c_void]),
+    "sml_full_rank_filtered": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
+                                              c_void, c_void, c_void]),
+    "sml_topk_items_filtered": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
+                                               c_void, c_void, c_void, c_void, c_void]),
+    "sml_user_rank_filtered": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64,
+                                              c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    "sml_full_rank_filtered_f16": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void,
+                                                  c_void, c_void, c_void, c_void]),
+    "sml_topk_items_filtered_f16": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void,
+                                                   c_void, c_void, c_void, c_void, c_void, c_void]),
+    "sml_user_rank_filtered_f16": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void,
+                                                  ctypes.c_int64, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    "sml_item_filter_words": (ctypes.c_int64, [ctypes.c_int64]),
+    "sml_item_filter_from_ids": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_void, c_void]),
     "sml_user_metrics": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,
                                         c_void]),
     "sml_stream_create_cu_range": (ctypes.c_int, [ctypes.POINTER(c_void), ctypes.c_int, ctypes.c_int, ctypes.c_int]),

@@ -1794,27 +1794,41 @@ static bool retrieval_args_ok(sml_ctx* ctx, int elem_bytes, int64_t n_item, cons
     return ctx && sml_retrieval_supports(ctx->d, elem_bytes) && n_item > 0 && n_item < ((int64_t)1 << 31) && (!seen_off) == (!seen_items);
 }
 
-// every table-reading entry point exists twice over one body: `what` names the caller, elem_bytes its tables
+// every table-reading entry point exists four times over one body: `what` names the caller, elem_bytes its tables, allow
+// the item filter of the _filtered forms (NULL: none, which is what the unfiltered entry points pass)
 static int full_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
                           const int64_t* rows, int64_t n, int n_cols, const int64_t* seen_off, const int32_t* seen_items,
-                          int32_t* rank, void* stream) {
+                          const uint32_t* allow, int32_t* rank, void* stream) {
     if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || n_cols < 2 || n < 0)
         return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, n_cols >= 2, seen_off and seen_items both or neither)");
     if (n == 0) return SML_OK;
     if (!w_user || !w_item || !rows || !rank) return fail(SML_EINVAL, what, "null argument");
     DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
-    PROFILED(PC_MISC, HIPCHK(sml_launch_full_rank(ctx->d, elem_bytes, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, st)));
+    PROFILED(PC_MISC, HIPCHK(sml_launch_full_rank(ctx->d, elem_bytes, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, rank, st)));
     return SML_OK;
 }
 
 int sml_full_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* rows, int64_t n,
                   int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, void* stream) {
-    return full_rank_impl("sml_full_rank", 4, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, stream);
+    return full_rank_impl("sml_full_rank", 4, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, nullptr, rank, stream);
 }
 
 int sml_full_rank_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* rows, int64_t n,
                       int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, void* stream) {
-    return full_rank_impl("sml_full_rank_f16", 2, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, rank, stream);
+    return full_rank_impl("sml_full_rank_f16", 2, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, nullptr, rank, stream);
+}
+
+int sml_full_rank_filtered(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* rows, int64_t n,
+                           int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int32_t* rank,
+                           void* stream) {
+    return full_rank_impl("sml_full_rank_filtered", 4, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, rank, stream);
+}
+
+int sml_full_rank_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* rows, int64_t n,
+                               int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int32_t* rank,
+                               void* stream) {
+    return full_rank_impl("sml_full_rank_filtered_f16", 2, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, rank,
+                          stream);
 }
 
 int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item) {
@@ -1824,24 +1838,40 @@ int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item) {
 
 static int topk_items_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
                            const int64_t* users, int64_t n, int k, const int64_t* seen_off, const int32_t* seen_items,
-                           void* scratch, int32_t* items, float* scores, void* stream) {
+                           const uint32_t* allow, void* scratch, int32_t* items, float* scores, void* stream) {
     if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || k < 1 || k > 128 || n < 0)
         return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 1 <= k <= 128, 0 < n_item < 2^31, seen_off and seen_items both or neither)");
     if (n == 0) return SML_OK;
     if (!w_user || !w_item || !users || !scratch || !items || !scores) return fail(SML_EINVAL, what, "null argument");
     DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
-    PROFILED(PC_MISC, HIPCHK(sml_launch_topk(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, st)));
+    PROFILED(PC_MISC, HIPCHK(sml_launch_topk(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, scratch, items, scores, st)));
     return SML_OK;
 }
 
 int sml_topk_items(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
                    const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores, void* stream) {
-    return topk_items_impl("sml_topk_items", 4, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, stream);
+    return topk_items_impl("sml_topk_items", 4, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, nullptr, scratch, items, scores,
+                           stream);
 }
 
 int sml_topk_items_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
                        const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores, void* stream) {
-    return topk_items_impl("sml_topk_items_f16", 2, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, scratch, items, scores, stream);
+    return topk_items_impl("sml_topk_items_f16", 2, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, nullptr, scratch, items,
+                           scores, stream);
+}
+
+int sml_topk_items_filtered(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
+                            const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* items,
+                            float* scores, void* stream) {
+    return topk_items_impl("sml_topk_items_filtered", 4, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, scratch, items,
+                           scores, stream);
+}
+
+int sml_topk_items_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
+                                const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* items,
+                                float* scores, void* stream) {
+    return topk_items_impl("sml_topk_items_filtered_f16", 2, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, scratch,
+                           items, scores, stream);
 }
 
 int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int64_t n_item) {
@@ -1853,8 +1883,8 @@ int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int6
 
 static int user_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
                           const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
-                          const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos,
-                          void* stream) {
+                          const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above,
+                          int32_t* pos, void* stream) {
     if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || n < 0 || n >= ((int64_t)1 << 31) || n_pos < 0 ||
         n_pos >= ((int64_t)1 << 31))
         return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, 0 <= n, n_pos < 2^31, seen_off and seen_items both or neither)");
@@ -1863,7 +1893,7 @@ static int user_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const 
         return fail(SML_EINVAL, what, "null argument");
     DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
     PROFILED(PC_MISC, HIPCHK(sml_launch_user_rank(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
-                                               seen_items, scratch, above, pos, st)));
+                                               seen_items, allow, scratch, above, pos, st)));
     return SML_OK;
 }
 
@@ -1871,14 +1901,43 @@ int sml_user_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_
                   const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                   const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, void* stream) {
     return user_rank_impl("sml_user_rank", 4, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off, seen_items,
-                          scratch, above, pos, stream);
+                          nullptr, scratch, above, pos, stream);
 }
 
 int sml_user_rank_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,
                       const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                       const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, void* stream) {
     return user_rank_impl("sml_user_rank_f16", 2, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
-                          seen_items, scratch, above, pos, stream);
+                          seen_items, nullptr, scratch, above, pos, stream);
+}
+
+int sml_user_rank_filtered(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n,
+                           const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
+                           const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above, int32_t* pos, void* stream) {
+    return user_rank_impl("sml_user_rank_filtered", 4, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
+                          seen_items, allow, scratch, above, pos, stream);
+}
+
+int sml_user_rank_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,
+                               const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
+                               const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above, int32_t* pos,
+                               void* stream) {
+    return user_rank_impl("sml_user_rank_filtered_f16", 2, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
+                          seen_items, allow, scratch, above, pos, stream);
+}
+
+int64_t sml_item_filter_words(int64_t n_item) {
+    if (n_item <= 0 || n_item >= ((int64_t)1 << 31)) return fail(SML_EINVAL, "sml_item_filter_words", "bad argument (0 < n_item < 2^31)");
+    return (n_item + 31) / 32;
+}
+
+int sml_item_filter_from_ids(sml_ctx* ctx, const int32_t* ids, int64_t n_ids, int64_t n_item, int invert, uint32_t* words, void* stream) {
+    if (!ctx || n_ids < 0 || n_ids >= ((int64_t)1 << 31) || n_item <= 0 || n_item >= ((int64_t)1 << 31) || (invert != 0 && invert != 1))
+        return fail(SML_EINVAL, "sml_item_filter_from_ids", "bad argument (0 <= n_ids < 2^31, 0 < n_item < 2^31, invert 0 or 1)");
+    if (!words || (n_ids && !ids)) return fail(SML_EINVAL, "sml_item_filter_from_ids", "null argument");
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_item_filter(ids, n_ids, n_item, invert, words, st)));
+    return SML_OK;
 }
 
 int sml_user_metrics(sml_ctx* ctx, const int32_t* pos, const int64_t* pos_off, int64_t n, const int32_t* ks, int n_k,

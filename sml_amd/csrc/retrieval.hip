@@ -49,6 +49,13 @@
 //   k_ur_finish      one workgroup per user: prefix sums over the bins give pos / above in sorted order, scattered back.
 //   k_ur_metrics     one workgroup per user: hit counts and `first` by LDS atomics, then dcg / ap summed by one thread
 //                    in ascending pos, read from a bitmap of the hit positions.
+//
+// Item filter (the sml_*_filtered entry points): a catalogue bitmap, one 32-bit word per tile, bit b of word t <=> item
+// 32 t + b may appear.  The filter is per call, not per user, so a tile's word is wave-uniform: the walk reads it with a
+// scalar load, ANDs it into the tile's eligibility word, and skips a tile whose word is 0 for the whole wave -- no item
+// rows, no MFMAs, no callback; the double buffer prefetches the next NON-EMPTY tile of the slice.  The filtered kernels
+// are instantiations of their own (walk_slice<.., true>, k_x_f<D> / k_x_f_h<D>); the unfiltered ones compile to what
+// they were without it.  k_filter_fill / k_filter_from_ids build a bitmap from a list of item ids.
 #include <climits>
 #include <cmath>
 #include <type_traits>
@@ -153,6 +160,13 @@ struct SeenCursor {
         cur = lower_bound(off[u], end, [&](int64_t m) { return it[m] < start; });
         nxt = cur < end ? it[cur] : LLONG_MAX;
     }
+    // the walk jumped over tiles: drop the Seen items below base (word() assumes that none is left)
+    __device__ void skip_to(long long base) {
+        if (nxt >= base) return;
+        const int32_t* it = items;
+        cur = lower_bound(cur + 1, end, [&](int64_t m) { return it[m] < base; });
+        nxt = cur < end ? it[cur] : LLONG_MAX;
+    }
     // bit b set <=> item base + b is in Seen; the cursor moves past the tile
     __device__ unsigned word(long long base) {
         unsigned w = 0;
@@ -186,51 +200,79 @@ __device__ __forceinline__ LanePos lane_pos(int slices, int waves, int64_t n) {
     return lp;
 }
 
+// bit i set <=> item 32 t + i exists (< n_item); t < n_tiles, so at least bit 0 is set
+__device__ __forceinline__ unsigned tile_items(int64_t t, int64_t n_item) {
+    const int64_t left = n_item - t * RT;
+    return left < RT ? (1u << left) - 1u : ~0u;
+}
+
 // The catalogue walk of one wave: user u's scores against every 32-item tile of the lane's slice, next tile's item rows
 // in flight under the current tile's MFMAs.  tile(acc, base, elig) runs once per tile: acc[q] = S(u, base + row_of(q, h)),
-// bit q of elig set <=> that item exists (< n_item) and is not in Seen(u).  An empty slice loads nothing and calls nothing.
-template <int D, class T, class Tile>
+// bit q of elig set <=> that item exists (< n_item), is not in Seen(u) and, with a filter, is allowed.  An empty slice
+// loads nothing and calls nothing.
+// F: `allow` holds one word per tile (bits past n_item are masked off here).  t, the words and the scan are wave-uniform
+// (the slice comes from blockIdx), so the words travel through scalar loads and SGPRs.  A tile whose word is 0 is never
+// visited: the scan for the next non-empty tile runs before the prefetch, and its first word -- tile t + 1's -- was
+// requested one tile earlier, together with that tile's item rows (`pre`).  A slice without a non-empty tile returns at once.
+template <int D, class T, bool F, class Tile>
 __device__ __forceinline__ void walk_slice(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item, int64_t u,
                                            const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                           const LanePos& lp, int slice_tiles, Tile&& tile) {
+                                           const uint32_t* __restrict__ allow, const LanePos& lp, int slice_tiles, Tile&& tile) {
     const int64_t n_tiles = (n_item + RT - 1) / RT;
     const int64_t t0 = (int64_t)lp.slice * slice_tiles;
     const int64_t t1 = t0 + slice_tiles < n_tiles ? t0 + slice_tiles : n_tiles;
     if (t0 >= t1) return;
+    int64_t t = t0;
+    unsigned w = 0, pre = 0;                             // F: the current tile's word; the raw word of tile t + 1
+    if constexpr (F) {
+        while (t < t1 && !(w = allow[t] & tile_items(t, n_item))) ++t;
+        if (t >= t1) return;
+        if (t + 1 < t1) pre = allow[t + 1];
+    }
     HalfRow<D, T> b;
     b.load(wu + u * D, lp.h);
     SeenCursor sc;
-    sc.init(seen_off, seen_items, u, t0 * RT);
+    sc.init(seen_off, seen_items, u, t * RT);
     HalfRow<D, T> a, an;
-    int64_t ia = t0 * RT + lp.j;
+    int64_t ia = t * RT + lp.j;
     a.load(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h);
-    for (int64_t t = t0; t < t1; ++t) {
-        if (t + 1 < t1) {
-            ia = (t + 1) * RT + lp.j;
+    for (int64_t tn; t < t1; t = tn) {
+        tn = t + 1;
+        unsigned wn = pre;
+        if constexpr (F) {
+            while (tn < t1 && !(wn &= tile_items(tn, n_item)))
+                if (++tn < t1) wn = allow[tn];
+            if (tn + 1 < t1) pre = allow[tn + 1];
+        }
+        if (tn < t1) {
+            ia = tn * RT + lp.j;
             an.load(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h);
         }
         b.keep_packed();
         const f32x16 acc = tile_scores<D, T>(a, b);
         const int64_t base = t * RT;
-        const int64_t left = n_item - base;              // >= 1; bit i of `real`: item base + i exists and is not in Seen
-        const unsigned real = ~sc.word(base) & (left < RT ? (1u << left) - 1u : ~0u);
+        if constexpr (F) sc.skip_to(base);
+        // bit i of `real`: item base + i exists, is not in Seen (and is allowed)
+        const unsigned real = ~sc.word(base) & (F ? w : tile_items(t, n_item));
         tile(acc, base, lane_rows(real, lp.h));
         a = an;
+        w = wn;
     }
 }
 
 // The kernels below are bodies over the element type T; each has two __global__ entry points, k_x<D> on fp32 tables and
 // k_x_h<D> on fp16 tables.
-template <int D, class T>
+template <int D, bool F = false, class T>
 __device__ __forceinline__ void full_rank_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                                const int64_t* __restrict__ rows, int64_t n, int n_cols,
                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                               int slices, int slice_tiles, int32_t* __restrict__ rank) {
+                                               int slices, int slice_tiles, int32_t* __restrict__ rank,
+                                               const uint32_t* __restrict__ allow = nullptr) {
     const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
     const int64_t u = rows[lp.rc * n_cols], p = rows[lp.rc * n_cols + 1];
     const float thr = score_chain<D>(wu + u * D, wi + p * D);
     int cnt = 0;
-    walk_slice<D>(wu, wi, n_item, u, seen_off, seen_items, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
+    walk_slice<D, T, F>(wu, wi, n_item, u, seen_off, seen_items, allow, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) cnt += (acc[q] > thr) & ((elig >> q) & 1u) & (base + row_of(q, lp.h) != p);
     });
@@ -252,6 +294,25 @@ __global__ __launch_bounds__(256) void k_full_rank_h(const _Float16* __restrict_
                                                      const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
                                                      int slices, int slice_tiles, int32_t* __restrict__ rank) {
     full_rank_body<D>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank);
+}
+
+// the filtered forms: the same bodies over walk_slice<.., true>; `allow` is the item filter, one word per tile
+template <int D>
+__global__ __launch_bounds__(256) void k_full_rank_f(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                     const int64_t* __restrict__ rows, int64_t n, int n_cols,
+                                                     const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                     const uint32_t* __restrict__ allow, int slices, int slice_tiles,
+                                                     int32_t* __restrict__ rank) {
+    full_rank_body<D, true>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank, allow);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_full_rank_f_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
+                                                       const int64_t* __restrict__ rows, int64_t n, int n_cols,
+                                                       const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                       const uint32_t* __restrict__ allow, int slices, int slice_tiles,
+                                                       int32_t* __restrict__ rank) {
+    full_rank_body<D, true>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank, allow);
 }
 
 // insert (s, i) into user j's list (k slots, column j of [k][32] arrays); cnt = live entries
@@ -276,12 +337,13 @@ __device__ __forceinline__ void list_insert(float* ls, int* li, int k, int j, in
 }
 
 // candidates of user x, slice s: cand_s / cand_i [(x * slices + s) * k + q], cand_n [x * slices + s]
-template <int D, class T>
+template <int D, bool F = false, class T>
 __device__ __forceinline__ void topk_slice_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                                 const int64_t* __restrict__ users, int64_t n, int k,
                                                 const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
                                                 int slices, int slice_tiles, float* __restrict__ cand_s,
-                                                int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n) {
+                                                int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n,
+                                                const uint32_t* __restrict__ allow = nullptr) {
     extern __shared__ float lds[];
     const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
     const int h = lp.h, j = lp.j;
@@ -291,7 +353,7 @@ __device__ __forceinline__ void topk_slice_body(const T* __restrict__ wu, const 
     int cnt = 0;                          // live entries of user j's list (both lane halves keep it)
     float thr_s = -INFINITY;              // register copy of the K-th entry: lags the list, never ahead of it
     int thr_i = INT_MAX;
-    walk_slice<D>(wu, wi, n_item, u, seen_off, seen_items, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
+    walk_slice<D, T, F>(wu, wi, n_item, u, seen_off, seen_items, allow, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
         unsigned pass = 0;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
@@ -342,6 +404,26 @@ __global__ __launch_bounds__(256) void k_topk_slice_h(const _Float16* __restrict
                                                       int slices, int slice_tiles, float* __restrict__ cand_s,
                                                       int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n) {
     topk_slice_body<D>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_topk_slice_f(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                      const int64_t* __restrict__ users, int64_t n, int k,
+                                                      const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                      const uint32_t* __restrict__ allow, int slices, int slice_tiles,
+                                                      float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
+                                                      int32_t* __restrict__ cand_n) {
+    topk_slice_body<D, true>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n, allow);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_topk_slice_f_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
+                                                        const int64_t* __restrict__ users, int64_t n, int k,
+                                                        const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                        const uint32_t* __restrict__ allow, int slices, int slice_tiles,
+                                                        float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
+                                                        int32_t* __restrict__ cand_n) {
+    topk_slice_body<D, true>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n, allow);
 }
 
 // one thread per (user, slice, slot): the candidate's final position is its slot plus the number of strictly better
@@ -457,14 +539,15 @@ __device__ __forceinline__ int64_t ur_segment(const int64_t* __restrict__ off, i
     return lo;
 }
 
-template <int D, class T>
+// in_seen[e] = 1: the held-out item is not eligible by id -- in Seen(u) or, with a filter (F), not allowed
+template <int D, bool F = false, class T>
 __device__ __forceinline__ void ur_thresholds_body(const T* __restrict__ wu, const T* __restrict__ wi,
                                                    const int64_t* __restrict__ users, int64_t n,
                                                    const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
                                                    int64_t n_pos, const int64_t* __restrict__ seen_off,
                                                    const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
                                                    float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
-                                                   int32_t* __restrict__ in_seen) {
+                                                   int32_t* __restrict__ in_seen, const uint32_t* __restrict__ allow = nullptr) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_pos) return;
     const int64_t x = ur_segment(pos_off, n, e);
@@ -476,6 +559,7 @@ __device__ __forceinline__ void ur_thresholds_body(const T* __restrict__ wu, con
         const int64_t lo = lower_bound(seen_off[u], end, [&](int64_t m) { return seen_items[m] < p; });
         sn = lo < end && seen_items[lo] == p;
     }
+    if constexpr (F) sn |= !((allow[p >> 5] >> (p & 31)) & 1u);
     seg[e] = (int32_t)x;
     ks[e] = score_chain<D>(wu + u * D, wi + (int64_t)p * D);
     ki[e] = p;
@@ -503,6 +587,28 @@ __global__ __launch_bounds__(256) void k_ur_thresholds_h(const _Float16* __restr
                                                          float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
                                                          int32_t* __restrict__ in_seen) {
     ur_thresholds_body<D>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_ur_thresholds_f(const float* __restrict__ wu, const float* __restrict__ wi,
+                                                         const int64_t* __restrict__ users, int64_t n,
+                                                         const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
+                                                         int64_t n_pos, const int64_t* __restrict__ seen_off,
+                                                         const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
+                                                         int32_t* __restrict__ seg, float* __restrict__ ks, int32_t* __restrict__ ki,
+                                                         int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
+    ur_thresholds_body<D, true>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen, allow);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_ur_thresholds_f_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
+                                                           const int64_t* __restrict__ users, int64_t n,
+                                                           const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
+                                                           int64_t n_pos, const int64_t* __restrict__ seen_off,
+                                                           const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
+                                                           int32_t* __restrict__ seg, float* __restrict__ ks, int32_t* __restrict__ ki,
+                                                           int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
+    ur_thresholds_body<D, true>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen, allow);
 }
 
 // runs [a0, a0 + w) and [a0 + w, a0 + 2w) of every user's range -> one sorted run
@@ -549,13 +655,13 @@ __device__ __forceinline__ void ur_place(const float* ts, const int32_t* ti, int
 
 // ss / si: every user's thresholds and ids in ur_less order.  At sorted place b of user x, bin_p (zeroed) receives the
 // number of eligible items whose pos bound is b, and bin_d (zeroed) what turns those counts into the above bounds'
-template <int D, class T>
+template <int D, bool F = false, class T>
 __device__ __forceinline__ void ur_count_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                               const int64_t* __restrict__ users, int64_t n, const int64_t* __restrict__ pos_off,
                                               const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
                                               int slices, int slice_tiles, const float* __restrict__ ss,
                                               const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
-                                              int32_t* __restrict__ bin_d) {
+                                              int32_t* __restrict__ bin_d, const uint32_t* __restrict__ allow = nullptr) {
     __shared__ float l_s[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_i[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_p[kUrWaves][kUrWin * RT];
@@ -579,7 +685,7 @@ __device__ __forceinline__ void ur_count_body(const T* __restrict__ wu, const T*
     const float t0s = mv ? ss[lo] : 0.0f, tws = mv ? ss[lo + mv - 1] : 0.0f;
     const int t0i = mv ? si[lo] : 0, twi = mv ? si[lo + mv - 1] : 0;
     int c0 = 0, d0 = 0;
-    walk_slice<D>(wu, wi, n_item, u, seen_off, seen_items, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
+    walk_slice<D, T, F>(wu, wi, n_item, u, seen_off, seen_items, allow, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
         unsigned live = 0;                 // NaN scores fail `better`; an item not better than the worst threshold is in no bin
         if (mv) {
 #pragma unroll
@@ -636,6 +742,46 @@ __global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_h(const _Float16* __
                                                               const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
                                                               int32_t* __restrict__ bin_d) {
     ur_count_body<D>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d);
+}
+
+template <int D>
+__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_f(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                              const int64_t* __restrict__ users, int64_t n,
+                                                              const int64_t* __restrict__ pos_off,
+                                                              const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                              const uint32_t* __restrict__ allow, int slices, int slice_tiles,
+                                                              const float* __restrict__ ss, const int32_t* __restrict__ si,
+                                                              int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
+    ur_count_body<D, true>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d, allow);
+}
+
+template <int D>
+__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_f_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
+                                                                int64_t n_item, const int64_t* __restrict__ users, int64_t n,
+                                                                const int64_t* __restrict__ pos_off,
+                                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                                const uint32_t* __restrict__ allow, int slices, int slice_tiles,
+                                                                const float* __restrict__ ss, const int32_t* __restrict__ si,
+                                                                int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
+    ur_count_body<D, true>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d, allow);
+}
+
+// ---- item filter from a list of ids -----------------------------------------------------------------------------------
+
+// every word allows nothing (invert = 0) or every item below n_item (invert = 1: the tail bits of the last word stay 0)
+__global__ __launch_bounds__(256) void k_filter_fill(uint32_t* __restrict__ words, int64_t n_words, int64_t n_item, int invert) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n_words) words[t] = invert ? tile_items(t, n_item) : 0u;
+}
+
+// one thread per id: set (or, inverted, clear) its bit.  Atomic OR / AND commute, so duplicates and order do not matter
+__global__ __launch_bounds__(256) void k_filter_from_ids(const int32_t* __restrict__ ids, int64_t n_ids, int invert,
+                                                         uint32_t* __restrict__ words) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_ids) return;
+    const int32_t i = ids[e];
+    if (invert) atomicAnd(words + (i >> 5), ~(1u << (i & 31)));
+    else atomicOr(words + (i >> 5), 1u << (i & 31));
 }
 
 // inclusive prefix sum of v over the workgroup (kUrBlock threads); *total = the sum of all
@@ -760,14 +906,19 @@ bool sml_retrieval_supports(int d, int elem_bytes) {
 }
 
 hipError_t sml_launch_full_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* rows, int64_t n,
-                                int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, hipStream_t st) {
+                                int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int32_t* rank,
+                                hipStream_t st) {
     hipError_t e = hipMemsetAsync(rank, 0, n * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
     const SliceGrid g = rank_grid(n, kRankWaves, n_item);
     const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kRankWaves);
     if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        LAUNCH_TYPED(k_full_rank, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, rows, n, n_cols, seen_off, seen_items,
-                     g.slices, g.slice_tiles, rank);
+        if (allow)
+            LAUNCH_TYPED(k_full_rank_f, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, rows, n, n_cols, seen_off, seen_items,
+                         allow, g.slices, g.slice_tiles, rank);
+        else
+            LAUNCH_TYPED(k_full_rank, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, rows, n, n_cols, seen_off, seen_items,
+                         g.slices, g.slice_tiles, rank);
     }))
         return hipErrorInvalidValue;
     return hipGetLastError();
@@ -779,8 +930,8 @@ int64_t sml_topk_scratch_size(int64_t n, int k, int64_t n_item) {
 }
 
 hipError_t sml_launch_topk(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
-                           int k, const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores,
-                           hipStream_t st) {
+                           int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* items,
+                           float* scores, hipStream_t st) {
     const SliceGrid g = topk_grid(n, k, n_item);
     const int slices = g.slices, waves = topk_waves(k);
     float* cs = static_cast<float*>(scratch);
@@ -789,8 +940,12 @@ hipError_t sml_launch_topk(int d, int elem_bytes, const void* wu, const void* wi
     const dim3 grid((unsigned)(g.groups * slices)), block(64 * waves);
     const size_t lds = (size_t)waves * 2 * k * RT * 4;
     if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        LAUNCH_TYPED(k_topk_slice, decltype(dd)::value, tu, grid, block, lds, st, tu, ti, n_item, users, n, k, seen_off, seen_items,
-                     slices, g.slice_tiles, cs, ci, cn);
+        if (allow)
+            LAUNCH_TYPED(k_topk_slice_f, decltype(dd)::value, tu, grid, block, lds, st, tu, ti, n_item, users, n, k, seen_off, seen_items,
+                         allow, slices, g.slice_tiles, cs, ci, cn);
+        else
+            LAUNCH_TYPED(k_topk_slice, decltype(dd)::value, tu, grid, block, lds, st, tu, ti, n_item, users, n, k, seen_off, seen_items,
+                         slices, g.slice_tiles, cs, ci, cn);
     }))
         return hipErrorInvalidValue;
     hipError_t e = hipGetLastError();
@@ -807,7 +962,8 @@ int64_t sml_user_rank_scratch_size(int64_t n_pos) { return 10 * ur_piece(n_pos);
 
 hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
                                 const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
-                                const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, hipStream_t st) {
+                                const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above, int32_t* pos,
+                                hipStream_t st) {
     char* base = static_cast<char*>(scratch);
     const int64_t pc = ur_piece(n_pos);
     int32_t* seg = reinterpret_cast<int32_t*>(base);
@@ -821,8 +977,12 @@ hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const voi
     if (e != hipSuccess) return e;
     const dim3 eg((unsigned)((n_pos + 255) / 256)), eb(256);
     if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        LAUNCH_TYPED(k_ur_thresholds, decltype(dd)::value, tu, eg, eb, 0, st, tu, ti, users, n, pos_off, pos_items, n_pos, seen_off,
-                     seen_items, seg, ks[0], ki[0], kx[0], in_seen);
+        if (allow)
+            LAUNCH_TYPED(k_ur_thresholds_f, decltype(dd)::value, tu, eg, eb, 0, st, tu, ti, users, n, pos_off, pos_items, n_pos, seen_off,
+                         seen_items, allow, seg, ks[0], ki[0], kx[0], in_seen);
+        else
+            LAUNCH_TYPED(k_ur_thresholds, decltype(dd)::value, tu, eg, eb, 0, st, tu, ti, users, n, pos_off, pos_items, n_pos, seen_off,
+                         seen_items, seg, ks[0], ki[0], kx[0], in_seen);
     }))
         return hipErrorInvalidValue;
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -835,8 +995,12 @@ hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const voi
     const SliceGrid g = rank_grid(n, kUrWaves, n_item);
     const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kUrWaves);
     if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        LAUNCH_TYPED(k_ur_count, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, users, n, pos_off, seen_off, seen_items,
-                     g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
+        if (allow)
+            LAUNCH_TYPED(k_ur_count_f, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, users, n, pos_off, seen_off, seen_items,
+                         allow, g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
+        else
+            LAUNCH_TYPED(k_ur_count, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, users, n, pos_off, seen_off, seen_items,
+                         g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
     }))
         return hipErrorInvalidValue;
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -849,5 +1013,14 @@ hipError_t sml_launch_user_metrics(const int32_t* pos, const int64_t* pos_off, i
     UrKs k = {};
     for (int q = 0; q < n_k; ++q) k.k[q] = ks[q];
     k_ur_metrics<<<dim3((unsigned)n), dim3(kUrBlock), 0, st>>>(pos, pos_off, k, n_k, hits, dcg, ap, first);
+    return hipGetLastError();
+}
+
+hipError_t sml_launch_item_filter(const int32_t* ids, int64_t n_ids, int64_t n_item, int invert, uint32_t* words, hipStream_t st) {
+    const int64_t n_words = (n_item + RT - 1) / RT;
+    k_filter_fill<<<dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st>>>(words, n_words, n_item, invert);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || n_ids == 0) return e;
+    k_filter_from_ids<<<dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, st>>>(ids, n_ids, invert, words);
     return hipGetLastError();
 }

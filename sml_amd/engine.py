@@ -711,6 +711,37 @@ class HipEngine(object):
             items = torch.zeros(1, device=self.device, dtype=torch.int32)
         return off, items
 
+    def _allow(self, allow, n_item):
+        """allow=: None, or the item filter of sml_*_filtered as an int32 word tensor [ceil(n_item / 32)] on this device
+        (sml_amd.retrieval.as_filter makes one from an ItemFilter or a bool mask)."""
+        if allow is None:
+            return None
+        if not torch.is_tensor(allow) or allow.dtype != torch.int32:
+            from .retrieval import as_filter
+            return as_filter(allow, n_item, self.device)
+        if allow.device != self.device or allow.dim() != 1 or not allow.is_contiguous() or allow.shape[0] != (n_item + 31) // 32:
+            raise ValueError("expected a contiguous int32 item filter [%d] on %s, got %s on %s"
+                             % ((n_item + 31) // 32, self.device, tuple(allow.shape), allow.device))
+        return allow
+
+    def item_filter_from_ids(self, ids, n_item, invert=False):
+        """The item filter (int32 words [ceil(n_item / 32)], tail bits 0) that allows exactly `ids` -- or, with invert,
+        everything except `ids` -- built on the device (sml_item_filter_from_ids).  Duplicates are allowed; ids outside
+        [0, n_item) raise."""
+        n_item = int(n_item)
+        n_words = int(self.lib.sml_item_filter_words(n_item))
+        if n_words < 0:
+            check(-1, "sml_item_filter_words")
+        if not torch.is_tensor(ids):
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if len(ids) and (int(ids.min()) < 0 or int(ids.max()) >= n_item):        # checked before the ids narrow to int32
+            raise ValueError("item id out of range (n_item=%d)" % n_item)
+        ids = self._dev(ids, torch.int32).reshape(-1)
+        words = torch.empty(n_words, device=self.device, dtype=torch.int32)
+        check(self.lib.sml_item_filter_from_ids(self._ctx, _ptr(ids), ids.numel(), n_item, int(bool(invert)), _ptr(words),
+                                                self._stream()), "sml_item_filter_from_ids")
+        return words
+
     def _retrieval_tables(self, user_tab, item_tab):
         """(user table, item table, entry-point suffix): both fp32 (the sml_* entry points) or both fp16 (sml_*_f16; the
         rows are read as packed halves, no fp32 copy).  Which widths each element type has is the library's answer."""
@@ -722,34 +753,41 @@ class HipEngine(object):
                                  % (self.d, self.device, tuple(t.shape), t.device))
         return user_tab, item_tab, "_f16" if user_tab.dtype == torch.float16 else ""
 
-    def full_rank(self, user_tab, item_tab, rows, seen=None):
+    def full_rank(self, user_tab, item_tab, rows, seen=None, allow=None):
         """int32 [n]: per row (u, p, ...) the number of items i != p, not in Seen(u), scoring strictly above p over the
         WHOLE item table (include/sml_hip.h, sml_full_rank / sml_full_rank_f16: fp32 or fp16 tables).
-        seen = (seen_off int64 [n_user + 1], seen_items int32)."""
+        seen = (seen_off int64 [n_user + 1], seen_items int32).  allow: an item filter (_allow); the count then runs over
+        the allowed items only (sml_full_rank_filtered)."""
         wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
-        call = getattr(self.lib, "sml_full_rank" + sfx)
+        allow = self._allow(allow, wi.shape[0])
+        name = "sml_full_rank" + ("" if allow is None else "_filtered") + sfx
+        call = getattr(self.lib, name)
+        flt = () if allow is None else (_ptr(allow),)
         rows = self._dev(rows, torch.int64)
         n, c = rows.shape
         rank = torch.empty(n, device=self.device, dtype=torch.int32)
         if n == 0:
             return rank
         off, items = self._seen(seen)
-        check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(rows), n, c, _ptr(off), _ptr(items), _ptr(rank), self._stream()),
-              "sml_full_rank" + sfx)
+        check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(rows), n, c, _ptr(off), _ptr(items), *flt, _ptr(rank),
+                   self._stream()), name)
         return rank
 
-    def topk_items(self, user_tab, item_tab, users, k, seen=None):
+    def topk_items(self, user_tab, item_tab, users, k, seen=None, allow=None):
         """(int64 items [n, k], float32 scores [n, k]): each user's k best items not in Seen(u), score descending then id
-        ascending; missing slots are (-1, -inf) (include/sml_hip.h, sml_topk_items / sml_topk_items_f16: fp32 or fp16 tables)."""
+        ascending; missing slots are (-1, -inf) (include/sml_hip.h, sml_topk_items / sml_topk_items_f16: fp32 or fp16 tables).
+        allow: an item filter (_allow); only allowed items enter the lists (sml_topk_items_filtered)."""
         wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
-        name = "sml_topk_items" + sfx
+        allow = self._allow(allow, wi.shape[0])
+        name = "sml_topk_items" + ("" if allow is None else "_filtered") + sfx
         call = getattr(self.lib, name)
+        flt = () if allow is None else (_ptr(allow),)
         users = self._dev(users, torch.int64).reshape(-1)
         n, k = users.shape[0], int(k)
         off, seen_items = self._seen(seen)
         total = int(self.lib.sml_topk_scratch_bytes(self._ctx, n, k, wi.shape[0]))
         if total < 0 or n == 0:          # argument checks (k, n_item) and the empty call go through the library
-            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users), 0, k, _ptr(off), _ptr(seen_items), None, None, None,
+            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users), 0, k, _ptr(off), _ptr(seen_items), *flt, None, None, None,
                        self._stream()), name)
         items = torch.empty(n, k, device=self.device, dtype=torch.int32)
         scores = torch.empty(n, k, device=self.device, dtype=torch.float32)
@@ -760,20 +798,23 @@ class HipEngine(object):
             nbytes = int(self.lib.sml_topk_scratch_bytes(self._ctx, m, k, wi.shape[0]))
             if scratch is None or scratch.numel() < nbytes:
                 scratch = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
-            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, k, _ptr(off), _ptr(seen_items), _ptr(scratch),
-                       _ptr(items[c0:]), _ptr(scores[c0:]), self._stream()), name)
+            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, k, _ptr(off), _ptr(seen_items), *flt,
+                       _ptr(scratch), _ptr(items[c0:]), _ptr(scores[c0:]), self._stream()), name)
         return items.long(), scores
 
     USER_RANK_SCRATCH_BYTES = 256 << 20  # held-out items of one sml_user_rank call are capped so its scratch fits this
 
-    def user_ranks(self, user_tab, item_tab, users, pos_off, pos_items, seen=None, ks=(20,)):
+    def user_ranks(self, user_tab, item_tab, users, pos_off, pos_items, seen=None, ks=(20,), allow=None):
         """Every user's held-out items ranked against the whole catalogue, and per-user metrics at each K in `ks`
         (include/sml_hip.h, sml_user_rank / sml_user_rank_f16 / sml_user_metrics: fp32 or fp16 tables).  users int64 [n]; pos_off int64 [n + 1] and pos_items
         int32 [n_pos]: users[x]'s held-out items, ascending and unique in [pos_off[x], pos_off[x + 1]).  Returns a dict:
-        above, pos int32 [n_pos]; hits int32, dcg, ap float32 [n, len(ks)]; first int32 [n]."""
+        above, pos int32 [n_pos]; hits int32, dcg, ap float32 [n, len(ks)]; first int32 [n].  allow: an item filter (_allow);
+        only allowed items are eligible, and a held-out item that is not allowed has pos -1 (sml_user_rank_filtered)."""
         wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
-        name = "sml_user_rank" + sfx
+        allow = self._allow(allow, wi.shape[0])
+        name = "sml_user_rank" + ("" if allow is None else "_filtered") + sfx
         call = getattr(self.lib, name)
+        flt = () if allow is None else (_ptr(allow),)
         users = self._dev(users, torch.int64).reshape(-1)
         off_h = np.asarray(pos_off.cpu() if torch.is_tensor(pos_off) else pos_off, dtype=np.int64).reshape(-1)
         pos_items = self._dev(pos_items, torch.int32).reshape(-1)
@@ -791,8 +832,8 @@ class HipEngine(object):
                    ap=torch.empty(n, n_k, device=self.device, dtype=torch.float32),
                    first=torch.empty(n, device=self.device, dtype=torch.int32))
         if n == 0 or n_pos == 0:         # argument checks (d, n_item, Seen, ks) go through the library
-            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], None, 0, None, None, 0, _ptr(off), _ptr(seen_items), None, None, None,
-                       self._stream()), name)
+            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], None, 0, None, None, 0, _ptr(off), _ptr(seen_items), *flt, None, None,
+                       None, self._stream()), name)
             check(self.lib.sml_user_metrics(self._ctx, None, None, 0, ks_p, n_k, None, None, None, None, self._stream()),
                   "sml_user_metrics")
             if n:
@@ -817,8 +858,8 @@ class HipEngine(object):
             if scratch is None or scratch.numel() < nbytes:
                 scratch = torch.empty(max(nbytes, 1), device=self.device, dtype=torch.uint8)
             check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, _ptr(sub_off), _ptr(pos_items[e0:]), e1 - e0,
-                       _ptr(off), _ptr(seen_items), _ptr(scratch), _ptr(out["above"][e0:]), _ptr(out["pos"][e0:]), self._stream()),
-                  name)
+                       _ptr(off), _ptr(seen_items), *flt, _ptr(scratch), _ptr(out["above"][e0:]), _ptr(out["pos"][e0:]),
+                       self._stream()), name)
             # a chunk of empty sets reads no pos; it still passes a valid pointer (an empty slice's may be null)
             pos_c = out["pos"][e0:] if e1 > e0 else out["pos"]
             check(self.lib.sml_user_metrics(self._ctx, _ptr(pos_c), _ptr(sub_off), m, ks_p, n_k,

@@ -69,39 +69,45 @@ class MFbasemode(nn.Module):
         hit_rows = (ranks < topK).nonzero()[:, 0]
         return hit_rows, ranks, hits * 1.0, (torch.tensor(ndcg) if hits > 0 else 0)
 
-    def recommend(self, users, topK=20, exclude=None):
+    def recommend(self, users, topK=20, exclude=None, items=None):
         """(items int64 [n, topK], scores float32 [n, topK]): each user's topK items over the whole catalogue by the score
         test() uses (no bias terms), score descending then item id ascending, leaving out `exclude` (a
-        sml_amd.retrieval.SeenItems or a (seen_off, seen_items) CSR); missing slots are (-1, -inf)."""
-        from .retrieval import as_csr
+        sml_amd.retrieval.SeenItems or a (seen_off, seen_items) CSR); missing slots are (-1, -inf).  items: restrict the
+        lists to a subset of the catalogue (a sml_amd.retrieval.ItemFilter, a bool mask [item_num] or int32 filter words)."""
+        from .retrieval import as_csr, as_filter
         eng = _engine_for(self)
         w = self.user_laten.weight
-        return eng.topk_items(w.data, self.item_laten.weight.data, users, topK, as_csr(exclude, w.device))
+        return eng.topk_items(w.data, self.item_laten.weight.data, users, topK, as_csr(exclude, w.device),
+                              as_filter(items, self.item_laten.weight.shape[0], w.device))
 
-    def test_full(self, inputs_data, topK=20, exclude=None):
+    def test_full(self, inputs_data, topK=20, exclude=None, items=None):
         """test() with the positive ranked against the WHOLE catalogue: inputs_data [n, >= 2] (user, positive, ... --
         further columns are ignored), rank = #{items != positive, not excluded, scoring strictly above it}.
-        Returns (hits, ndcg_sum, indices of the rows that hit)."""
-        from .retrieval import as_csr
+        Returns (hits, ndcg_sum, indices of the rows that hit).  items (as in recommend): the positive is ranked among
+        the allowed items only; a positive outside the subset still gets its rank among them."""
+        from .retrieval import as_csr, as_filter
         eng = _engine_for(self)
         w = self.user_laten.weight
-        ranks = eng.full_rank(w.data, self.item_laten.weight.data, inputs_data, as_csr(exclude, w.device))
+        ranks = eng.full_rank(w.data, self.item_laten.weight.data, inputs_data, as_csr(exclude, w.device),
+                              as_filter(items, self.item_laten.weight.shape[0], w.device))
         hits, ndcg = eng.eval_metrics(ranks, topK)
         hit_rows = (ranks < topK).nonzero()[:, 0]
         batch_ndcg = torch.tensor(ndcg) if hits > 0 else 0
         return hits * 1.0, batch_ndcg, hit_rows
 
-    def test_users(self, held_out, topK=(20, 10, 5), exclude=None):
+    def test_users(self, held_out, topK=(20, 10, 5), exclude=None, items=None):
         """Every user's whole held-out set ranked against the WHOLE catalogue at once (HipEngine.user_ranks), by the score
         test() uses.  held_out: a sml_amd.retrieval.SeenItems (retrieval.held_out) or a (off, items) CSR over all users;
         exclude as in recommend().  Returns a dict: users, pos_off, pos_items (the users with at least one held-out item
-        and their items, sml_amd.retrieval.nonempty_users), ks, and the engine's above / pos / hits / dcg / ap / first."""
-        from .retrieval import as_csr, nonempty_users
+        and their items, sml_amd.retrieval.nonempty_users), ks, and the engine's above / pos / hits / dcg / ap / first.
+        items (as in recommend): only the allowed items are ranked; a held-out item outside the subset has pos -1."""
+        from .retrieval import as_csr, as_filter, nonempty_users
         eng = _engine_for(self)
         w = self.user_laten.weight
         users, pos_off, pos_items = nonempty_users(held_out)
         ks = tuple(int(k) for k in (topK if hasattr(topK, "__len__") else (topK,)))
-        out = eng.user_ranks(w.data, self.item_laten.weight.data, users, pos_off, pos_items, as_csr(exclude, w.device), ks)
+        out = eng.user_ranks(w.data, self.item_laten.weight.data, users, pos_off, pos_items, as_csr(exclude, w.device), ks,
+                             as_filter(items, self.item_laten.weight.shape[0], w.device))
         out.update(users=users, pos_off=pos_off, pos_items=pos_items, ks=ks)
         return out
 

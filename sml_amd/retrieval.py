@@ -1,4 +1,5 @@
-"""Full-catalogue retrieval helpers: the Seen-items exclusion set of sml_full_rank / sml_topk_items.
+"""Full-catalogue retrieval helpers: the Seen-items exclusion set of sml_full_rank / sml_topk_items, and the item filter
+of their _filtered forms.
 
 SeenItems keeps, per user, the items to leave out of recommendations and full-catalogue ranks (typically everything
 the user interacted with in earlier periods) as a CSR over users:
@@ -7,6 +8,13 @@ the user interacted with in earlier periods) as a CSR over users:
     seen_items  int32, ascending and unique inside each user's range [seen_off[u], seen_off[u + 1])
 
 It is built on the host with numpy (a unique over the key u * n_item + i) and touches no random number generator.
+
+ItemFilter restricts a call to a subset of the catalogue, for every user alike: a bitmap over the items,
+
+    allow  uint32 [ceil(n_item / 32)], bit i & 31 of word i >> 5 set <=> item i may appear
+
+(bits at positions >= n_item of the last word are ignored by the kernels; ItemFilter keeps them 0).  A filtered call
+returns what the unfiltered call returns with the complement of the filter added to every user's Seen range.
 """
 import os
 
@@ -98,3 +106,92 @@ def as_csr(exclude, device):
         return exclude.device(device)
     off, items = exclude
     return torch.as_tensor(off), torch.as_tensor(items)
+
+
+class ItemFilter(object):
+    """The items a retrieval call may return or count, as the catalogue bitmap of include/sml_hip.h (sml_*_filtered).
+    A new filter allows nothing; allow / deny / from_mask edit it on the host with numpy."""
+
+    def __init__(self, n_item):
+        self.n_item = int(n_item)
+        if self.n_item <= 0:
+            raise ValueError("n_item must be positive, got %d" % self.n_item)
+        self._mask = np.zeros(self.n_item, dtype=bool)
+        self._dev = {}
+
+    def _ids(self, ids):
+        ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids).reshape(-1)
+        if ids.size == 0:
+            return ids.astype(np.int64)
+        if ids.dtype.kind not in "iu":
+            raise ValueError("item ids must be integers, got %s" % ids.dtype)
+        ids = ids.astype(np.int64)
+        if ids.min() < 0 or ids.max() >= self.n_item:
+            raise ValueError("item id out of range (n_item=%d)" % self.n_item)
+        return ids
+
+    def _set(self, ids, value):
+        self._mask[self._ids(ids)] = value
+        self._dev = {}
+        return self
+
+    def allow(self, ids):
+        """Add `ids` (duplicates allowed) to the allowed items."""
+        return self._set(ids, True)
+
+    def deny(self, ids):
+        """Remove `ids` from the allowed items."""
+        return self._set(ids, False)
+
+    @classmethod
+    def from_mask(cls, mask):
+        """mask: bool [n_item], True = allowed."""
+        mask = np.asarray(mask.cpu() if torch.is_tensor(mask) else mask)
+        if mask.dtype != np.bool_ or mask.ndim != 1:
+            raise ValueError("expected a bool mask [n_item], got %s %s" % (mask.dtype, mask.shape))
+        f = cls(mask.shape[0])
+        f._mask = mask.copy()
+        return f
+
+    def mask(self):
+        """bool [n_item] copy: True = allowed."""
+        return self._mask.copy()
+
+    def host(self):
+        """The words, uint32 [ceil(n_item / 32)] (tail bits 0)."""
+        b = np.packbits(self._mask, bitorder="little")
+        b = np.concatenate([b, np.zeros(-len(b) % 4, np.uint8)])
+        return b.view("<u4").astype(np.uint32)
+
+    def device(self, device):
+        """The cached int32 word tensor (the same bits) on `device`; rebuilt only after an edit."""
+        key = str(torch.device(device))
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.host().view(np.int32)).to(device)
+        return self._dev[key]
+
+    def __len__(self):
+        return int(self._mask.sum())
+
+
+def filter_words(n_item):
+    return (int(n_item) + 31) // 32
+
+
+def as_filter(x, n_item, device):
+    """x: None, an ItemFilter, a bool mask [n_item] (numpy or tensor), or a ready int32 word tensor
+    [ceil(n_item / 32)] -> the int32 word tensor on `device` the engine's retrieval calls take as allow= (None: no filter)."""
+    if x is None:
+        return None
+    if isinstance(x, ItemFilter):
+        if x.n_item != int(n_item):
+            raise ValueError("the filter is over %d items, the catalogue has %d" % (x.n_item, n_item))
+        return x.device(device)
+    if torch.is_tensor(x) and x.dtype == torch.int32:
+        if x.dim() != 1 or x.shape[0] != filter_words(n_item):
+            raise ValueError("an item filter over %d items has %d words, got shape %s" % (n_item, filter_words(n_item), tuple(x.shape)))
+        return x.to(device).contiguous()
+    m = np.asarray(x.cpu() if torch.is_tensor(x) else x)
+    if m.dtype != np.bool_ or m.shape != (int(n_item),):
+        raise ValueError("an item filter is None, an ItemFilter, a bool mask [n_item] or int32 words, got %s %s" % (m.dtype, m.shape))
+    return ItemFilter.from_mask(m).device(device)

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """The fp32 retrieval entry points of the in-tree libsml_hip.so against ANOTHER build of the library (e.g. the previous
 commit's, built by hand into tools/_ab/), alternating in one process at the Yelp shape of tools/half_retrieval_probe.py:
-full_rank over 10,000 rows, topk_items K = 20 over all 60,000 users, user_ranks over the held-out sets, d = 32 and 64.
+full_rank over 10,000 rows, topk_items K = 20 over all 60,000 users, user_ranks over the held-out sets, d = 32 and 64
+(--half_d 128: the _f16 entry points on fp16 tables at those widths as well).  Every call passes allow=None.
 Medians, minima and the interquartile spread of the alternated repetitions; outputs compared byte for byte.  The other
 build may be older than the header: only the symbols it exports are bound.
-usage: python tools/retrieval_ab.py <other.so> [--d 32,64] [--reps 20] [--out file.json]"""
+usage: python tools/retrieval_ab.py <other.so> [--d 32,64] [--half_d 128] [--reps 20] [--out file.json]"""
 import argparse
 import ctypes
 import json
@@ -36,6 +37,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("other")
     ap.add_argument("--d", default="32,64")
+    ap.add_argument("--half_d", default="", help="widths measured on fp16 tables (the _f16 entry points)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
@@ -54,10 +56,13 @@ def main():
     users = torch.arange(U, device=dev)
     result = {"tool": "retrieval_ab", "device": torch.cuda.get_device_name(dev), "other": os.path.basename(args.other), "U": U, "I": I,
               "rows": N_ROWS, "k": K, "held_out_users": int(len(h_users)), "reps": args.reps, "dtype": "fp32", "by_d": {}}
-    for d in [int(x) for x in args.d.split(",")]:
+    widths = [(int(x), False) for x in args.d.split(",") if x] + [(int(x), True) for x in args.half_d.split(",") if x]
+    for d, half in widths:
         g = torch.Generator().manual_seed(d)
-        wu = (torch.randn(U, d, generator=g) * 0.3).half().float().to(dev)       # the probe's tables, widened
-        wi = (torch.randn(I, d, generator=g) * 0.3).half().float().to(dev)
+        wu = (torch.randn(U, d, generator=g) * 0.3).half().to(dev)               # the probe's tables (fp32: widened)
+        wi = (torch.randn(I, d, generator=g) * 0.3).half().to(dev)
+        if not half:
+            wu, wi = wu.float(), wi.float()
         engs = {"tree": HipEngine(dev, d, 256), "other": HipEngine(dev, d, 256, lib=other)}
         calls = {"full_rank": lambda e: e.full_rank(wu, wi, rows, csr),
                  "topk_items": lambda e: e.topk_items(wu, wi, users, K, csr),
@@ -67,7 +72,7 @@ def main():
             ta, tb, oa, ob = alternate(lambda: fn(engs["tree"]), lambda: fn(engs["other"]), args.reps, args.warmup, dev)
             sa, sb = stats(ta), stats(tb)
             res[name] = {"tree": sa, "other": sb, "tree_over_other": round(sa["ms"] / sb["ms"], 3), "same_bytes": same(oa, ob)}
-        result["by_d"][str(d)] = res
+        result["by_d"][str(d) + ("_fp16" if half else "")] = res
         del engs
     line = json.dumps(result)
     print(line)
