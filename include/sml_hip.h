@@ -423,7 +423,8 @@ int sml_flag_wait(int32_t* flag, int value, double timeout_s, void* stream);
 int sml_eval_metrics(sml_ctx* ctx, const int32_t* rank, int64_t n, int topk, float* out, void* stream);
 
 /* ---- full-catalogue retrieval ------------------------------------------------------ */
-/* S(u, i) = <w_user[u], w_item[i]> in fp32 (no bias terms, as MFbasemode.test scores), one fmaf chain over the d
+/* S(u, i) = <w_user[u], w_item[i]> in fp32 (no bias terms, as MFbasemode.test scores; the _adjusted entry points below
+ * add per-item terms), one fmaf chain over the d
  * dims in a fixed order shared by both entry points: the two score every (u, i) to the same float, bit for bit.
  * The order pairs dim s with dim s + d/2: acc = 0; for s = 0 .. d/2 - 1 { acc = fmaf(x[s], u[s], acc);
  * acc = fmaf(x[s + d/2], u[s + d/2], acc); } with u = w_user[u], x = w_item[i], each fmaf rounded once (round to
@@ -543,6 +544,61 @@ int64_t sml_item_filter_words(int64_t n_item);
  * checks them: HipEngine.item_filter_from_ids does). */
 int sml_item_filter_from_ids(sml_ctx* ctx, const int32_t* ids, int64_t n_ids, int64_t n_item, int invert, uint32_t* words,
                              void* stream);
+/* ADJUSTED SCORE: the three calls ranking by a per-item affine function of the score instead of the bare dot product,
+ *
+ *     A(u, i) = fmaf(S(u, i), scale[i], offset[i])
+ *
+ * computed in fp32 and rounded once: S is the fmaf chain defined above (fp16 tables widened exactly as above), and the
+ * term is one more fused multiply-add on its rounded value.  scale and offset are fp32 per-item arrays for both table
+ * element types.  offset = an item bias ranks by dot + bias (a per-user bias cannot reorder a user's list and is left
+ * out); scale[i] = 1 / ||x_i|| ranks by the cosine.
+ * Everything the three calls do with S they do with A:
+ *   rank / above   strict > against the positive's own A(u, p);
+ *   top-K order    A descending, then item id ascending; the returned scores are A;
+ *   pos            eligible means not in Seen(u), allowed, and A not NaN.
+ * The NaN rules are stated on A: a NaN is never above anything, a NaN positive ranks 0, a NaN item enters no list, and as
+ * a held-out item it has pos -1.  scale and offset may hold any float: an offset of -inf sends an item to the end of every
+ * list but keeps it eligible (it fills a list that has room, after every finite score, by id); a NaN term removes the item.
+ * With scale == 1 and offset == +0 everywhere (scale ≡ 1, offset ≡ +0), A == S as values: only the sign bit of a -0 score
+ * changes (fmaf(-0, 1, +0) = +0), every integer output equals the unadjusted call's byte for byte, and every score
+ * compares equal.
+ * Layout: adj float [2][n_pad], device memory, 16-byte aligned, n_pad = sml_item_adjust_len(n_item) = 32 * ceil(n_item / 32);
+ * plane 0 (adj[0 .. n_pad)) is scale, plane 1 (adj[n_pad .. 2 n_pad)) is offset.  Pad entries are ignored, whatever they
+ * hold (the walk loads whole 32-item tiles; the items past n_item are masked by id).
+ * Each _adjusted entry point takes the argument list of its _filtered form with `elem_bytes` (4: fp32 tables, d = 32 / 64;
+ * 2: fp16 tables, d = 32 / 64 / 128; any other pair is refused) inserted after w_item and `adj` after allow.  allow may be
+ * NULL: no filter.  adj == NULL is refused, and so is an adj that is not 16-byte aligned (the unadjusted entry points are
+ * the calls without terms).  One entry point per
+ * operation serves both element types.  Seen, the item filter and its identity, (-1, -inf) padding, 1 <= k <= 128,
+ * determinism and the scratch sizes carry over verbatim: sml_topk_scratch_bytes and sml_user_rank_scratch_bytes serve
+ * these calls, and sml_user_metrics is unchanged.  At d = 32 / 64 an adjusted call on fp16 tables equals the call on fp32
+ * copies of them bit for bit, with the same adj.  With the same Seen, filter and adj, the positive of a row (u, p) sits at
+ * position rank + #{eligible i != p : A(u,i) == A(u,p), i < p} of u's adjusted list whenever that is < k.
+ * Cost: four 16-byte loads per plane per lane and tile, the same for the 32 user lanes of a lane half (they are served by
+ * one cache line each), requested with the next tile's item rows; a tile the filter skips loads none. */
+/* n_pad, the floats of one plane of adj for n_item items; < 0: bad argument (0 < n_item < 2^31). */
+int64_t sml_item_adjust_len(int64_t n_item);
+/* Build adj [2][n_pad] on the device from optional device arrays scale and offset, float [n_item] each: NULL scale means
+ * 1 everywhere, NULL offset means +0 everywhere.  The pad entries are written (1, 0). */
+int sml_item_adjust_fill(sml_ctx* ctx, const float* scale, const float* offset, int64_t n_item, float* adj, void* stream);
+/* Cosine: write plane 0 of adj (only; plane 1 is not touched, the pad entries of plane 0 are written 1) from an item table
+ * [n_item, d] of elem_bytes 4 or 2: n2 = the score chain of row i with itself (x_i on both sides, same dim order, fp16
+ * widened exactly), scale[i] = n2 > 0 ? 1.0f / sqrtf(n2) : 0.0f with correctly rounded sqrtf and division.  A zero row
+ * therefore scores 0 against everything instead of NaN (a row whose n2 is NaN gets scale 0 too, one whose n2 is +inf gets
+ * 1 / inf = 0). */
+int sml_item_adjust_cosine(sml_ctx* ctx, const void* w_item, int elem_bytes, int64_t n_item, float* adj, void* stream);
+int sml_full_rank_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item,
+                           const int64_t* rows, int64_t n, int n_cols,
+                           const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                           int32_t* rank, void* stream);
+int sml_topk_items_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item,
+                            const int64_t* users, int64_t n, int k,
+                            const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                            void* scratch, int32_t* items, float* scores, void* stream);
+int sml_user_rank_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item,
+                           const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
+                           const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                           void* scratch, int32_t* above, int32_t* pos, void* stream);
 /* Per-user metrics from pos (as sml_user_rank writes it; any value < 0 is never a hit) over the ranges of pos_off,
  * n < 2^31.  ks: HOST int32 [n_k], 1 <= n_k <= 8, every K >= 1.  For user x with m = |T(x)| and each K (outputs [n, n_k], row-major):
  *   hits = #{p : 0 <= pos(p) < K};  dcg = sum over hits of 1/log2(pos + 2), fp32, summed in ascending pos;

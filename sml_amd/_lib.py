@@ -130,6 +130,15 @@ SIGNATURES = {
                                                   ctypes.c_int64, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "sml_item_filter_words": (ctypes.c_int64, [ctypes.c_int64]),
     "sml_item_filter_from_ids": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_void, c_void]),
+    "sml_item_adjust_len": (ctypes.c_int64, [ctypes.c_int64]),
+    "sml_item_adjust_fill": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, c_void]),
+    "sml_item_adjust_cosine": (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, c_void]),
+    "sml_full_rank_adjusted": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int,
+                                              c_void, c_void, c_void, c_void, c_void, c_void]),
+    "sml_topk_items_adjusted": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int,
+                                               c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    "sml_user_rank_adjusted": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void,
+                                              ctypes.c_int64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "sml_user_metrics": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,
                                         c_void]),
     "sml_stream_create_cu_range": (ctypes.c_int, [ctypes.POINTER(c_void), ctypes.c_int, ctypes.c_int, ctypes.c_int]),

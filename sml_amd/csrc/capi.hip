@@ -1795,16 +1795,18 @@ static bool retrieval_args_ok(sml_ctx* ctx, int elem_bytes, int64_t n_item, cons
 }
 
 // every table-reading entry point exists four times over one body: `what` names the caller, elem_bytes its tables, allow
-// the item filter of the _filtered forms (NULL: none, which is what the unfiltered entry points pass)
+// the item filter of the _filtered forms (NULL: none, which is what the unfiltered entry points pass).  The _adjusted entry
+// points are a fifth caller: adj is their per-item term table (NULL everywhere else), with_adj says that one is required
 static int full_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
                           const int64_t* rows, int64_t n, int n_cols, const int64_t* seen_off, const int32_t* seen_items,
-                          const uint32_t* allow, int32_t* rank, void* stream) {
+                          const uint32_t* allow, int32_t* rank, void* stream, const float* adj = nullptr, bool with_adj = false) {
+    if (with_adj && (!adj || ((uintptr_t)adj & 15))) return fail(SML_EINVAL, what, "adj must be non-null and 16-byte aligned");
     if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || n_cols < 2 || n < 0)
         return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, n_cols >= 2, seen_off and seen_items both or neither)");
     if (n == 0) return SML_OK;
     if (!w_user || !w_item || !rows || !rank) return fail(SML_EINVAL, what, "null argument");
     DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
-    PROFILED(PC_MISC, HIPCHK(sml_launch_full_rank(ctx->d, elem_bytes, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, rank, st)));
+    PROFILED(PC_MISC, HIPCHK(sml_launch_full_rank(ctx->d, elem_bytes, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, adj, rank, st)));
     return SML_OK;
 }
 
@@ -1838,13 +1840,15 @@ int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item) {
 
 static int topk_items_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
                            const int64_t* users, int64_t n, int k, const int64_t* seen_off, const int32_t* seen_items,
-                           const uint32_t* allow, void* scratch, int32_t* items, float* scores, void* stream) {
+                           const uint32_t* allow, void* scratch, int32_t* items, float* scores, void* stream, const float* adj = nullptr,
+                           bool with_adj = false) {
+    if (with_adj && (!adj || ((uintptr_t)adj & 15))) return fail(SML_EINVAL, what, "adj must be non-null and 16-byte aligned");
     if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || k < 1 || k > 128 || n < 0)
         return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 1 <= k <= 128, 0 < n_item < 2^31, seen_off and seen_items both or neither)");
     if (n == 0) return SML_OK;
     if (!w_user || !w_item || !users || !scratch || !items || !scores) return fail(SML_EINVAL, what, "null argument");
     DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
-    PROFILED(PC_MISC, HIPCHK(sml_launch_topk(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, scratch, items, scores, st)));
+    PROFILED(PC_MISC, HIPCHK(sml_launch_topk(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, adj, scratch, items, scores, st)));
     return SML_OK;
 }
 
@@ -1884,7 +1888,8 @@ int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int6
 static int user_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
                           const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
                           const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above,
-                          int32_t* pos, void* stream) {
+                          int32_t* pos, void* stream, const float* adj = nullptr, bool with_adj = false) {
+    if (with_adj && (!adj || ((uintptr_t)adj & 15))) return fail(SML_EINVAL, what, "adj must be non-null and 16-byte aligned");
     if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || n < 0 || n >= ((int64_t)1 << 31) || n_pos < 0 ||
         n_pos >= ((int64_t)1 << 31))
         return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, 0 <= n, n_pos < 2^31, seen_off and seen_items both or neither)");
@@ -1893,7 +1898,7 @@ static int user_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const 
         return fail(SML_EINVAL, what, "null argument");
     DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
     PROFILED(PC_MISC, HIPCHK(sml_launch_user_rank(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
-                                               seen_items, allow, scratch, above, pos, st)));
+                                               seen_items, allow, adj, scratch, above, pos, st)));
     return SML_OK;
 }
 
@@ -1924,6 +1929,56 @@ int sml_user_rank_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_i
                                void* stream) {
     return user_rank_impl("sml_user_rank_filtered_f16", 2, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
                           seen_items, allow, scratch, above, pos, stream);
+}
+
+// the adjusted score A(u, i) = fmaf(S(u, i), scale[i], offset[i]): one entry point per operation serves both element types
+static bool elem_ok(int elem_bytes) { return elem_bytes == 4 || elem_bytes == 2; }
+
+int sml_full_rank_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* rows,
+                           int64_t n, int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow,
+                           const float* adj, int32_t* rank, void* stream) {
+    if (!elem_ok(elem_bytes)) return fail(SML_EINVAL, "sml_full_rank_adjusted", "bad argument (elem_bytes must be 4 or 2)");
+    return full_rank_impl("sml_full_rank_adjusted", elem_bytes, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, rank,
+                          stream, adj, true);
+}
+
+int sml_topk_items_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* users,
+                            int64_t n, int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                            void* scratch, int32_t* items, float* scores, void* stream) {
+    if (!elem_ok(elem_bytes)) return fail(SML_EINVAL, "sml_topk_items_adjusted", "bad argument (elem_bytes must be 4 or 2)");
+    return topk_items_impl("sml_topk_items_adjusted", elem_bytes, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, scratch,
+                           items, scores, stream, adj, true);
+}
+
+int sml_user_rank_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* users,
+                           int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
+                           const int32_t* seen_items, const uint32_t* allow, const float* adj, void* scratch, int32_t* above, int32_t* pos,
+                           void* stream) {
+    if (!elem_ok(elem_bytes)) return fail(SML_EINVAL, "sml_user_rank_adjusted", "bad argument (elem_bytes must be 4 or 2)");
+    return user_rank_impl("sml_user_rank_adjusted", elem_bytes, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
+                          seen_items, allow, scratch, above, pos, stream, adj, true);
+}
+
+int64_t sml_item_adjust_len(int64_t n_item) {
+    if (n_item <= 0 || n_item >= ((int64_t)1 << 31)) return fail(SML_EINVAL, "sml_item_adjust_len", "bad argument (0 < n_item < 2^31)");
+    return sml_item_adjust_pad(n_item);
+}
+
+int sml_item_adjust_fill(sml_ctx* ctx, const float* scale, const float* offset, int64_t n_item, float* adj, void* stream) {
+    if (!ctx || n_item <= 0 || n_item >= ((int64_t)1 << 31)) return fail(SML_EINVAL, "sml_item_adjust_fill", "bad argument (0 < n_item < 2^31)");
+    if (!adj || ((uintptr_t)adj & 15)) return fail(SML_EINVAL, "sml_item_adjust_fill", "adj must be non-null and 16-byte aligned");
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_item_adjust_fill(scale, offset, n_item, adj, st)));
+    return SML_OK;
+}
+
+int sml_item_adjust_cosine(sml_ctx* ctx, const void* w_item, int elem_bytes, int64_t n_item, float* adj, void* stream) {
+    if (!ctx || !elem_ok(elem_bytes) || !sml_retrieval_supports(ctx->d, elem_bytes) || n_item <= 0 || n_item >= ((int64_t)1 << 31))
+        return fail(SML_EINVAL, "sml_item_adjust_cosine", "bad argument (d must be 32/64, or 128 for fp16 tables; elem_bytes 4 or 2; 0 < n_item < 2^31)");
+    if (!w_item || !adj || ((uintptr_t)adj & 15)) return fail(SML_EINVAL, "sml_item_adjust_cosine", "null argument, or adj not 16-byte aligned");
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_item_adjust_cosine(ctx->d, elem_bytes, w_item, n_item, adj, st)));
+    return SML_OK;
 }
 
 int64_t sml_item_filter_words(int64_t n_item) {

@@ -56,6 +56,16 @@
 // rows, no MFMAs, no callback; the double buffer prefetches the next NON-EMPTY tile of the slice.  The filtered kernels
 // are instantiations of their own (walk_slice<.., true>, k_x_f<D> / k_x_f_h<D>); the unfiltered ones compile to what
 // they were without it.  k_filter_fill / k_filter_from_ids build a bitmap from a list of item ids.
+//
+// Adjusted score (the sml_*_adjusted entry points): A(u, i) = fmaf(S(u, i), scale[i], offset[i]), one more fp32 rounding
+// per score, from a padded per-item table adj float [2][n_pad], n_pad = 32 * n_tiles (plane 0 scale, plane 1 offset).  A
+// lane's 16 items of a tile are four runs of four consecutive rows (row_of), so the terms of a tile are four 16-byte loads
+// per plane, the same for the 32 user lanes of a half; they are requested with the next tile's item rows and applied to
+// the 16 accumulators, one explicit fmaf each, before the kernel's callable sees them -- the callables do not change.
+// The thresholds (full_rank_body's thr, ur_thresholds_body's key) are the same expression on score_chain.  A skipped
+// tile loads no adj; the last tile's loads end at n_pad, whose pad entries belong to items the eligibility word masks.
+// The adjusted kernels are instantiations of their own (walk_slice<.., F, true>, k_x_a<D, F> / k_x_a_h<D, F>).
+// k_adjust_fill / k_adjust_cosine build the table.
 #include <climits>
 #include <cmath>
 #include <type_traits>
@@ -206,6 +216,42 @@ __device__ __forceinline__ unsigned tile_items(int64_t t, int64_t n_item) {
     return left < RT ? (1u << left) - 1u : ~0u;
 }
 
+// the per-item score terms of the 16 items a lane holds of one tile: rows 8 g + 4 h + {0..3}, g = 0..3, are four floats at a
+// 16-byte aligned address of each plane (tiles start at multiples of 32).  A = false: empty, and every use in the walk is
+// under `if constexpr (A)`, so that the existing instantiations compile to the instructions they had
+template <bool A>
+struct TileTerms {};
+
+template <>
+struct TileTerms<true> {
+    f32x4 sc[4], of[4];
+    // base: the tile's first item, a multiple of 32 below n_pad, so every load ends at or before the plane's end
+    __device__ __forceinline__ void load(const float* __restrict__ adj, int64_t n_pad, int64_t base, int h) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(adj + base + 4 * h);
+        const f32x4* q = reinterpret_cast<const f32x4*>(adj + n_pad + base + 4 * h);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) { sc[g] = p[2 * g]; of[g] = q[2 * g]; }
+    }
+    // acc[r] = S of item row_of(r, h) -> A: one fmaf each, rounded once, never left to contraction
+    __device__ __forceinline__ f32x16 apply(const f32x16& acc) const {
+        f32x16 out;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) out[r] = __builtin_fmaf(acc[r], sc[r >> 2][r & 3], of[r >> 2][r & 3]);
+        return out;
+    }
+};
+
+// A(u, p) from s = S(u, p): the expression of TileTerms::apply, for the thresholds (A = false: s itself).  scale / offset:
+// the two planes of adj
+template <bool A>
+__device__ __forceinline__ float adjusted(float s, const float* __restrict__ scale, const float* __restrict__ offset, int64_t p) {
+    if constexpr (!A) return s;
+    else return __builtin_fmaf(s, scale[p], offset[p]);
+}
+
+// plane 1 of adj [2][n_pad]
+__device__ __forceinline__ const float* offset_plane(const float* adj, int64_t n_item) { return adj + (n_item + RT - 1) / RT * RT; }
+
 // The catalogue walk of one wave: user u's scores against every 32-item tile of the lane's slice, next tile's item rows
 // in flight under the current tile's MFMAs.  tile(acc, base, elig) runs once per tile: acc[q] = S(u, base + row_of(q, h)),
 // bit q of elig set <=> that item exists (< n_item), is not in Seen(u) and, with a filter, is allowed.  An empty slice
@@ -214,10 +260,12 @@ __device__ __forceinline__ unsigned tile_items(int64_t t, int64_t n_item) {
 // (the slice comes from blockIdx), so the words travel through scalar loads and SGPRs.  A tile whose word is 0 is never
 // visited: the scan for the next non-empty tile runs before the prefetch, and its first word -- tile t + 1's -- was
 // requested one tile earlier, together with that tile's item rows (`pre`).  A slice without a non-empty tile returns at once.
-template <int D, class T, bool F, class Tile>
+// A: acc[q] is A(u, i) = fmaf(S(u, i), scale[i], offset[i]) instead, the terms read from adj (float [2][32 * n_tiles]).
+template <int D, class T, bool F, bool A, class Tile>
 __device__ __forceinline__ void walk_slice(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item, int64_t u,
                                            const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                           const uint32_t* __restrict__ allow, const LanePos& lp, int slice_tiles, Tile&& tile) {
+                                           const uint32_t* __restrict__ allow, const float* __restrict__ adj, const LanePos& lp,
+                                           int slice_tiles, Tile&& tile) {
     const int64_t n_tiles = (n_item + RT - 1) / RT;
     const int64_t t0 = (int64_t)lp.slice * slice_tiles;
     const int64_t t1 = t0 + slice_tiles < n_tiles ? t0 + slice_tiles : n_tiles;
@@ -236,6 +284,8 @@ __device__ __forceinline__ void walk_slice(const T* __restrict__ wu, const T* __
     HalfRow<D, T> a, an;
     int64_t ia = t * RT + lp.j;
     a.load(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h);
+    TileTerms<A> m, mn;
+    if constexpr (A) m.load(adj, n_tiles * RT, t * RT, lp.h);
     for (int64_t tn; t < t1; t = tn) {
         tn = t + 1;
         unsigned wn = pre;
@@ -247,32 +297,35 @@ __device__ __forceinline__ void walk_slice(const T* __restrict__ wu, const T* __
         if (tn < t1) {
             ia = tn * RT + lp.j;
             an.load(wi + (ia < n_item ? ia : n_item - 1) * D, lp.h);
+            if constexpr (A) mn.load(adj, n_tiles * RT, tn * RT, lp.h);
         }
         b.keep_packed();
-        const f32x16 acc = tile_scores<D, T>(a, b);
+        f32x16 acc = tile_scores<D, T>(a, b);
+        if constexpr (A) acc = m.apply(acc);
         const int64_t base = t * RT;
         if constexpr (F) sc.skip_to(base);
         // bit i of `real`: item base + i exists, is not in Seen (and is allowed)
         const unsigned real = ~sc.word(base) & (F ? w : tile_items(t, n_item));
         tile(acc, base, lane_rows(real, lp.h));
         a = an;
+        if constexpr (A) m = mn;
         w = wn;
     }
 }
 
 // The kernels below are bodies over the element type T; each has two __global__ entry points, k_x<D> on fp32 tables and
 // k_x_h<D> on fp16 tables.
-template <int D, bool F = false, class T>
+template <int D, bool F = false, bool A = false, class T>
 __device__ __forceinline__ void full_rank_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                                const int64_t* __restrict__ rows, int64_t n, int n_cols,
                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
                                                int slices, int slice_tiles, int32_t* __restrict__ rank,
-                                               const uint32_t* __restrict__ allow = nullptr) {
+                                               const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr) {
     const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
     const int64_t u = rows[lp.rc * n_cols], p = rows[lp.rc * n_cols + 1];
-    const float thr = score_chain<D>(wu + u * D, wi + p * D);
+    const float thr = adjusted<A>(score_chain<D>(wu + u * D, wi + p * D), adj, A ? offset_plane(adj, n_item) : nullptr, p);
     int cnt = 0;
-    walk_slice<D, T, F>(wu, wi, n_item, u, seen_off, seen_items, allow, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
+    walk_slice<D, T, F, A>(wu, wi, n_item, u, seen_off, seen_items, allow, adj, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) cnt += (acc[q] > thr) & ((elig >> q) & 1u) & (base + row_of(q, lp.h) != p);
     });
@@ -337,13 +390,13 @@ __device__ __forceinline__ void list_insert(float* ls, int* li, int k, int j, in
 }
 
 // candidates of user x, slice s: cand_s / cand_i [(x * slices + s) * k + q], cand_n [x * slices + s]
-template <int D, bool F = false, class T>
+template <int D, bool F = false, bool A = false, class T>
 __device__ __forceinline__ void topk_slice_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                                 const int64_t* __restrict__ users, int64_t n, int k,
                                                 const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
                                                 int slices, int slice_tiles, float* __restrict__ cand_s,
                                                 int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n,
-                                                const uint32_t* __restrict__ allow = nullptr) {
+                                                const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr) {
     extern __shared__ float lds[];
     const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
     const int h = lp.h, j = lp.j;
@@ -353,7 +406,7 @@ __device__ __forceinline__ void topk_slice_body(const T* __restrict__ wu, const 
     int cnt = 0;                          // live entries of user j's list (both lane halves keep it)
     float thr_s = -INFINITY;              // register copy of the K-th entry: lags the list, never ahead of it
     int thr_i = INT_MAX;
-    walk_slice<D, T, F>(wu, wi, n_item, u, seen_off, seen_items, allow, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
+    walk_slice<D, T, F, A>(wu, wi, n_item, u, seen_off, seen_items, allow, adj, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
         unsigned pass = 0;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
@@ -540,14 +593,15 @@ __device__ __forceinline__ int64_t ur_segment(const int64_t* __restrict__ off, i
 }
 
 // in_seen[e] = 1: the held-out item is not eligible by id -- in Seen(u) or, with a filter (F), not allowed
-template <int D, bool F = false, class T>
+template <int D, bool F = false, bool A = false, class T>
 __device__ __forceinline__ void ur_thresholds_body(const T* __restrict__ wu, const T* __restrict__ wi,
                                                    const int64_t* __restrict__ users, int64_t n,
                                                    const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
                                                    int64_t n_pos, const int64_t* __restrict__ seen_off,
                                                    const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
                                                    float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
-                                                   int32_t* __restrict__ in_seen, const uint32_t* __restrict__ allow = nullptr) {
+                                                   int32_t* __restrict__ in_seen, const uint32_t* __restrict__ allow = nullptr,
+                                                   const float* __restrict__ scale = nullptr, const float* __restrict__ offset = nullptr) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_pos) return;
     const int64_t x = ur_segment(pos_off, n, e);
@@ -561,7 +615,7 @@ __device__ __forceinline__ void ur_thresholds_body(const T* __restrict__ wu, con
     }
     if constexpr (F) sn |= !((allow[p >> 5] >> (p & 31)) & 1u);
     seg[e] = (int32_t)x;
-    ks[e] = score_chain<D>(wu + u * D, wi + (int64_t)p * D);
+    ks[e] = adjusted<A>(score_chain<D>(wu + u * D, wi + (int64_t)p * D), scale, offset, p);
     ki[e] = p;
     kx[e] = (int32_t)e;
     in_seen[e] = sn;
@@ -655,13 +709,14 @@ __device__ __forceinline__ void ur_place(const float* ts, const int32_t* ti, int
 
 // ss / si: every user's thresholds and ids in ur_less order.  At sorted place b of user x, bin_p (zeroed) receives the
 // number of eligible items whose pos bound is b, and bin_d (zeroed) what turns those counts into the above bounds'
-template <int D, bool F = false, class T>
+template <int D, bool F = false, bool A = false, class T>
 __device__ __forceinline__ void ur_count_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                               const int64_t* __restrict__ users, int64_t n, const int64_t* __restrict__ pos_off,
                                               const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
                                               int slices, int slice_tiles, const float* __restrict__ ss,
                                               const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
-                                              int32_t* __restrict__ bin_d, const uint32_t* __restrict__ allow = nullptr) {
+                                              int32_t* __restrict__ bin_d, const uint32_t* __restrict__ allow = nullptr,
+                                              const float* __restrict__ adj = nullptr) {
     __shared__ float l_s[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_i[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_p[kUrWaves][kUrWin * RT];
@@ -685,7 +740,7 @@ __device__ __forceinline__ void ur_count_body(const T* __restrict__ wu, const T*
     const float t0s = mv ? ss[lo] : 0.0f, tws = mv ? ss[lo + mv - 1] : 0.0f;
     const int t0i = mv ? si[lo] : 0, twi = mv ? si[lo + mv - 1] : 0;
     int c0 = 0, d0 = 0;
-    walk_slice<D, T, F>(wu, wi, n_item, u, seen_off, seen_items, allow, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
+    walk_slice<D, T, F, A>(wu, wi, n_item, u, seen_off, seen_items, allow, adj, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
         unsigned live = 0;                 // NaN scores fail `better`; an item not better than the worst threshold is in no bin
         if (mv) {
 #pragma unroll
@@ -764,6 +819,139 @@ __global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_f_h(const _Float16* 
                                                                 const float* __restrict__ ss, const int32_t* __restrict__ si,
                                                                 int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
     ur_count_body<D, true>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d, allow);
+}
+
+// ---- adjusted score: the kernels of sml_*_adjusted -------------------------------------------------------------------
+
+// the same bodies over walk_slice<.., F, true>: adj is the padded term table, allow the item filter when F (else unused)
+template <int D, bool F>
+__global__ __launch_bounds__(256) void k_full_rank_a(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                     const int64_t* __restrict__ rows, int64_t n, int n_cols,
+                                                     const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                     const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                     int slice_tiles, int32_t* __restrict__ rank) {
+    full_rank_body<D, F, true>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank, allow, adj);
+}
+
+template <int D, bool F>
+__global__ __launch_bounds__(256) void k_full_rank_a_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
+                                                       const int64_t* __restrict__ rows, int64_t n, int n_cols,
+                                                       const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                       const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                       int slice_tiles, int32_t* __restrict__ rank) {
+    full_rank_body<D, F, true>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank, allow, adj);
+}
+
+template <int D, bool F>
+__global__ __launch_bounds__(256) void k_topk_slice_a(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                      const int64_t* __restrict__ users, int64_t n, int k,
+                                                      const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                      const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                      int slice_tiles, float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
+                                                      int32_t* __restrict__ cand_n) {
+    topk_slice_body<D, F, true>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n, allow, adj);
+}
+
+template <int D, bool F>
+__global__ __launch_bounds__(256) void k_topk_slice_a_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
+                                                        const int64_t* __restrict__ users, int64_t n, int k,
+                                                        const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                        const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                        int slice_tiles, float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
+                                                        int32_t* __restrict__ cand_n) {
+    topk_slice_body<D, F, true>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n, allow, adj);
+}
+
+template <int D, bool F>
+__global__ __launch_bounds__(256) void k_ur_thresholds_a(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                         const int64_t* __restrict__ users, int64_t n,
+                                                         const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
+                                                         int64_t n_pos, const int64_t* __restrict__ seen_off,
+                                                         const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
+                                                         const float* __restrict__ adj, int32_t* __restrict__ seg, float* __restrict__ ks,
+                                                         int32_t* __restrict__ ki, int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
+    ur_thresholds_body<D, F, true>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen, allow, adj,
+                                   offset_plane(adj, n_item));
+}
+
+template <int D, bool F>
+__global__ __launch_bounds__(256) void k_ur_thresholds_a_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
+                                                           const int64_t* __restrict__ users, int64_t n,
+                                                           const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
+                                                           int64_t n_pos, const int64_t* __restrict__ seen_off,
+                                                           const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
+                                                           const float* __restrict__ adj, int32_t* __restrict__ seg, float* __restrict__ ks,
+                                                           int32_t* __restrict__ ki, int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
+    ur_thresholds_body<D, F, true>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen, allow, adj,
+                                   offset_plane(adj, n_item));
+}
+
+template <int D, bool F>
+__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_a(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+                                                              const int64_t* __restrict__ users, int64_t n,
+                                                              const int64_t* __restrict__ pos_off,
+                                                              const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                              const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                              int slice_tiles, const float* __restrict__ ss, const int32_t* __restrict__ si,
+                                                              int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
+    ur_count_body<D, F, true>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d, allow, adj);
+}
+
+template <int D, bool F>
+__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_a_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
+                                                                int64_t n_item, const int64_t* __restrict__ users, int64_t n,
+                                                                const int64_t* __restrict__ pos_off,
+                                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                                const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                                int slice_tiles, const float* __restrict__ ss, const int32_t* __restrict__ si,
+                                                                int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
+    ur_count_body<D, F, true>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d, allow, adj);
+}
+
+// LAUNCH_TYPED for the adjusted kernels: k_x_a<D, F> / k_x_a_h<D, F>, F = a filter was given
+#define LAUNCH_ADJUSTED(name, D, tu, allow, grid, block, lds, st, ...)                                                    \
+    do {                                                                                                                  \
+        if constexpr (std::is_same<decltype(tu), const float*>::value) {                                                  \
+            if (allow) name<D, true><<<grid, block, lds, st>>>(__VA_ARGS__);                                              \
+            else name<D, false><<<grid, block, lds, st>>>(__VA_ARGS__);                                                   \
+        } else {                                                                                                          \
+            if (allow) name##_h<D, true><<<grid, block, lds, st>>>(__VA_ARGS__);                                          \
+            else name##_h<D, false><<<grid, block, lds, st>>>(__VA_ARGS__);                                               \
+        }                                                                                                                 \
+    } while (0)
+
+// adj [2][n_pad] from optional per-item arrays: NULL scale = 1, NULL offset = +0; the pad entries are written (1, 0)
+__global__ __launch_bounds__(256) void k_adjust_fill(const float* __restrict__ scale, const float* __restrict__ offset, int64_t n_item,
+                                                     int64_t n_pad, float* __restrict__ adj) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad) return;
+    adj[i] = scale && i < n_item ? scale[i] : 1.0f;
+    adj[n_pad + i] = offset && i < n_item ? offset[i] : 0.0f;
+}
+
+// plane 0 of adj = 1 / ||x_i||, the squared norm by the score chain with the row on both sides; a zero row (and a row
+// whose chain is NaN) gets 0.  sqrtf and the division are the correctly rounded ones (the build has no fast-math flag)
+template <int D, class T>
+__device__ __forceinline__ void adjust_cosine_body(const T* __restrict__ wi, int64_t n_item, int64_t n_pad, float* __restrict__ adj) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad) return;
+    float s = 1.0f;
+    if (i < n_item) {
+        const float n2 = score_chain<D>(wi + i * D, wi + i * D);
+        s = n2 > 0.0f ? 1.0f / sqrtf(n2) : 0.0f;
+    }
+    adj[i] = s;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_adjust_cosine(const float* __restrict__ wi, int64_t n_item, int64_t n_pad, float* __restrict__ adj) {
+    adjust_cosine_body<D>(wi, n_item, n_pad, adj);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_adjust_cosine_h(const _Float16* __restrict__ wi, int64_t n_item, int64_t n_pad,
+                                                         float* __restrict__ adj) {
+    adjust_cosine_body<D>(wi, n_item, n_pad, adj);
 }
 
 // ---- item filter from a list of ids -----------------------------------------------------------------------------------
@@ -906,14 +1094,17 @@ bool sml_retrieval_supports(int d, int elem_bytes) {
 }
 
 hipError_t sml_launch_full_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* rows, int64_t n,
-                                int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int32_t* rank,
-                                hipStream_t st) {
+                                int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                                int32_t* rank, hipStream_t st) {
     hipError_t e = hipMemsetAsync(rank, 0, n * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
     const SliceGrid g = rank_grid(n, kRankWaves, n_item);
     const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kRankWaves);
     if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        if (allow)
+        if (adj)
+            LAUNCH_ADJUSTED(k_full_rank_a, decltype(dd)::value, tu, allow, grid, block, 0, st, tu, ti, n_item, rows, n, n_cols, seen_off,
+                            seen_items, allow, adj, g.slices, g.slice_tiles, rank);
+        else if (allow)
             LAUNCH_TYPED(k_full_rank_f, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, rows, n, n_cols, seen_off, seen_items,
                          allow, g.slices, g.slice_tiles, rank);
         else
@@ -930,8 +1121,8 @@ int64_t sml_topk_scratch_size(int64_t n, int k, int64_t n_item) {
 }
 
 hipError_t sml_launch_topk(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
-                           int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* items,
-                           float* scores, hipStream_t st) {
+                           int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj, void* scratch,
+                           int32_t* items, float* scores, hipStream_t st) {
     const SliceGrid g = topk_grid(n, k, n_item);
     const int slices = g.slices, waves = topk_waves(k);
     float* cs = static_cast<float*>(scratch);
@@ -940,7 +1131,10 @@ hipError_t sml_launch_topk(int d, int elem_bytes, const void* wu, const void* wi
     const dim3 grid((unsigned)(g.groups * slices)), block(64 * waves);
     const size_t lds = (size_t)waves * 2 * k * RT * 4;
     if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        if (allow)
+        if (adj)
+            LAUNCH_ADJUSTED(k_topk_slice_a, decltype(dd)::value, tu, allow, grid, block, lds, st, tu, ti, n_item, users, n, k, seen_off,
+                            seen_items, allow, adj, slices, g.slice_tiles, cs, ci, cn);
+        else if (allow)
             LAUNCH_TYPED(k_topk_slice_f, decltype(dd)::value, tu, grid, block, lds, st, tu, ti, n_item, users, n, k, seen_off, seen_items,
                          allow, slices, g.slice_tiles, cs, ci, cn);
         else
@@ -962,8 +1156,8 @@ int64_t sml_user_rank_scratch_size(int64_t n_pos) { return 10 * ur_piece(n_pos);
 
 hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
                                 const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
-                                const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above, int32_t* pos,
-                                hipStream_t st) {
+                                const int32_t* seen_items, const uint32_t* allow, const float* adj, void* scratch, int32_t* above,
+                                int32_t* pos, hipStream_t st) {
     char* base = static_cast<char*>(scratch);
     const int64_t pc = ur_piece(n_pos);
     int32_t* seg = reinterpret_cast<int32_t*>(base);
@@ -977,7 +1171,10 @@ hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const voi
     if (e != hipSuccess) return e;
     const dim3 eg((unsigned)((n_pos + 255) / 256)), eb(256);
     if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        if (allow)
+        if (adj)
+            LAUNCH_ADJUSTED(k_ur_thresholds_a, decltype(dd)::value, tu, allow, eg, eb, 0, st, tu, ti, n_item, users, n, pos_off, pos_items,
+                            n_pos, seen_off, seen_items, allow, adj, seg, ks[0], ki[0], kx[0], in_seen);
+        else if (allow)
             LAUNCH_TYPED(k_ur_thresholds_f, decltype(dd)::value, tu, eg, eb, 0, st, tu, ti, users, n, pos_off, pos_items, n_pos, seen_off,
                          seen_items, allow, seg, ks[0], ki[0], kx[0], in_seen);
         else
@@ -995,7 +1192,10 @@ hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const voi
     const SliceGrid g = rank_grid(n, kUrWaves, n_item);
     const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kUrWaves);
     if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        if (allow)
+        if (adj)
+            LAUNCH_ADJUSTED(k_ur_count_a, decltype(dd)::value, tu, allow, grid, block, 0, st, tu, ti, n_item, users, n, pos_off, seen_off,
+                            seen_items, allow, adj, g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
+        else if (allow)
             LAUNCH_TYPED(k_ur_count_f, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, users, n, pos_off, seen_off, seen_items,
                          allow, g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
         else
@@ -1022,5 +1222,23 @@ hipError_t sml_launch_item_filter(const int32_t* ids, int64_t n_ids, int64_t n_i
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || n_ids == 0) return e;
     k_filter_from_ids<<<dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, st>>>(ids, n_ids, invert, words);
+    return hipGetLastError();
+}
+
+int64_t sml_item_adjust_pad(int64_t n_item) { return (n_item + RT - 1) / RT * RT; }
+
+hipError_t sml_launch_item_adjust_fill(const float* scale, const float* offset, int64_t n_item, float* adj, hipStream_t st) {
+    const int64_t n_pad = sml_item_adjust_pad(n_item);
+    k_adjust_fill<<<dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st>>>(scale, offset, n_item, n_pad, adj);
+    return hipGetLastError();
+}
+
+hipError_t sml_launch_item_adjust_cosine(int d, int elem_bytes, const void* wi, int64_t n_item, float* adj, hipStream_t st) {
+    const int64_t n_pad = sml_item_adjust_pad(n_item);
+    const dim3 grid((unsigned)((n_pad + 255) / 256)), block(256);
+    if (!with_width(d, elem_bytes, wi, wi, [&](auto dd, auto*, auto* ti) {
+        LAUNCH_TYPED(k_adjust_cosine, decltype(dd)::value, ti, grid, block, 0, st, ti, n_item, n_pad, adj);
+    }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -742,6 +742,61 @@ class HipEngine(object):
                                                 self._stream()), "sml_item_filter_from_ids")
         return words
 
+    def _adjust(self, adjust, item_tab):
+        """adjust=: None (the bare score), or the per-item score terms of sml_*_adjusted: a float32 tensor [2, n_pad] on this
+        device (item_adjust / item_adjust_cosine build one), or a sml_amd.retrieval.ItemScore (resolved against item_tab)."""
+        if adjust is None:
+            return None
+        if not torch.is_tensor(adjust):
+            from .retrieval import ItemScore
+            if not isinstance(adjust, ItemScore):
+                raise ValueError("adjust= is None, an ItemScore or a float32 tensor [2, n_pad], got %s" % type(adjust).__name__)
+            return adjust.device(self, item_tab)
+        n_pad = (item_tab.shape[0] + 31) // 32 * 32
+        if adjust.dtype != torch.float32 or adjust.device != self.device or not adjust.is_contiguous() or tuple(adjust.shape) != (2, n_pad):
+            raise ValueError("expected a contiguous float32 item adjust [2, %d] on %s, got %s %s on %s"
+                             % (n_pad, self.device, adjust.dtype, tuple(adjust.shape), adjust.device))
+        if adjust.data_ptr() % 16:           # the walk reads it with 16-byte loads
+            raise ValueError("the item adjust table must be 16-byte aligned (a view at an odd storage offset is not)")
+        return adjust
+
+    def item_adjust(self, n_item, scale=None, offset=None):
+        """The padded per-item term table float32 [2, n_pad] (plane 0 scale, plane 1 offset; include/sml_hip.h) from optional
+        per-item arrays [n_item]: scale None = 1, offset None = +0.  Built on the device (sml_item_adjust_fill)."""
+        n_item = int(n_item)
+        n_pad = int(self.lib.sml_item_adjust_len(n_item))
+        if n_pad < 0:
+            check(-1, "sml_item_adjust_len")
+        parts = []
+        for name, v in (("scale", scale), ("offset", offset)):
+            if v is not None:
+                v = self._dev(v, torch.float32).reshape(-1)
+                if v.shape[0] != n_item:
+                    raise ValueError("%s must have %d entries, got %d" % (name, n_item, v.shape[0]))
+            parts.append(v)
+        adj = torch.empty(2, n_pad, device=self.device, dtype=torch.float32)
+        check(self.lib.sml_item_adjust_fill(self._ctx, _ptr(parts[0]), _ptr(parts[1]), n_item, _ptr(adj), self._stream()),
+              "sml_item_adjust_fill")
+        return adj
+
+    def item_adjust_cosine(self, item_tab, adj=None):
+        """Write scale[i] = 1 / ||item_tab[i]|| (0 for a zero row) into plane 0 of adj (a new table with offset 0 when adj is
+        None) and return it: ranking by it is ranking by the cosine (sml_item_adjust_cosine; fp32 or fp16 table)."""
+        _, wi, _ = self._retrieval_tables(item_tab, item_tab)
+        adj = self.item_adjust(wi.shape[0]) if adj is None else self._adjust(adj, wi)
+        check(self.lib.sml_item_adjust_cosine(self._ctx, _ptr(wi), wi.element_size(), wi.shape[0], _ptr(adj), self._stream()),
+              "sml_item_adjust_cosine")
+        return adj
+
+    def _retrieval_call(self, base, wi, sfx, allow, adj):
+        """(entry point, its name, what follows w_item, what follows seen_items): adj None -- the entry points without terms,
+        exactly as before; else sml_<base>_adjusted, which takes elem_bytes, and allow (NULL: no filter) and adj."""
+        if adj is None:
+            name = base + ("" if allow is None else "_filtered") + sfx
+            return getattr(self.lib, name), name, (), (() if allow is None else (_ptr(allow),))
+        name = base + "_adjusted"
+        return getattr(self.lib, name), name, (wi.element_size(),), (_ptr(allow), _ptr(adj))
+
     def _retrieval_tables(self, user_tab, item_tab):
         """(user table, item table, entry-point suffix): both fp32 (the sml_* entry points) or both fp16 (sml_*_f16; the
         rows are read as packed halves, no fp32 copy).  Which widths each element type has is the library's answer."""
@@ -753,41 +808,39 @@ class HipEngine(object):
                                  % (self.d, self.device, tuple(t.shape), t.device))
         return user_tab, item_tab, "_f16" if user_tab.dtype == torch.float16 else ""
 
-    def full_rank(self, user_tab, item_tab, rows, seen=None, allow=None):
+    def full_rank(self, user_tab, item_tab, rows, seen=None, allow=None, adjust=None):
         """int32 [n]: per row (u, p, ...) the number of items i != p, not in Seen(u), scoring strictly above p over the
         WHOLE item table (include/sml_hip.h, sml_full_rank / sml_full_rank_f16: fp32 or fp16 tables).
         seen = (seen_off int64 [n_user + 1], seen_items int32).  allow: an item filter (_allow); the count then runs over
-        the allowed items only (sml_full_rank_filtered)."""
+        the allowed items only (sml_full_rank_filtered).  adjust: per-item score terms (_adjust); the rank is then by
+        A(u, i) = fmaf(S(u, i), scale[i], offset[i]) (sml_full_rank_adjusted)."""
         wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
         allow = self._allow(allow, wi.shape[0])
-        name = "sml_full_rank" + ("" if allow is None else "_filtered") + sfx
-        call = getattr(self.lib, name)
-        flt = () if allow is None else (_ptr(allow),)
+        call, name, eb, flt = self._retrieval_call("sml_full_rank", wi, sfx, allow, self._adjust(adjust, wi))
         rows = self._dev(rows, torch.int64)
         n, c = rows.shape
         rank = torch.empty(n, device=self.device, dtype=torch.int32)
         if n == 0:
             return rank
         off, items = self._seen(seen)
-        check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(rows), n, c, _ptr(off), _ptr(items), *flt, _ptr(rank),
+        check(call(self._ctx, _ptr(wu), _ptr(wi), *eb, wi.shape[0], _ptr(rows), n, c, _ptr(off), _ptr(items), *flt, _ptr(rank),
                    self._stream()), name)
         return rank
 
-    def topk_items(self, user_tab, item_tab, users, k, seen=None, allow=None):
+    def topk_items(self, user_tab, item_tab, users, k, seen=None, allow=None, adjust=None):
         """(int64 items [n, k], float32 scores [n, k]): each user's k best items not in Seen(u), score descending then id
         ascending; missing slots are (-1, -inf) (include/sml_hip.h, sml_topk_items / sml_topk_items_f16: fp32 or fp16 tables).
-        allow: an item filter (_allow); only allowed items enter the lists (sml_topk_items_filtered)."""
+        allow: an item filter (_allow); only allowed items enter the lists (sml_topk_items_filtered).  adjust: per-item score
+        terms (_adjust); order and returned scores are then A(u, i) (sml_topk_items_adjusted)."""
         wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
         allow = self._allow(allow, wi.shape[0])
-        name = "sml_topk_items" + ("" if allow is None else "_filtered") + sfx
-        call = getattr(self.lib, name)
-        flt = () if allow is None else (_ptr(allow),)
+        call, name, eb, flt = self._retrieval_call("sml_topk_items", wi, sfx, allow, self._adjust(adjust, wi))
         users = self._dev(users, torch.int64).reshape(-1)
         n, k = users.shape[0], int(k)
         off, seen_items = self._seen(seen)
         total = int(self.lib.sml_topk_scratch_bytes(self._ctx, n, k, wi.shape[0]))
         if total < 0 or n == 0:          # argument checks (k, n_item) and the empty call go through the library
-            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users), 0, k, _ptr(off), _ptr(seen_items), *flt, None, None, None,
+            check(call(self._ctx, _ptr(wu), _ptr(wi), *eb, wi.shape[0], _ptr(users), 0, k, _ptr(off), _ptr(seen_items), *flt, None, None, None,
                        self._stream()), name)
         items = torch.empty(n, k, device=self.device, dtype=torch.int32)
         scores = torch.empty(n, k, device=self.device, dtype=torch.float32)
@@ -798,23 +851,22 @@ class HipEngine(object):
             nbytes = int(self.lib.sml_topk_scratch_bytes(self._ctx, m, k, wi.shape[0]))
             if scratch is None or scratch.numel() < nbytes:
                 scratch = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
-            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, k, _ptr(off), _ptr(seen_items), *flt,
+            check(call(self._ctx, _ptr(wu), _ptr(wi), *eb, wi.shape[0], _ptr(users[c0:]), m, k, _ptr(off), _ptr(seen_items), *flt,
                        _ptr(scratch), _ptr(items[c0:]), _ptr(scores[c0:]), self._stream()), name)
         return items.long(), scores
 
     USER_RANK_SCRATCH_BYTES = 256 << 20  # held-out items of one sml_user_rank call are capped so its scratch fits this
 
-    def user_ranks(self, user_tab, item_tab, users, pos_off, pos_items, seen=None, ks=(20,), allow=None):
+    def user_ranks(self, user_tab, item_tab, users, pos_off, pos_items, seen=None, ks=(20,), allow=None, adjust=None):
         """Every user's held-out items ranked against the whole catalogue, and per-user metrics at each K in `ks`
         (include/sml_hip.h, sml_user_rank / sml_user_rank_f16 / sml_user_metrics: fp32 or fp16 tables).  users int64 [n]; pos_off int64 [n + 1] and pos_items
         int32 [n_pos]: users[x]'s held-out items, ascending and unique in [pos_off[x], pos_off[x + 1]).  Returns a dict:
         above, pos int32 [n_pos]; hits int32, dcg, ap float32 [n, len(ks)]; first int32 [n].  allow: an item filter (_allow);
-        only allowed items are eligible, and a held-out item that is not allowed has pos -1 (sml_user_rank_filtered)."""
+        only allowed items are eligible, and a held-out item that is not allowed has pos -1 (sml_user_rank_filtered).
+        adjust: per-item score terms (_adjust); above, pos and the metrics are then by A(u, i) (sml_user_rank_adjusted)."""
         wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
         allow = self._allow(allow, wi.shape[0])
-        name = "sml_user_rank" + ("" if allow is None else "_filtered") + sfx
-        call = getattr(self.lib, name)
-        flt = () if allow is None else (_ptr(allow),)
+        call, name, eb, flt = self._retrieval_call("sml_user_rank", wi, sfx, allow, self._adjust(adjust, wi))
         users = self._dev(users, torch.int64).reshape(-1)
         off_h = np.asarray(pos_off.cpu() if torch.is_tensor(pos_off) else pos_off, dtype=np.int64).reshape(-1)
         pos_items = self._dev(pos_items, torch.int32).reshape(-1)
@@ -832,7 +884,7 @@ class HipEngine(object):
                    ap=torch.empty(n, n_k, device=self.device, dtype=torch.float32),
                    first=torch.empty(n, device=self.device, dtype=torch.int32))
         if n == 0 or n_pos == 0:         # argument checks (d, n_item, Seen, ks) go through the library
-            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], None, 0, None, None, 0, _ptr(off), _ptr(seen_items), *flt, None, None,
+            check(call(self._ctx, _ptr(wu), _ptr(wi), *eb, wi.shape[0], None, 0, None, None, 0, _ptr(off), _ptr(seen_items), *flt, None, None,
                        None, self._stream()), name)
             check(self.lib.sml_user_metrics(self._ctx, None, None, 0, ks_p, n_k, None, None, None, None, self._stream()),
                   "sml_user_metrics")
@@ -857,7 +909,7 @@ class HipEngine(object):
                 check(-1, "sml_user_rank_scratch_bytes")
             if scratch is None or scratch.numel() < nbytes:
                 scratch = torch.empty(max(nbytes, 1), device=self.device, dtype=torch.uint8)
-            check(call(self._ctx, _ptr(wu), _ptr(wi), wi.shape[0], _ptr(users[c0:]), m, _ptr(sub_off), _ptr(pos_items[e0:]), e1 - e0,
+            check(call(self._ctx, _ptr(wu), _ptr(wi), *eb, wi.shape[0], _ptr(users[c0:]), m, _ptr(sub_off), _ptr(pos_items[e0:]), e1 - e0,
                        _ptr(off), _ptr(seen_items), *flt, _ptr(scratch), _ptr(out["above"][e0:]), _ptr(out["pos"][e0:]),
                        self._stream()), name)
             # a chunk of empty sets reads no pos; it still passes a valid pointer (an empty slice's may be null)

@@ -56,12 +56,13 @@ def test_model(model, test_set, old_user=None, old_item=None, topK=10, need_pbar
     return hits / num_test, torch.tensor(np.float32(ndcg / num_test))
 
 
-def test_model_full(model, test_set, seen=None, topK=10, items=None):
+def test_model_full(model, test_set, seen=None, topK=10, items=None, score=None):
     """(recall@topK, ndcg@topK) as test_model returns them, with every positive ranked against the whole catalogue
     (MFbasemode.test_full), leaving out `seen` (a sml_amd.retrieval.SeenItems or a (seen_off, seen_items) CSR).
     test_set: a DeviceRows, an array / tensor [n, >= 2], or an iterable of such batches.  Unlike test_model this
     makes no DataLoader-emulating RNG draw: the run's random streams stay where they were.  items: rank inside a subset
-    of the catalogue (a sml_amd.retrieval.ItemFilter, a bool mask or filter words, as MFbasemode.recommend takes)."""
+    of the catalogue (a sml_amd.retrieval.ItemFilter, a bool mask or filter words, as MFbasemode.recommend takes).  score:
+    rank by an adjusted score ("bias", "cosine", an ItemScore ..., as MFbasemode.recommend takes); None is the bare dot."""
     model.eval()
     device = model.user_laten.weight.device
     if isinstance(test_set, DeviceRows):
@@ -74,10 +75,10 @@ def test_model_full(model, test_set, seen=None, topK=10, items=None):
     num_test = 0
     hits = 0.0
     ndcg = 0.0
+    extra = dict(([("items", items)] if items is not None else []) + ([("score", score)] if score is not None else []))
     for datas in batches:
         datas = torch.as_tensor(datas).long().to(device)
-        batch_hit, batch_ndcg, _ = model.test_full(datas, topK=topK, exclude=seen) if items is None else \
-            model.test_full(datas, topK=topK, exclude=seen, items=items)
+        batch_hit, batch_ndcg, _ = model.test_full(datas, topK=topK, exclude=seen, **extra)
         hits += batch_hit
         ndcg += float(batch_ndcg)
         num_test += datas.shape[0]
@@ -131,15 +132,15 @@ def user_metrics(out, old_user=None, old_item=None):
     return res
 
 
-def test_model_users(model, test_pairs, seen=None, topK=(20, 10, 5), old_user=None, old_item=None, items=None):
+def test_model_users(model, test_pairs, seen=None, topK=(20, 10, 5), old_user=None, old_item=None, items=None, score=None):
     """All-ranking evaluation of a test period: every user's whole held-out set T(u) (the distinct (user, item) pairs of
     test_pairs [n, >= 2]; further columns are ignored) placed in the user's ranked list over the entire catalogue minus
     `seen` (MFbasemode.test_users), then Recall / Precision / NDCG / MAP / MRR @K averaged over the users with m > 0
     (user_metrics).  Makes no RNG draw.  items: rank inside a subset of the catalogue (as test_model_full); held-out items
-    outside it never hit."""
+    outside it never hit.  score: rank by an adjusted score (as test_model_full)."""
     from .retrieval import held_out
     model.eval()
     sets = held_out(test_pairs, model.user_num, model.item_num)
-    out = model.test_users(sets, topK=topK, exclude=seen) if items is None else \
-        model.test_users(sets, topK=topK, exclude=seen, items=items)
+    extra = dict(([("items", items)] if items is not None else []) + ([("score", score)] if score is not None else []))
+    out = model.test_users(sets, topK=topK, exclude=seen, **extra)
     return user_metrics(out, old_user, old_item)

@@ -69,45 +69,73 @@ class MFbasemode(nn.Module):
         hit_rows = (ranks < topK).nonzero()[:, 0]
         return hit_rows, ranks, hits * 1.0, (torch.tensor(ndcg) if hits > 0 else 0)
 
-    def recommend(self, users, topK=20, exclude=None, items=None):
+    def recommend(self, users, topK=20, exclude=None, items=None, score=None):
         """(items int64 [n, topK], scores float32 [n, topK]): each user's topK items over the whole catalogue by the score
         test() uses (no bias terms), score descending then item id ascending, leaving out `exclude` (a
         sml_amd.retrieval.SeenItems or a (seen_off, seen_items) CSR); missing slots are (-1, -inf).  items: restrict the
-        lists to a subset of the catalogue (a sml_amd.retrieval.ItemFilter, a bool mask [item_num] or int32 filter words)."""
-        from .retrieval import as_csr, as_filter
+        lists to a subset of the catalogue (a sml_amd.retrieval.ItemFilter, a bool mask [item_num] or int32 filter words).
+        score: rank by A(u, i) = fmaf(S(u, i), scale[i], offset[i]) instead (sml_amd.retrieval.as_score): "bias" adds
+        item_bais, "cosine" divides by the item row's norm, an ItemScore gives any per-item terms; None / "dot" is the bare
+        dot product.  The returned scores are A."""
+        from .retrieval import as_csr, as_filter, as_score
         eng = _engine_for(self)
         w = self.user_laten.weight
         return eng.topk_items(w.data, self.item_laten.weight.data, users, topK, as_csr(exclude, w.device),
-                              as_filter(items, self.item_laten.weight.shape[0], w.device))
+                              as_filter(items, self.item_laten.weight.shape[0], w.device), as_score(score, self))
 
-    def test_full(self, inputs_data, topK=20, exclude=None, items=None):
+    def similar_items(self, items, topK=20, metric="cosine", among=None, exclude_self=True):
+        """(int64 [n, topK], float32 [n, topK]): for each query item its topK most similar items of the catalogue, the item
+        table serving as both tables (score descending, then id ascending; missing slots (-1, -inf)).  metric="dot": the
+        bare dot product <x_q, x_i>.  metric="cosine": the order is the kernel's A(q, i) = <x_q, x_i> / ||x_i|| (the query's
+        norm cannot reorder its own list); the returned score is A * (1 / ||x_q||), one more fp32 rounding done in torch, so
+        it is the cosine up to three roundings, not a correctly rounded one.  among: an item filter (as recommend's items=)
+        on the returned items; exclude_self: leave the query out of its own list.  Every cosine call rebuilds the norm table
+        of the whole catalogue from the current weights (one pass over the item table, never stale): batch small query sets
+        into one call rather than paying it per query."""
+        from .retrieval import as_filter, self_seen
+        eng = _engine_for(self)
+        w = self.item_laten.weight.data
+        q = torch.as_tensor(items).to(w.device).long().reshape(-1)
+        seen = self_seen(w.shape[0], w.device) if exclude_self else None
+        allow = as_filter(among, w.shape[0], w.device)
+        if metric == "dot":
+            return eng.topk_items(w, w, q, topK, seen, allow)
+        if metric != "cosine":
+            raise ValueError('metric is "cosine" or "dot", got %r' % (metric,))
+        adj = eng.item_adjust_cosine(w)
+        it, sc = eng.topk_items(w, w, q, topK, seen, allow, adjust=adj)
+        return it, torch.where(it >= 0, sc * adj[0, q].unsqueeze(1), sc)
+
+    def test_full(self, inputs_data, topK=20, exclude=None, items=None, score=None):
         """test() with the positive ranked against the WHOLE catalogue: inputs_data [n, >= 2] (user, positive, ... --
         further columns are ignored), rank = #{items != positive, not excluded, scoring strictly above it}.
         Returns (hits, ndcg_sum, indices of the rows that hit).  items (as in recommend): the positive is ranked among
-        the allowed items only; a positive outside the subset still gets its rank among them."""
-        from .retrieval import as_csr, as_filter
+        the allowed items only; a positive outside the subset still gets its rank among them.  score (as in recommend):
+        rank by the adjusted score."""
+        from .retrieval import as_csr, as_filter, as_score
         eng = _engine_for(self)
         w = self.user_laten.weight
         ranks = eng.full_rank(w.data, self.item_laten.weight.data, inputs_data, as_csr(exclude, w.device),
-                              as_filter(items, self.item_laten.weight.shape[0], w.device))
+                              as_filter(items, self.item_laten.weight.shape[0], w.device), as_score(score, self))
         hits, ndcg = eng.eval_metrics(ranks, topK)
         hit_rows = (ranks < topK).nonzero()[:, 0]
         batch_ndcg = torch.tensor(ndcg) if hits > 0 else 0
         return hits * 1.0, batch_ndcg, hit_rows
 
-    def test_users(self, held_out, topK=(20, 10, 5), exclude=None, items=None):
+    def test_users(self, held_out, topK=(20, 10, 5), exclude=None, items=None, score=None):
         """Every user's whole held-out set ranked against the WHOLE catalogue at once (HipEngine.user_ranks), by the score
         test() uses.  held_out: a sml_amd.retrieval.SeenItems (retrieval.held_out) or a (off, items) CSR over all users;
         exclude as in recommend().  Returns a dict: users, pos_off, pos_items (the users with at least one held-out item
         and their items, sml_amd.retrieval.nonempty_users), ks, and the engine's above / pos / hits / dcg / ap / first.
-        items (as in recommend): only the allowed items are ranked; a held-out item outside the subset has pos -1."""
-        from .retrieval import as_csr, as_filter, nonempty_users
+        items (as in recommend): only the allowed items are ranked; a held-out item outside the subset has pos -1.
+        score (as in recommend): rank by the adjusted score."""
+        from .retrieval import as_csr, as_filter, as_score, nonempty_users
         eng = _engine_for(self)
         w = self.user_laten.weight
         users, pos_off, pos_items = nonempty_users(held_out)
         ks = tuple(int(k) for k in (topK if hasattr(topK, "__len__") else (topK,)))
         out = eng.user_ranks(w.data, self.item_laten.weight.data, users, pos_off, pos_items, as_csr(exclude, w.device), ks,
-                             as_filter(items, self.item_laten.weight.shape[0], w.device))
+                             as_filter(items, self.item_laten.weight.shape[0], w.device), as_score(score, self))
         out.update(users=users, pos_off=pos_off, pos_items=pos_items, ks=ks)
         return out
 
@@ -159,7 +187,12 @@ class _MF2Train(torch.autograd.Function):
 class MF2(MFbasemode):
     """model/MF.py:118-156.  Test branch: the dot product plus both biases.  Training branch (`neg_item` given): the
     reference's (bpr_loss, l2loss) pair, differentiable w.r.t. the four embedding tables (`_MF2Train`).  Nothing in the
-    reference calls this class; the bare BPR step at table scale is HipEngine.bare_epoch(bce=False)."""
+    reference calls this class; the bare BPR step at table scale is HipEngine.bare_epoch(bce=False).
+
+    Retrieval: recommend / test_full / test_users rank by the bare dot product unless told otherwise, as they do for
+    MFbasemode.  score="bias" is the order of this class's own test-branch score: the user bias is constant per user and
+    cannot reorder a user's list, the item bias can.  The scores returned then are fmaf(dot, 1, item bias) -- they leave out
+    the user bias and are rounded once, so they are not bit-equal to forward's three-term sum."""
 
     def forward(self, user, item, neg_item=None):
         if neg_item is not None:

@@ -15,6 +15,12 @@ ItemFilter restricts a call to a subset of the catalogue, for every user alike: 
 
 (bits at positions >= n_item of the last word are ignored by the kernels; ItemFilter keeps them 0).  A filtered call
 returns what the unfiltered call returns with the complement of the filter added to every user's Seen range.
+
+ItemScore describes per-item score terms: a call given one ranks by A(u, i) = fmaf(S(u, i), scale[i], offset[i]) instead of
+the bare dot product S (include/sml_hip.h, the sml_*_adjusted entry points) -- an item bias is an offset, the cosine a scale.
+On the device the terms are one padded table,
+
+    adj  float32 [2, n_pad], n_pad = 32 * ceil(n_item / 32): plane 0 scale, plane 1 offset (pad entries are ignored)
 """
 import os
 
@@ -195,3 +201,128 @@ def as_filter(x, n_item, device):
     if m.dtype != np.bool_ or m.shape != (int(n_item),):
         raise ValueError("an item filter is None, an ItemFilter, a bool mask [n_item] or int32 words, got %s %s" % (m.dtype, m.shape))
     return ItemFilter.from_mask(m).device(device)
+
+
+def adjust_len(n_item):
+    """n_pad: the floats of one plane of the padded term table of n_item items."""
+    return (int(n_item) + 31) // 32 * 32
+
+
+class ItemScore(object):
+    """Per-item score terms of a retrieval call, described on the host with numpy: A(u, i) = fmaf(S(u, i), scale[i],
+    offset[i]) (include/sml_hip.h).  A new ItemScore is neutral (scale 1, offset +0).  scale / offset / bias / cosine edit it
+    and return it; any float may be given: an offset of -inf sends an item to the end of every list, a NaN removes it."""
+
+    def __init__(self, n_item):
+        self.n_item = int(n_item)
+        if self.n_item <= 0:
+            raise ValueError("n_item must be positive, got %d" % self.n_item)
+        self._scale = None               # None: 1 everywhere
+        self._offset = None              # None: +0 everywhere
+        self._cosine = False
+        self._dev = {}
+
+    def _values(self, values, what, column=False):
+        v = np.asarray(values.detach().cpu() if torch.is_tensor(values) else values)
+        if v.dtype.kind not in "fiu":
+            raise ValueError("%s must be numbers, got %s" % (what, v.dtype))
+        if column and v.shape == (self.n_item, 1):
+            v = v[:, 0]
+        if v.shape != (self.n_item,):
+            raise ValueError("%s must have shape [%d]%s, got %s" % (what, self.n_item, " or [%d, 1]" % self.n_item if column else "",
+                                                                    v.shape))
+        return np.ascontiguousarray(v, dtype=np.float32)
+
+    def scale(self, values):
+        """scale[i] = values[i], float [n_item] (replaces an earlier scale or cosine())."""
+        self._scale, self._cosine, self._dev = self._values(values, "scale"), False, {}
+        return self
+
+    def offset(self, values):
+        """offset[i] = values[i], float [n_item]."""
+        self._offset, self._dev = self._values(values, "offset"), {}
+        return self
+
+    def bias(self, item_bias):
+        """An item bias as the offset: [n_item], or the [n_item, 1] weight of a bias embedding (MFbasemode.item_bais)."""
+        self._offset, self._dev = self._values(item_bias, "item_bias", column=True), {}
+        return self
+
+    def cosine(self):
+        """scale[i] = 1 / ||x_i||, resolved against the item table a call is made with (replaces an earlier scale)."""
+        self._scale, self._cosine, self._dev = None, True, {}
+        return self
+
+    @property
+    def is_cosine(self):
+        return self._cosine
+
+    def padded_len(self):
+        return adjust_len(self.n_item)
+
+    def host(self):
+        """float32 [2, n_pad]: the table with pads (1, 0).  A cosine() score has no host form: its scale needs the table."""
+        if self._cosine:
+            raise ValueError("a cosine ItemScore is resolved on the device against an item table (ItemScore.device)")
+        adj = np.zeros((2, self.padded_len()), np.float32)
+        adj[0] = 1.0
+        if self._scale is not None:
+            adj[0, :self.n_item] = self._scale
+        if self._offset is not None:
+            adj[1, :self.n_item] = self._offset
+        return adj
+
+    def device(self, engine, item_tab=None):
+        """The float32 [2, n_pad] table on the engine's device.  Fixed terms are cached and rebuilt only after an edit.  A
+        cosine() score is built from item_tab at EVERY call (one small launch over the table) and never cached: training
+        writes the tables in place through raw pointers, which no version counter or address records, so a cached norm
+        could be stale."""
+        if self._cosine:
+            if item_tab is None or item_tab.shape[0] != self.n_item:
+                raise ValueError("a cosine ItemScore over %d items needs the item table [%d, d]" % (self.n_item, self.n_item))
+            return engine.item_adjust_cosine(item_tab, engine.item_adjust(self.n_item, None, self._offset))
+        # (the engine's calls always pass their item table; a table built without one is still shape-checked by the call
+        # it is handed to)
+        if item_tab is not None and item_tab.shape[0] != self.n_item:
+            raise ValueError("the score terms are over %d items, the catalogue has %d" % (self.n_item, item_tab.shape[0]))
+        key = str(engine.device)
+        if key not in self._dev:
+            self._dev[key] = engine.item_adjust(self.n_item, self._scale, self._offset)
+        return self._dev[key]
+
+
+def as_score(x, model):
+    """x: None or "dot" (the bare dot product), "cosine" (S / ||x_i||, the model's item table), "bias" (S + the model's item
+    bias, MFbasemode.item_bais), an ItemScore, or a ready float32 [2, n_pad] table -> what the engine's retrieval calls take as
+    adjust= (None: no terms).  "cosine" and "bias" are built on the device from the model's current weights at every call
+    (one small launch), so they are never stale."""
+    if x is None or (isinstance(x, str) and x == "dot"):
+        return None
+    if isinstance(x, ItemScore):
+        if x.n_item != model.item_laten.weight.shape[0]:
+            raise ValueError("the score terms are over %d items, the catalogue has %d" % (x.n_item, model.item_laten.weight.shape[0]))
+        return x
+    if torch.is_tensor(x):
+        return x
+    if isinstance(x, str) and x in ("cosine", "bias"):
+        from .mf import _engine_for
+        eng = _engine_for(model)
+        if x == "cosine":
+            return eng.item_adjust_cosine(model.item_laten.weight.data)
+        return eng.item_adjust(model.item_laten.weight.shape[0], offset=model.item_bais.weight.data[:, 0].float())
+    raise ValueError('score= is None, "dot", "cosine", "bias", an ItemScore or a float32 [2, n_pad] table, got %r' % (x,))
+
+
+_SELF_SEEN = {}
+
+
+def self_seen(n_item, device):
+    """The Seen CSR over ITEM ids that excludes every item from its own list (off = arange(n_item + 1), items =
+    arange(n_item)), built on the device: similar_items' self-exclusion.  One is kept per device, for the catalogue size
+    asked for last (12 bytes per item), so a catalogue that grows from period to period does not pile them up."""
+    key = str(torch.device(device))
+    hit = _SELF_SEEN.get(key)
+    if hit is None or hit[0] != int(n_item):
+        hit = _SELF_SEEN[key] = (int(n_item), (torch.arange(n_item + 1, device=device, dtype=torch.int64),
+                                              torch.arange(n_item, device=device, dtype=torch.int32)))
+    return hit[1]
