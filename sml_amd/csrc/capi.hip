@@ -1789,48 +1789,56 @@ int sml_eval_metrics(sml_ctx* ctx, const int32_t* rank, int64_t n, int topk, flo
 
 // ---- full-catalogue retrieval (retrieval.hip) ----------------------------------------------------------------------
 
-// elem_bytes: 4 for the fp32 entry points (d = 32 / 64), 2 for the _f16 ones (d = 32 / 64 / 128)
-static bool retrieval_args_ok(sml_ctx* ctx, int elem_bytes, int64_t n_item, const int64_t* seen_off, const int32_t* seen_items) {
-    return ctx && sml_retrieval_supports(ctx->d, elem_bytes) && n_item > 0 && n_item < ((int64_t)1 << 31) && (!seen_off) == (!seen_items);
+static bool elem_ok(int elem_bytes) { return elem_bytes == 4 || elem_bytes == 2; }
+
+// Every table-reading entry point fills a catalogue (sml_kernels.h) and makes one call.  elem_bytes: 4 for the fp32 entry points
+// (d = 32 / 64), 2 for the _f16 ones (d = 32 / 64 / 128), the caller's for the _adjusted ones; allow / adj: NULL where the form
+// has none.  The refusals they share, in order: with_adj (the _adjusted forms: adj is required) a bad elem_bytes, a null or
+// misaligned adj; then the common arguments and the operation's own ranges (own_ok; `ranges` names them all).  c.d: the context's
+static int catalogue_ok(const char* what, sml_ctx* ctx, SmlCatalogue& c, bool with_adj, bool own_ok, const char* ranges) {
+    if (with_adj && !elem_ok(c.elem_bytes)) return fail(SML_EINVAL, what, "bad argument (elem_bytes must be 4 or 2)");
+    if (with_adj && (!c.adj || ((uintptr_t)c.adj & 15))) return fail(SML_EINVAL, what, "adj must be non-null and 16-byte aligned");
+    if (!ctx || !sml_retrieval_supports(ctx->d, c.elem_bytes) || c.n_item <= 0 || c.n_item >= ((int64_t)1 << 31) ||
+        (!c.seen_off) != (!c.seen_items) || !own_ok)
+        return fail(SML_EINVAL, what, ranges);
+    c.d = ctx->d;
+    return SML_OK;
 }
 
-// every table-reading entry point exists four times over one body: `what` names the caller, elem_bytes its tables, allow
-// the item filter of the _filtered forms (NULL: none, which is what the unfiltered entry points pass).  The _adjusted entry
-// points are a fifth caller: adj is their per-item term table (NULL everywhere else), with_adj says that one is required
-static int full_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
-                          const int64_t* rows, int64_t n, int n_cols, const int64_t* seen_off, const int32_t* seen_items,
-                          const uint32_t* allow, int32_t* rank, void* stream, const float* adj = nullptr, bool with_adj = false) {
-    if (with_adj && (!adj || ((uintptr_t)adj & 15))) return fail(SML_EINVAL, what, "adj must be non-null and 16-byte aligned");
-    if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || n_cols < 2 || n < 0)
-        return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, n_cols >= 2, seen_off and seen_items both or neither)");
+static int full_rank_impl(const char* what, sml_ctx* ctx, SmlCatalogue c, bool with_adj, const int64_t* rows, int64_t n, int n_cols,
+                          int32_t* rank, void* stream) {
+    if (int rc = catalogue_ok(what, ctx, c, with_adj, n_cols >= 2 && n >= 0,
+                              "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, n_cols >= 2, seen_off and seen_items both or neither)"))
+        return rc;
     if (n == 0) return SML_OK;
-    if (!w_user || !w_item || !rows || !rank) return fail(SML_EINVAL, what, "null argument");
+    if (!c.wu || !c.wi || !rows || !rank) return fail(SML_EINVAL, what, "null argument");
     DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
-    PROFILED(PC_MISC, HIPCHK(sml_launch_full_rank(ctx->d, elem_bytes, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, adj, rank, st)));
+    PROFILED(PC_MISC, HIPCHK(sml_launch_full_rank(c, rows, n, n_cols, rank, st)));
     return SML_OK;
 }
 
 int sml_full_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* rows, int64_t n,
                   int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, void* stream) {
-    return full_rank_impl("sml_full_rank", 4, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, nullptr, rank, stream);
+    return full_rank_impl("sml_full_rank", ctx, {0, 4, w_user, w_item, n_item, seen_off, seen_items}, false, rows, n, n_cols, rank, stream);
 }
 
 int sml_full_rank_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* rows, int64_t n,
                       int n_cols, const int64_t* seen_off, const int32_t* seen_items, int32_t* rank, void* stream) {
-    return full_rank_impl("sml_full_rank_f16", 2, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, nullptr, rank, stream);
+    return full_rank_impl("sml_full_rank_f16", ctx, {0, 2, w_user, w_item, n_item, seen_off, seen_items}, false, rows, n, n_cols, rank, stream);
 }
 
 int sml_full_rank_filtered(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* rows, int64_t n,
                            int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int32_t* rank,
                            void* stream) {
-    return full_rank_impl("sml_full_rank_filtered", 4, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, rank, stream);
+    return full_rank_impl("sml_full_rank_filtered", ctx, {0, 4, w_user, w_item, n_item, seen_off, seen_items, allow}, false, rows, n, n_cols, rank,
+                          stream);
 }
 
 int sml_full_rank_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* rows, int64_t n,
                                int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int32_t* rank,
                                void* stream) {
-    return full_rank_impl("sml_full_rank_filtered_f16", 2, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, rank,
-                          stream);
+    return full_rank_impl("sml_full_rank_filtered_f16", ctx, {0, 2, w_user, w_item, n_item, seen_off, seen_items, allow}, false, rows, n, n_cols,
+                          rank, stream);
 }
 
 int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item) {
@@ -1838,44 +1846,42 @@ int64_t sml_topk_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item) {
     return n == 0 ? 0 : sml_topk_scratch_size(n, k, n_item);
 }
 
-static int topk_items_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
-                           const int64_t* users, int64_t n, int k, const int64_t* seen_off, const int32_t* seen_items,
-                           const uint32_t* allow, void* scratch, int32_t* items, float* scores, void* stream, const float* adj = nullptr,
-                           bool with_adj = false) {
-    if (with_adj && (!adj || ((uintptr_t)adj & 15))) return fail(SML_EINVAL, what, "adj must be non-null and 16-byte aligned");
-    if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || k < 1 || k > 128 || n < 0)
-        return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 1 <= k <= 128, 0 < n_item < 2^31, seen_off and seen_items both or neither)");
+static int topk_items_impl(const char* what, sml_ctx* ctx, SmlCatalogue c, bool with_adj, const int64_t* users, int64_t n, int k,
+                           void* scratch, int32_t* items, float* scores, void* stream) {
+    if (int rc = catalogue_ok(what, ctx, c, with_adj, k >= 1 && k <= 128 && n >= 0,
+                              "bad argument (d must be 32/64, or 128 for fp16 tables; 1 <= k <= 128, 0 < n_item < 2^31, seen_off and seen_items both or neither)"))
+        return rc;
     if (n == 0) return SML_OK;
-    if (!w_user || !w_item || !users || !scratch || !items || !scores) return fail(SML_EINVAL, what, "null argument");
+    if (!c.wu || !c.wi || !users || !scratch || !items || !scores) return fail(SML_EINVAL, what, "null argument");
     DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
-    PROFILED(PC_MISC, HIPCHK(sml_launch_topk(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, adj, scratch, items, scores, st)));
+    PROFILED(PC_MISC, HIPCHK(sml_launch_topk(c, users, n, k, scratch, items, scores, st)));
     return SML_OK;
 }
 
 int sml_topk_items(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
                    const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores, void* stream) {
-    return topk_items_impl("sml_topk_items", 4, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, nullptr, scratch, items, scores,
+    return topk_items_impl("sml_topk_items", ctx, {0, 4, w_user, w_item, n_item, seen_off, seen_items}, false, users, n, k, scratch, items, scores,
                            stream);
 }
 
 int sml_topk_items_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
                        const int64_t* seen_off, const int32_t* seen_items, void* scratch, int32_t* items, float* scores, void* stream) {
-    return topk_items_impl("sml_topk_items_f16", 2, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, nullptr, scratch, items,
+    return topk_items_impl("sml_topk_items_f16", ctx, {0, 2, w_user, w_item, n_item, seen_off, seen_items}, false, users, n, k, scratch, items,
                            scores, stream);
 }
 
 int sml_topk_items_filtered(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
                             const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* items,
                             float* scores, void* stream) {
-    return topk_items_impl("sml_topk_items_filtered", 4, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, scratch, items,
-                           scores, stream);
+    return topk_items_impl("sml_topk_items_filtered", ctx, {0, 4, w_user, w_item, n_item, seen_off, seen_items, allow}, false, users, n, k, scratch,
+                           items, scores, stream);
 }
 
 int sml_topk_items_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n, int k,
                                 const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* items,
                                 float* scores, void* stream) {
-    return topk_items_impl("sml_topk_items_filtered_f16", 2, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, scratch,
-                           items, scores, stream);
+    return topk_items_impl("sml_topk_items_filtered_f16", ctx, {0, 2, w_user, w_item, n_item, seen_off, seen_items, allow}, false, users, n, k,
+                           scratch, items, scores, stream);
 }
 
 int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int64_t n_item) {
@@ -1885,78 +1891,70 @@ int64_t sml_user_rank_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t n_pos, int6
     return n == 0 || n_pos == 0 ? 0 : sml_user_rank_scratch_size(n_pos);
 }
 
-static int user_rank_impl(const char* what, int elem_bytes, sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item,
-                          const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
-                          const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above,
-                          int32_t* pos, void* stream, const float* adj = nullptr, bool with_adj = false) {
-    if (with_adj && (!adj || ((uintptr_t)adj & 15))) return fail(SML_EINVAL, what, "adj must be non-null and 16-byte aligned");
-    if (!retrieval_args_ok(ctx, elem_bytes, n_item, seen_off, seen_items) || n < 0 || n >= ((int64_t)1 << 31) || n_pos < 0 ||
-        n_pos >= ((int64_t)1 << 31))
-        return fail(SML_EINVAL, what, "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, 0 <= n, n_pos < 2^31, seen_off and seen_items both or neither)");
+static int user_rank_impl(const char* what, sml_ctx* ctx, SmlCatalogue c, bool with_adj, const int64_t* users, int64_t n,
+                          const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, void* scratch, int32_t* above, int32_t* pos,
+                          void* stream) {
+    if (int rc = catalogue_ok(what, ctx, c, with_adj, n >= 0 && n < ((int64_t)1 << 31) && n_pos >= 0 && n_pos < ((int64_t)1 << 31),
+                              "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, 0 <= n, n_pos < 2^31, seen_off and seen_items both or neither)"))
+        return rc;
     if (n == 0 || n_pos == 0) return SML_OK;
-    if (!w_user || !w_item || !users || !pos_off || !pos_items || !scratch || !above || !pos)
+    if (!c.wu || !c.wi || !users || !pos_off || !pos_items || !scratch || !above || !pos)
         return fail(SML_EINVAL, what, "null argument");
     DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
-    PROFILED(PC_MISC, HIPCHK(sml_launch_user_rank(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
-                                               seen_items, allow, adj, scratch, above, pos, st)));
+    PROFILED(PC_MISC, HIPCHK(sml_launch_user_rank(c, users, n, pos_off, pos_items, n_pos, scratch, above, pos, st)));
     return SML_OK;
 }
 
 int sml_user_rank(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n,
                   const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                   const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, void* stream) {
-    return user_rank_impl("sml_user_rank", 4, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off, seen_items,
-                          nullptr, scratch, above, pos, stream);
+    return user_rank_impl("sml_user_rank", ctx, {0, 4, w_user, w_item, n_item, seen_off, seen_items}, false, users, n, pos_off, pos_items, n_pos,
+                          scratch, above, pos, stream);
 }
 
 int sml_user_rank_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,
                       const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                       const int32_t* seen_items, void* scratch, int32_t* above, int32_t* pos, void* stream) {
-    return user_rank_impl("sml_user_rank_f16", 2, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
-                          seen_items, nullptr, scratch, above, pos, stream);
+    return user_rank_impl("sml_user_rank_f16", ctx, {0, 2, w_user, w_item, n_item, seen_off, seen_items}, false, users, n, pos_off, pos_items, n_pos,
+                          scratch, above, pos, stream);
 }
 
 int sml_user_rank_filtered(sml_ctx* ctx, const float* w_user, const float* w_item, int64_t n_item, const int64_t* users, int64_t n,
                            const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                            const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above, int32_t* pos, void* stream) {
-    return user_rank_impl("sml_user_rank_filtered", 4, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
-                          seen_items, allow, scratch, above, pos, stream);
+    return user_rank_impl("sml_user_rank_filtered", ctx, {0, 4, w_user, w_item, n_item, seen_off, seen_items, allow}, false, users, n, pos_off,
+                          pos_items, n_pos, scratch, above, pos, stream);
 }
 
 int sml_user_rank_filtered_f16(sml_ctx* ctx, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,
                                const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                                const int32_t* seen_items, const uint32_t* allow, void* scratch, int32_t* above, int32_t* pos,
                                void* stream) {
-    return user_rank_impl("sml_user_rank_filtered_f16", 2, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
-                          seen_items, allow, scratch, above, pos, stream);
+    return user_rank_impl("sml_user_rank_filtered_f16", ctx, {0, 2, w_user, w_item, n_item, seen_off, seen_items, allow}, false, users, n, pos_off,
+                          pos_items, n_pos, scratch, above, pos, stream);
 }
 
 // the adjusted score A(u, i) = fmaf(S(u, i), scale[i], offset[i]): one entry point per operation serves both element types
-static bool elem_ok(int elem_bytes) { return elem_bytes == 4 || elem_bytes == 2; }
-
 int sml_full_rank_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* rows,
                            int64_t n, int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow,
                            const float* adj, int32_t* rank, void* stream) {
-    if (!elem_ok(elem_bytes)) return fail(SML_EINVAL, "sml_full_rank_adjusted", "bad argument (elem_bytes must be 4 or 2)");
-    return full_rank_impl("sml_full_rank_adjusted", elem_bytes, ctx, w_user, w_item, n_item, rows, n, n_cols, seen_off, seen_items, allow, rank,
-                          stream, adj, true);
+    return full_rank_impl("sml_full_rank_adjusted", ctx, {0, elem_bytes, w_user, w_item, n_item, seen_off, seen_items, allow, adj}, true, rows, n,
+                          n_cols, rank, stream);
 }
 
 int sml_topk_items_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* users,
                             int64_t n, int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
                             void* scratch, int32_t* items, float* scores, void* stream) {
-    if (!elem_ok(elem_bytes)) return fail(SML_EINVAL, "sml_topk_items_adjusted", "bad argument (elem_bytes must be 4 or 2)");
-    return topk_items_impl("sml_topk_items_adjusted", elem_bytes, ctx, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, scratch,
-                           items, scores, stream, adj, true);
+    return topk_items_impl("sml_topk_items_adjusted", ctx, {0, elem_bytes, w_user, w_item, n_item, seen_off, seen_items, allow, adj}, true, users, n,
+                           k, scratch, items, scores, stream);
 }
 
 int sml_user_rank_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* users,
                            int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
                            const int32_t* seen_items, const uint32_t* allow, const float* adj, void* scratch, int32_t* above, int32_t* pos,
                            void* stream) {
-    if (!elem_ok(elem_bytes)) return fail(SML_EINVAL, "sml_user_rank_adjusted", "bad argument (elem_bytes must be 4 or 2)");
-    return user_rank_impl("sml_user_rank_adjusted", elem_bytes, ctx, w_user, w_item, n_item, users, n, pos_off, pos_items, n_pos, seen_off,
-                          seen_items, allow, scratch, above, pos, stream, adj, true);
+    return user_rank_impl("sml_user_rank_adjusted", ctx, {0, elem_bytes, w_user, w_item, n_item, seen_off, seen_items, allow, adj}, true, users, n,
+                          pos_off, pos_items, n_pos, scratch, above, pos, stream);
 }
 
 int64_t sml_item_adjust_len(int64_t n_item) {

@@ -14,7 +14,14 @@
 // in registers that way (3 D/4 VGPRs instead of 3 D/2).  A half is widened to fp32 (exact: every fp16 value is an fp32
 // value) only where it feeds an fmaf or the fp32 MFMA, so S(u, i) on fp16 tables is the same chain on the widened entries
 // and equals the fp32 kernels' score of the widened tables bit for bit.  The element type is a parameter of the walk's
-// loads (HalfRow); the fp16 kernels are the k_*_h entry points over the same bodies.
+// loads (HalfRow).
+//
+// Every kernel that reads the tables is ONE __global__ template k_x<D, T, F, A>: width, element type (float / _Float16),
+// F = an item filter was given, A = per-item score terms were given.  The four share a flat parameter list -- the tables
+// and n_item first, allow and adj directly after seen_items -- and an instantiation with F or A false never reads its
+// pointer (every use is under `if constexpr`).  with_width() alone turns a catalogue into those four arguments.  (Before
+// this, F and the element type were part of the name: k_x_f<D> / k_x_h<D> / k_x_f_h<D>, and k_x_a<D, F> / k_x_a_h<D, F>
+// for A; profiles/ and the tables of DESIGN.md recorded under those names keep them.)
 //
 // Grid: (32 * W users) x slices; slice = blockIdx % slices, so with slices a multiple of 8 an XCD walks 1/8 of the
 // item table (plan_grid on the host, lane_pos on the device).  Every wave owns 32 users.
@@ -54,18 +61,17 @@
 // 32 t + b may appear.  The filter is per call, not per user, so a tile's word is wave-uniform: the walk reads it with a
 // scalar load, ANDs it into the tile's eligibility word, and skips a tile whose word is 0 for the whole wave -- no item
 // rows, no MFMAs, no callback; the double buffer prefetches the next NON-EMPTY tile of the slice.  The filtered kernels
-// are instantiations of their own (walk_slice<.., true>, k_x_f<D> / k_x_f_h<D>); the unfiltered ones compile to what
-// they were without it.  k_filter_fill / k_filter_from_ids build a bitmap from a list of item ids.
+// are instantiations of their own (F = true); the unfiltered ones compile to what they were without it.  k_filter_fill /
+// k_filter_from_ids build a bitmap from a list of item ids.
 //
 // Adjusted score (the sml_*_adjusted entry points): A(u, i) = fmaf(S(u, i), scale[i], offset[i]), one more fp32 rounding
 // per score, from a padded per-item table adj float [2][n_pad], n_pad = 32 * n_tiles (plane 0 scale, plane 1 offset).  A
 // lane's 16 items of a tile are four runs of four consecutive rows (row_of), so the terms of a tile are four 16-byte loads
 // per plane, the same for the 32 user lanes of a half; they are requested with the next tile's item rows and applied to
 // the 16 accumulators, one explicit fmaf each, before the kernel's callable sees them -- the callables do not change.
-// The thresholds (full_rank_body's thr, ur_thresholds_body's key) are the same expression on score_chain.  A skipped
+// The thresholds (k_full_rank's thr, k_ur_thresholds' key) are the same expression on score_chain.  A skipped
 // tile loads no adj; the last tile's loads end at n_pad, whose pad entries belong to items the eligibility word masks.
-// The adjusted kernels are instantiations of their own (walk_slice<.., F, true>, k_x_a<D, F> / k_x_a_h<D, F>).
-// k_adjust_fill / k_adjust_cosine build the table.
+// The adjusted kernels are instantiations of their own (A = true).  k_adjust_fill / k_adjust_cosine build the table.
 #include <climits>
 #include <cmath>
 #include <type_traits>
@@ -241,6 +247,9 @@ struct TileTerms<true> {
     }
 };
 
+// plane 1 of adj [2][n_pad]
+__device__ __forceinline__ const float* offset_plane(const float* adj, int64_t n_item) { return adj + (n_item + RT - 1) / RT * RT; }
+
 // A(u, p) from s = S(u, p): the expression of TileTerms::apply, for the thresholds (A = false: s itself).  scale / offset:
 // the two planes of adj
 template <bool A>
@@ -248,9 +257,6 @@ __device__ __forceinline__ float adjusted(float s, const float* __restrict__ sca
     if constexpr (!A) return s;
     else return __builtin_fmaf(s, scale[p], offset[p]);
 }
-
-// plane 1 of adj [2][n_pad]
-__device__ __forceinline__ const float* offset_plane(const float* adj, int64_t n_item) { return adj + (n_item + RT - 1) / RT * RT; }
 
 // The catalogue walk of one wave: user u's scores against every 32-item tile of the lane's slice, next tile's item rows
 // in flight under the current tile's MFMAs.  tile(acc, base, elig) runs once per tile: acc[q] = S(u, base + row_of(q, h)),
@@ -313,14 +319,12 @@ __device__ __forceinline__ void walk_slice(const T* __restrict__ wu, const T* __
     }
 }
 
-// The kernels below are bodies over the element type T; each has two __global__ entry points, k_x<D> on fp32 tables and
-// k_x_h<D> on fp16 tables.
-template <int D, bool F = false, bool A = false, class T>
-__device__ __forceinline__ void full_rank_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
-                                               const int64_t* __restrict__ rows, int64_t n, int n_cols,
-                                               const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                               int slices, int slice_tiles, int32_t* __restrict__ rank,
-                                               const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr) {
+template <int D, class T, bool F, bool A>
+__global__ __launch_bounds__(256) void k_full_rank(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                                   const int64_t* __restrict__ rows, int64_t n, int n_cols,
+                                                   const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                   const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                   int slice_tiles, int32_t* __restrict__ rank) {
     const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
     const int64_t u = rows[lp.rc * n_cols], p = rows[lp.rc * n_cols + 1];
     const float thr = adjusted<A>(score_chain<D>(wu + u * D, wi + p * D), adj, A ? offset_plane(adj, n_item) : nullptr, p);
@@ -331,41 +335,6 @@ __device__ __forceinline__ void full_rank_body(const T* __restrict__ wu, const T
     });
     cnt += __shfl_xor(cnt, 32, 64);
     if (lp.h == 0 && lp.valid && cnt) atomicAdd(rank + lp.row, cnt);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_full_rank(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                   const int64_t* __restrict__ rows, int64_t n, int n_cols,
-                                                   const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                   int slices, int slice_tiles, int32_t* __restrict__ rank) {
-    full_rank_body<D>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_full_rank_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
-                                                     const int64_t* __restrict__ rows, int64_t n, int n_cols,
-                                                     const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                     int slices, int slice_tiles, int32_t* __restrict__ rank) {
-    full_rank_body<D>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank);
-}
-
-// the filtered forms: the same bodies over walk_slice<.., true>; `allow` is the item filter, one word per tile
-template <int D>
-__global__ __launch_bounds__(256) void k_full_rank_f(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                     const int64_t* __restrict__ rows, int64_t n, int n_cols,
-                                                     const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                     const uint32_t* __restrict__ allow, int slices, int slice_tiles,
-                                                     int32_t* __restrict__ rank) {
-    full_rank_body<D, true>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank, allow);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_full_rank_f_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
-                                                       const int64_t* __restrict__ rows, int64_t n, int n_cols,
-                                                       const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                       const uint32_t* __restrict__ allow, int slices, int slice_tiles,
-                                                       int32_t* __restrict__ rank) {
-    full_rank_body<D, true>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank, allow);
 }
 
 // insert (s, i) into user j's list (k slots, column j of [k][32] arrays); cnt = live entries
@@ -389,14 +358,20 @@ __device__ __forceinline__ void list_insert(float* ls, int* li, int k, int j, in
     li[q * RT + j] = i;
 }
 
+// k_topk_slice, k_ur_thresholds and k_ur_count keep their code in a __forceinline__ body that the kernel only forwards to.
+// Folded into their kernels these three, which store to global memory between their loads, compile to other code
+// (k_topk_slice 7 to 31 instructions longer in every instantiation): the body's __restrict__ parameters become alias scopes
+// where it is inlined, and those evidently tell the compiler more than the same qualifiers on a __global__ function's
+// parameters do.  k_full_rank, whose only write is an atomic, is the same code either way and has no body.
+
 // candidates of user x, slice s: cand_s / cand_i [(x * slices + s) * k + q], cand_n [x * slices + s]
-template <int D, bool F = false, bool A = false, class T>
+template <int D, class T, bool F, bool A>
 __device__ __forceinline__ void topk_slice_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                                 const int64_t* __restrict__ users, int64_t n, int k,
                                                 const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                int slices, int slice_tiles, float* __restrict__ cand_s,
-                                                int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n,
-                                                const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr) {
+                                                const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                int slice_tiles, float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
+                                                int32_t* __restrict__ cand_n) {
     extern __shared__ float lds[];
     const LanePos lp = lane_pos(slices, blockDim.x >> 6, n);
     const int h = lp.h, j = lp.j;
@@ -441,42 +416,14 @@ __device__ __forceinline__ void topk_slice_body(const T* __restrict__ wu, const 
     if (h == 0) cand_n[lp.row * slices + lp.slice] = cnt;
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void k_topk_slice(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+template <int D, class T, bool F, bool A>
+__global__ __launch_bounds__(256) void k_topk_slice(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                                     const int64_t* __restrict__ users, int64_t n, int k,
                                                     const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                    int slices, int slice_tiles, float* __restrict__ cand_s,
-                                                    int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n) {
-    topk_slice_body<D>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_topk_slice_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
-                                                      const int64_t* __restrict__ users, int64_t n, int k,
-                                                      const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                      int slices, int slice_tiles, float* __restrict__ cand_s,
-                                                      int32_t* __restrict__ cand_i, int32_t* __restrict__ cand_n) {
-    topk_slice_body<D>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_topk_slice_f(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                      const int64_t* __restrict__ users, int64_t n, int k,
-                                                      const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                      const uint32_t* __restrict__ allow, int slices, int slice_tiles,
-                                                      float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
-                                                      int32_t* __restrict__ cand_n) {
-    topk_slice_body<D, true>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n, allow);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_topk_slice_f_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
-                                                        const int64_t* __restrict__ users, int64_t n, int k,
-                                                        const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                        const uint32_t* __restrict__ allow, int slices, int slice_tiles,
-                                                        float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
-                                                        int32_t* __restrict__ cand_n) {
-    topk_slice_body<D, true>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n, allow);
+                                                    const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                    int slice_tiles, float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
+                                                    int32_t* __restrict__ cand_n) {
+    topk_slice_body<D, T, F, A>(wu, wi, n_item, users, n, k, seen_off, seen_items, allow, adj, slices, slice_tiles, cand_s, cand_i, cand_n);
 }
 
 // one thread per (user, slice, slot): the candidate's final position is its slot plus the number of strictly better
@@ -538,34 +485,37 @@ int topk_waves(int k) {
 
 SliceGrid topk_grid(int64_t n, int k, int64_t n_item) { return plan_grid(n, topk_waves(k), n_item, 2048, 4); }
 
-// the one place that turns the embedding width and the element type into template arguments: f(D, wu, wi) with D a
-// std::integral_constant and the tables typed (fp32: d = 32 / 64; fp16, elem_bytes 2: d = 32 / 64 / 128).  false: a pair
-// the kernels do not exist for, nothing was called -- the launchers' refusal, and what sml_retrieval_supports asks
-template <class F>
-bool with_width(int d, int elem_bytes, const void* wu, const void* wi, F&& f) {
+// the one place that turns a catalogue -- embedding width, element type, filter or none, terms or none -- into template
+// arguments: f(D, F, A, wu, wi) with D a std::integral_constant, F and A std::bool_constants and the tables typed (fp32:
+// d = 32 / 64; fp16, elem_bytes 2: d = 32 / 64 / 128).  A kernel named inside the generic callable depends on D and the
+// tables' type, so only the pairs called here are instantiated.  false: a pair the kernels do not exist for, nothing was
+// called -- the launchers' refusal, and what sml_retrieval_supports asks
+template <class Fn>
+bool with_width(const SmlCatalogue& c, Fn&& f) {
     const auto typed = [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
-        f(dd, static_cast<const T*>(wu), static_cast<const T*>(wi));
+        const T* wu = static_cast<const T*>(c.wu);
+        const T* wi = static_cast<const T*>(c.wi);
+        if (c.allow && c.adj) f(dd, std::true_type(), std::true_type(), wu, wi);
+        else if (c.adj) f(dd, std::false_type(), std::true_type(), wu, wi);
+        else if (c.allow) f(dd, std::true_type(), std::false_type(), wu, wi);
+        else f(dd, std::false_type(), std::false_type(), wu, wi);
         return true;
     };
-    if (elem_bytes == 4) {
-        if (d == 32) return typed(std::integral_constant<int, 32>(), (float*)nullptr);
-        if (d == 64) return typed(std::integral_constant<int, 64>(), (float*)nullptr);
-    } else if (elem_bytes == 2) {
-        if (d == 32) return typed(std::integral_constant<int, 32>(), (_Float16*)nullptr);
-        if (d == 64) return typed(std::integral_constant<int, 64>(), (_Float16*)nullptr);
-        if (d == 128) return typed(std::integral_constant<int, 128>(), (_Float16*)nullptr);
+    if (c.elem_bytes == 4) {
+        if (c.d == 32) return typed(std::integral_constant<int, 32>(), (float*)nullptr);
+        if (c.d == 64) return typed(std::integral_constant<int, 64>(), (float*)nullptr);
+    } else if (c.elem_bytes == 2) {
+        if (c.d == 32) return typed(std::integral_constant<int, 32>(), (_Float16*)nullptr);
+        if (c.d == 64) return typed(std::integral_constant<int, 64>(), (_Float16*)nullptr);
+        if (c.d == 128) return typed(std::integral_constant<int, 128>(), (_Float16*)nullptr);
     }
     return false;
 }
 
-// inside with_width's callable: launch k_x<D> when the typed user table tu is fp32, k_x_h<D> when it is fp16.  (A macro
-// because only the taken branch may name its kernel: a function taking both kernels would instantiate k_x<128> on fp32.)
-#define LAUNCH_TYPED(name, D, tu, grid, block, lds, st, ...)                                                              \
-    do {                                                                                                                  \
-        if constexpr (std::is_same<decltype(tu), const float*>::value) name<D><<<grid, block, lds, st>>>(__VA_ARGS__);    \
-        else name##_h<D><<<grid, block, lds, st>>>(__VA_ARGS__);                                                          \
-    } while (0)
+// the element type of a typed table pointer, as the kernels' T
+template <class P>
+using elem_t = std::remove_const_t<std::remove_pointer_t<P>>;
 
 // ---- per-user ranking of held-out sets ------------------------------------------------------------------------------
 
@@ -593,15 +543,15 @@ __device__ __forceinline__ int64_t ur_segment(const int64_t* __restrict__ off, i
 }
 
 // in_seen[e] = 1: the held-out item is not eligible by id -- in Seen(u) or, with a filter (F), not allowed
-template <int D, bool F = false, bool A = false, class T>
+template <int D, class T, bool F, bool A>
 __device__ __forceinline__ void ur_thresholds_body(const T* __restrict__ wu, const T* __restrict__ wi,
                                                    const int64_t* __restrict__ users, int64_t n,
                                                    const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
                                                    int64_t n_pos, const int64_t* __restrict__ seen_off,
-                                                   const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
-                                                   float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
-                                                   int32_t* __restrict__ in_seen, const uint32_t* __restrict__ allow = nullptr,
-                                                   const float* __restrict__ scale = nullptr, const float* __restrict__ offset = nullptr) {
+                                                   const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
+                                                   const float* __restrict__ scale, const float* __restrict__ offset,
+                                                   int32_t* __restrict__ seg, float* __restrict__ ks, int32_t* __restrict__ ki,
+                                                   int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_pos) return;
     const int64_t x = ur_segment(pos_off, n, e);
@@ -621,48 +571,16 @@ __device__ __forceinline__ void ur_thresholds_body(const T* __restrict__ wu, con
     in_seen[e] = sn;
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void k_ur_thresholds(const float* __restrict__ wu, const float* __restrict__ wi,
+template <int D, class T, bool F, bool A>
+__global__ __launch_bounds__(256) void k_ur_thresholds(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                                        const int64_t* __restrict__ users, int64_t n,
                                                        const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
                                                        int64_t n_pos, const int64_t* __restrict__ seen_off,
-                                                       const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
-                                                       float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
-                                                       int32_t* __restrict__ in_seen) {
-    ur_thresholds_body<D>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_ur_thresholds_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
-                                                         const int64_t* __restrict__ users, int64_t n,
-                                                         const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
-                                                         int64_t n_pos, const int64_t* __restrict__ seen_off,
-                                                         const int32_t* __restrict__ seen_items, int32_t* __restrict__ seg,
-                                                         float* __restrict__ ks, int32_t* __restrict__ ki, int32_t* __restrict__ kx,
-                                                         int32_t* __restrict__ in_seen) {
-    ur_thresholds_body<D>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_ur_thresholds_f(const float* __restrict__ wu, const float* __restrict__ wi,
-                                                         const int64_t* __restrict__ users, int64_t n,
-                                                         const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
-                                                         int64_t n_pos, const int64_t* __restrict__ seen_off,
-                                                         const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
-                                                         int32_t* __restrict__ seg, float* __restrict__ ks, int32_t* __restrict__ ki,
-                                                         int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
-    ur_thresholds_body<D, true>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen, allow);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_ur_thresholds_f_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
-                                                           const int64_t* __restrict__ users, int64_t n,
-                                                           const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
-                                                           int64_t n_pos, const int64_t* __restrict__ seen_off,
-                                                           const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
-                                                           int32_t* __restrict__ seg, float* __restrict__ ks, int32_t* __restrict__ ki,
-                                                           int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
-    ur_thresholds_body<D, true>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen, allow);
+                                                       const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
+                                                       const float* __restrict__ adj, int32_t* __restrict__ seg, float* __restrict__ ks,
+                                                       int32_t* __restrict__ ki, int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
+    ur_thresholds_body<D, T, F, A>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, allow, adj,
+                                   A ? offset_plane(adj, n_item) : nullptr, seg, ks, ki, kx, in_seen);
 }
 
 // runs [a0, a0 + w) and [a0 + w, a0 + 2w) of every user's range -> one sorted run
@@ -709,14 +627,14 @@ __device__ __forceinline__ void ur_place(const float* ts, const int32_t* ti, int
 
 // ss / si: every user's thresholds and ids in ur_less order.  At sorted place b of user x, bin_p (zeroed) receives the
 // number of eligible items whose pos bound is b, and bin_d (zeroed) what turns those counts into the above bounds'
-template <int D, bool F = false, bool A = false, class T>
+template <int D, class T, bool F, bool A>
 __device__ __forceinline__ void ur_count_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
-                                              const int64_t* __restrict__ users, int64_t n, const int64_t* __restrict__ pos_off,
+                                              const int64_t* __restrict__ users, int64_t n,
+                                              const int64_t* __restrict__ pos_off,
                                               const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                              int slices, int slice_tiles, const float* __restrict__ ss,
-                                              const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
-                                              int32_t* __restrict__ bin_d, const uint32_t* __restrict__ allow = nullptr,
-                                              const float* __restrict__ adj = nullptr) {
+                                              const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                              int slice_tiles, const float* __restrict__ ss, const int32_t* __restrict__ si,
+                                              int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
     __shared__ float l_s[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_i[kUrWaves][kUrWin * RT];
     __shared__ int32_t l_p[kUrWaves][kUrWin * RT];
@@ -777,148 +695,18 @@ __device__ __forceinline__ void ur_count_body(const T* __restrict__ wu, const T*
     }
 }
 
-template <int D>
-__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
+template <int D, class T, bool F, bool A>
+__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
                                                             const int64_t* __restrict__ users, int64_t n,
                                                             const int64_t* __restrict__ pos_off,
                                                             const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                            int slices, int slice_tiles, const float* __restrict__ ss,
-                                                            const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
-                                                            int32_t* __restrict__ bin_d) {
-    ur_count_body<D>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d);
+                                                            const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                            int slice_tiles, const float* __restrict__ ss, const int32_t* __restrict__ si,
+                                                            int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
+    ur_count_body<D, T, F, A>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, allow, adj, slices, slice_tiles, ss, si, bin_p, bin_d);
 }
 
-template <int D>
-__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
-                                                              int64_t n_item, const int64_t* __restrict__ users, int64_t n,
-                                                              const int64_t* __restrict__ pos_off,
-                                                              const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                              int slices, int slice_tiles, const float* __restrict__ ss,
-                                                              const int32_t* __restrict__ si, int32_t* __restrict__ bin_p,
-                                                              int32_t* __restrict__ bin_d) {
-    ur_count_body<D>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d);
-}
-
-template <int D>
-__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_f(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                              const int64_t* __restrict__ users, int64_t n,
-                                                              const int64_t* __restrict__ pos_off,
-                                                              const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                              const uint32_t* __restrict__ allow, int slices, int slice_tiles,
-                                                              const float* __restrict__ ss, const int32_t* __restrict__ si,
-                                                              int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
-    ur_count_body<D, true>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d, allow);
-}
-
-template <int D>
-__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_f_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
-                                                                int64_t n_item, const int64_t* __restrict__ users, int64_t n,
-                                                                const int64_t* __restrict__ pos_off,
-                                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                                const uint32_t* __restrict__ allow, int slices, int slice_tiles,
-                                                                const float* __restrict__ ss, const int32_t* __restrict__ si,
-                                                                int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
-    ur_count_body<D, true>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d, allow);
-}
-
-// ---- adjusted score: the kernels of sml_*_adjusted -------------------------------------------------------------------
-
-// the same bodies over walk_slice<.., F, true>: adj is the padded term table, allow the item filter when F (else unused)
-template <int D, bool F>
-__global__ __launch_bounds__(256) void k_full_rank_a(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                     const int64_t* __restrict__ rows, int64_t n, int n_cols,
-                                                     const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                     const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
-                                                     int slice_tiles, int32_t* __restrict__ rank) {
-    full_rank_body<D, F, true>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank, allow, adj);
-}
-
-template <int D, bool F>
-__global__ __launch_bounds__(256) void k_full_rank_a_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
-                                                       const int64_t* __restrict__ rows, int64_t n, int n_cols,
-                                                       const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                       const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
-                                                       int slice_tiles, int32_t* __restrict__ rank) {
-    full_rank_body<D, F, true>(wu, wi, n_item, rows, n, n_cols, seen_off, seen_items, slices, slice_tiles, rank, allow, adj);
-}
-
-template <int D, bool F>
-__global__ __launch_bounds__(256) void k_topk_slice_a(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                      const int64_t* __restrict__ users, int64_t n, int k,
-                                                      const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                      const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
-                                                      int slice_tiles, float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
-                                                      int32_t* __restrict__ cand_n) {
-    topk_slice_body<D, F, true>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n, allow, adj);
-}
-
-template <int D, bool F>
-__global__ __launch_bounds__(256) void k_topk_slice_a_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
-                                                        const int64_t* __restrict__ users, int64_t n, int k,
-                                                        const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                        const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
-                                                        int slice_tiles, float* __restrict__ cand_s, int32_t* __restrict__ cand_i,
-                                                        int32_t* __restrict__ cand_n) {
-    topk_slice_body<D, F, true>(wu, wi, n_item, users, n, k, seen_off, seen_items, slices, slice_tiles, cand_s, cand_i, cand_n, allow, adj);
-}
-
-template <int D, bool F>
-__global__ __launch_bounds__(256) void k_ur_thresholds_a(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                         const int64_t* __restrict__ users, int64_t n,
-                                                         const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
-                                                         int64_t n_pos, const int64_t* __restrict__ seen_off,
-                                                         const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
-                                                         const float* __restrict__ adj, int32_t* __restrict__ seg, float* __restrict__ ks,
-                                                         int32_t* __restrict__ ki, int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
-    ur_thresholds_body<D, F, true>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen, allow, adj,
-                                   offset_plane(adj, n_item));
-}
-
-template <int D, bool F>
-__global__ __launch_bounds__(256) void k_ur_thresholds_a_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi, int64_t n_item,
-                                                           const int64_t* __restrict__ users, int64_t n,
-                                                           const int64_t* __restrict__ pos_off, const int32_t* __restrict__ pos_items,
-                                                           int64_t n_pos, const int64_t* __restrict__ seen_off,
-                                                           const int32_t* __restrict__ seen_items, const uint32_t* __restrict__ allow,
-                                                           const float* __restrict__ adj, int32_t* __restrict__ seg, float* __restrict__ ks,
-                                                           int32_t* __restrict__ ki, int32_t* __restrict__ kx, int32_t* __restrict__ in_seen) {
-    ur_thresholds_body<D, F, true>(wu, wi, users, n, pos_off, pos_items, n_pos, seen_off, seen_items, seg, ks, ki, kx, in_seen, allow, adj,
-                                   offset_plane(adj, n_item));
-}
-
-template <int D, bool F>
-__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_a(const float* __restrict__ wu, const float* __restrict__ wi, int64_t n_item,
-                                                              const int64_t* __restrict__ users, int64_t n,
-                                                              const int64_t* __restrict__ pos_off,
-                                                              const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                              const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
-                                                              int slice_tiles, const float* __restrict__ ss, const int32_t* __restrict__ si,
-                                                              int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
-    ur_count_body<D, F, true>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d, allow, adj);
-}
-
-template <int D, bool F>
-__global__ __launch_bounds__(64 * kUrWaves) void k_ur_count_a_h(const _Float16* __restrict__ wu, const _Float16* __restrict__ wi,
-                                                                int64_t n_item, const int64_t* __restrict__ users, int64_t n,
-                                                                const int64_t* __restrict__ pos_off,
-                                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
-                                                                const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
-                                                                int slice_tiles, const float* __restrict__ ss, const int32_t* __restrict__ si,
-                                                                int32_t* __restrict__ bin_p, int32_t* __restrict__ bin_d) {
-    ur_count_body<D, F, true>(wu, wi, n_item, users, n, pos_off, seen_off, seen_items, slices, slice_tiles, ss, si, bin_p, bin_d, allow, adj);
-}
-
-// LAUNCH_TYPED for the adjusted kernels: k_x_a<D, F> / k_x_a_h<D, F>, F = a filter was given
-#define LAUNCH_ADJUSTED(name, D, tu, allow, grid, block, lds, st, ...)                                                    \
-    do {                                                                                                                  \
-        if constexpr (std::is_same<decltype(tu), const float*>::value) {                                                  \
-            if (allow) name<D, true><<<grid, block, lds, st>>>(__VA_ARGS__);                                              \
-            else name<D, false><<<grid, block, lds, st>>>(__VA_ARGS__);                                                   \
-        } else {                                                                                                          \
-            if (allow) name##_h<D, true><<<grid, block, lds, st>>>(__VA_ARGS__);                                          \
-            else name##_h<D, false><<<grid, block, lds, st>>>(__VA_ARGS__);                                               \
-        }                                                                                                                 \
-    } while (0)
+// ---- adjusted score: the table builders of sml_item_adjust_* ------------------------------------------------------------
 
 // adj [2][n_pad] from optional per-item arrays: NULL scale = 1, NULL offset = +0; the pad entries are written (1, 0)
 __global__ __launch_bounds__(256) void k_adjust_fill(const float* __restrict__ scale, const float* __restrict__ offset, int64_t n_item,
@@ -932,7 +720,7 @@ __global__ __launch_bounds__(256) void k_adjust_fill(const float* __restrict__ s
 // plane 0 of adj = 1 / ||x_i||, the squared norm by the score chain with the row on both sides; a zero row (and a row
 // whose chain is NaN) gets 0.  sqrtf and the division are the correctly rounded ones (the build has no fast-math flag)
 template <int D, class T>
-__device__ __forceinline__ void adjust_cosine_body(const T* __restrict__ wi, int64_t n_item, int64_t n_pad, float* __restrict__ adj) {
+__global__ __launch_bounds__(256) void k_adjust_cosine(const T* __restrict__ wi, int64_t n_item, int64_t n_pad, float* __restrict__ adj) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pad) return;
     float s = 1.0f;
@@ -941,17 +729,6 @@ __device__ __forceinline__ void adjust_cosine_body(const T* __restrict__ wi, int
         s = n2 > 0.0f ? 1.0f / sqrtf(n2) : 0.0f;
     }
     adj[i] = s;
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_adjust_cosine(const float* __restrict__ wi, int64_t n_item, int64_t n_pad, float* __restrict__ adj) {
-    adjust_cosine_body<D>(wi, n_item, n_pad, adj);
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_adjust_cosine_h(const _Float16* __restrict__ wi, int64_t n_item, int64_t n_pad,
-                                                         float* __restrict__ adj) {
-    adjust_cosine_body<D>(wi, n_item, n_pad, adj);
 }
 
 // ---- item filter from a list of ids -----------------------------------------------------------------------------------
@@ -1090,26 +867,20 @@ __global__ __launch_bounds__(kUrBlock) void k_ur_metrics(const int32_t* __restri
 }  // namespace
 
 bool sml_retrieval_supports(int d, int elem_bytes) {
-    return with_width(d, elem_bytes, nullptr, nullptr, [](auto, auto*, auto*) {});
+    SmlCatalogue c = {};
+    c.d = d;
+    c.elem_bytes = elem_bytes;
+    return with_width(c, [](auto, auto, auto, auto*, auto*) {});
 }
 
-hipError_t sml_launch_full_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* rows, int64_t n,
-                                int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
-                                int32_t* rank, hipStream_t st) {
+hipError_t sml_launch_full_rank(const SmlCatalogue& c, const int64_t* rows, int64_t n, int n_cols, int32_t* rank, hipStream_t st) {
     hipError_t e = hipMemsetAsync(rank, 0, n * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
-    const SliceGrid g = rank_grid(n, kRankWaves, n_item);
+    const SliceGrid g = rank_grid(n, kRankWaves, c.n_item);
     const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kRankWaves);
-    if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        if (adj)
-            LAUNCH_ADJUSTED(k_full_rank_a, decltype(dd)::value, tu, allow, grid, block, 0, st, tu, ti, n_item, rows, n, n_cols, seen_off,
-                            seen_items, allow, adj, g.slices, g.slice_tiles, rank);
-        else if (allow)
-            LAUNCH_TYPED(k_full_rank_f, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, rows, n, n_cols, seen_off, seen_items,
-                         allow, g.slices, g.slice_tiles, rank);
-        else
-            LAUNCH_TYPED(k_full_rank, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, rows, n, n_cols, seen_off, seen_items,
-                         g.slices, g.slice_tiles, rank);
+    if (!with_width(c, [&](auto dd, auto ff, auto aa, auto* tu, auto* ti) {
+        k_full_rank<dd(), elem_t<decltype(tu)>, ff(), aa()><<<grid, block, 0, st>>>(
+            tu, ti, c.n_item, rows, n, n_cols, c.seen_off, c.seen_items, c.allow, c.adj, g.slices, g.slice_tiles, rank);
     }))
         return hipErrorInvalidValue;
     return hipGetLastError();
@@ -1120,26 +891,18 @@ int64_t sml_topk_scratch_size(int64_t n, int k, int64_t n_item) {
     return n * s * (int64_t)k * 8 + n * s * 4;
 }
 
-hipError_t sml_launch_topk(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
-                           int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj, void* scratch,
-                           int32_t* items, float* scores, hipStream_t st) {
-    const SliceGrid g = topk_grid(n, k, n_item);
+hipError_t sml_launch_topk(const SmlCatalogue& c, const int64_t* users, int64_t n, int k, void* scratch, int32_t* items, float* scores,
+                           hipStream_t st) {
+    const SliceGrid g = topk_grid(n, k, c.n_item);
     const int slices = g.slices, waves = topk_waves(k);
     float* cs = static_cast<float*>(scratch);
     int32_t* ci = reinterpret_cast<int32_t*>(cs + n * slices * k);
     int32_t* cn = ci + n * slices * k;
     const dim3 grid((unsigned)(g.groups * slices)), block(64 * waves);
     const size_t lds = (size_t)waves * 2 * k * RT * 4;
-    if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        if (adj)
-            LAUNCH_ADJUSTED(k_topk_slice_a, decltype(dd)::value, tu, allow, grid, block, lds, st, tu, ti, n_item, users, n, k, seen_off,
-                            seen_items, allow, adj, slices, g.slice_tiles, cs, ci, cn);
-        else if (allow)
-            LAUNCH_TYPED(k_topk_slice_f, decltype(dd)::value, tu, grid, block, lds, st, tu, ti, n_item, users, n, k, seen_off, seen_items,
-                         allow, slices, g.slice_tiles, cs, ci, cn);
-        else
-            LAUNCH_TYPED(k_topk_slice, decltype(dd)::value, tu, grid, block, lds, st, tu, ti, n_item, users, n, k, seen_off, seen_items,
-                         slices, g.slice_tiles, cs, ci, cn);
+    if (!with_width(c, [&](auto dd, auto ff, auto aa, auto* tu, auto* ti) {
+        k_topk_slice<dd(), elem_t<decltype(tu)>, ff(), aa()><<<grid, block, lds, st>>>(
+            tu, ti, c.n_item, users, n, k, c.seen_off, c.seen_items, c.allow, c.adj, slices, g.slice_tiles, cs, ci, cn);
     }))
         return hipErrorInvalidValue;
     hipError_t e = hipGetLastError();
@@ -1154,10 +917,8 @@ static int64_t ur_piece(int64_t n_pos) { return (n_pos * 4 + 255) / 256 * 256; }
 
 int64_t sml_user_rank_scratch_size(int64_t n_pos) { return 10 * ur_piece(n_pos); }
 
-hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
-                                const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
-                                const int32_t* seen_items, const uint32_t* allow, const float* adj, void* scratch, int32_t* above,
-                                int32_t* pos, hipStream_t st) {
+hipError_t sml_launch_user_rank(const SmlCatalogue& c, const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items,
+                                int64_t n_pos, void* scratch, int32_t* above, int32_t* pos, hipStream_t st) {
     char* base = static_cast<char*>(scratch);
     const int64_t pc = ur_piece(n_pos);
     int32_t* seg = reinterpret_cast<int32_t*>(base);
@@ -1170,16 +931,9 @@ hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const voi
     hipError_t e = hipMemsetAsync(bin_p, 0, 2 * pc, st);
     if (e != hipSuccess) return e;
     const dim3 eg((unsigned)((n_pos + 255) / 256)), eb(256);
-    if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        if (adj)
-            LAUNCH_ADJUSTED(k_ur_thresholds_a, decltype(dd)::value, tu, allow, eg, eb, 0, st, tu, ti, n_item, users, n, pos_off, pos_items,
-                            n_pos, seen_off, seen_items, allow, adj, seg, ks[0], ki[0], kx[0], in_seen);
-        else if (allow)
-            LAUNCH_TYPED(k_ur_thresholds_f, decltype(dd)::value, tu, eg, eb, 0, st, tu, ti, users, n, pos_off, pos_items, n_pos, seen_off,
-                         seen_items, allow, seg, ks[0], ki[0], kx[0], in_seen);
-        else
-            LAUNCH_TYPED(k_ur_thresholds, decltype(dd)::value, tu, eg, eb, 0, st, tu, ti, users, n, pos_off, pos_items, n_pos, seen_off,
-                         seen_items, seg, ks[0], ki[0], kx[0], in_seen);
+    if (!with_width(c, [&](auto dd, auto ff, auto aa, auto* tu, auto* ti) {
+        k_ur_thresholds<dd(), elem_t<decltype(tu)>, ff(), aa()><<<eg, eb, 0, st>>>(
+            tu, ti, c.n_item, users, n, pos_off, pos_items, n_pos, c.seen_off, c.seen_items, c.allow, c.adj, seg, ks[0], ki[0], kx[0], in_seen);
     }))
         return hipErrorInvalidValue;
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1189,18 +943,11 @@ hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const voi
         k_ur_merge<<<eg, eb, 0, st>>>(pos_off, seg, n_pos, w, ks[cur], ki[cur], kx[cur], ks[cur ^ 1], ki[cur ^ 1], kx[cur ^ 1]);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    const SliceGrid g = rank_grid(n, kUrWaves, n_item);
+    const SliceGrid g = rank_grid(n, kUrWaves, c.n_item);
     const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kUrWaves);
-    if (!with_width(d, elem_bytes, wu, wi, [&](auto dd, auto* tu, auto* ti) {
-        if (adj)
-            LAUNCH_ADJUSTED(k_ur_count_a, decltype(dd)::value, tu, allow, grid, block, 0, st, tu, ti, n_item, users, n, pos_off, seen_off,
-                            seen_items, allow, adj, g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
-        else if (allow)
-            LAUNCH_TYPED(k_ur_count_f, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, users, n, pos_off, seen_off, seen_items,
-                         allow, g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
-        else
-            LAUNCH_TYPED(k_ur_count, decltype(dd)::value, tu, grid, block, 0, st, tu, ti, n_item, users, n, pos_off, seen_off, seen_items,
-                         g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
+    if (!with_width(c, [&](auto dd, auto ff, auto aa, auto* tu, auto* ti) {
+        k_ur_count<dd(), elem_t<decltype(tu)>, ff(), aa()><<<grid, block, 0, st>>>(
+            tu, ti, c.n_item, users, n, pos_off, c.seen_off, c.seen_items, c.allow, c.adj, g.slices, g.slice_tiles, ks[cur], ki[cur], bin_p, bin_d);
     }))
         return hipErrorInvalidValue;
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1236,8 +983,12 @@ hipError_t sml_launch_item_adjust_fill(const float* scale, const float* offset, 
 hipError_t sml_launch_item_adjust_cosine(int d, int elem_bytes, const void* wi, int64_t n_item, float* adj, hipStream_t st) {
     const int64_t n_pad = sml_item_adjust_pad(n_item);
     const dim3 grid((unsigned)((n_pad + 255) / 256)), block(256);
-    if (!with_width(d, elem_bytes, wi, wi, [&](auto dd, auto*, auto* ti) {
-        LAUNCH_TYPED(k_adjust_cosine, decltype(dd)::value, ti, grid, block, 0, st, ti, n_item, n_pad, adj);
+    SmlCatalogue c = {};
+    c.d = d;
+    c.elem_bytes = elem_bytes;
+    c.wi = wi;
+    if (!with_width(c, [&](auto dd, auto, auto, auto*, auto* ti) {
+        k_adjust_cosine<dd(), elem_t<decltype(ti)>><<<grid, block, 0, st>>>(ti, n_item, n_pad, adj);
     }))
         return hipErrorInvalidValue;
     return hipGetLastError();

@@ -417,22 +417,26 @@ hipError_t sml_launch_device_epoch(const int64_t* ui, const void* mat, int elem_
 hipError_t sml_launch_eval_metrics(const int32_t* rank, int64_t n, int topk, float* out, hipStream_t st);
 // retrieval.hip: full-catalogue rank and top-K (n_item < 2^31).  elem_bytes 4: fp32 tables, d = 32 / 64; elem_bytes 2: fp16
 // tables, d = 32 / 64 / 128 -- sml_retrieval_supports says which pairs exist; the launchers refuse the others
+// SmlCatalogue: what every table-reading launcher is given, a host-side argument only (never a kernel parameter).
 // allow: the item filter (one word per 32-item tile, include/sml_hip.h), NULL = none: the unfiltered kernels run
-// adj: the per-item score terms float [2][sml_item_adjust_pad(n_item)] of the _adjusted entry points, NULL = the bare score:
-// the kernels above run, untouched
+// adj: the per-item score terms float [2][sml_item_adjust_pad(n_item)] of the _adjusted entry points, NULL = the bare score
+struct SmlCatalogue {
+    int d, elem_bytes;
+    const void *wu, *wi;
+    int64_t n_item;
+    const int64_t* seen_off;
+    const int32_t* seen_items;
+    const uint32_t* allow;
+    const float* adj;
+};
 bool sml_retrieval_supports(int d, int elem_bytes);
-hipError_t sml_launch_full_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* rows, int64_t n,
-                                int n_cols, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
-                                int32_t* rank, hipStream_t st);
+hipError_t sml_launch_full_rank(const SmlCatalogue& c, const int64_t* rows, int64_t n, int n_cols, int32_t* rank, hipStream_t st);
 int64_t sml_topk_scratch_size(int64_t n, int k, int64_t n_item);
-hipError_t sml_launch_topk(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
-                           int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj, void* scratch,
-                           int32_t* items, float* scores, hipStream_t st);
+hipError_t sml_launch_topk(const SmlCatalogue& c, const int64_t* users, int64_t n, int k, void* scratch, int32_t* items, float* scores,
+                           hipStream_t st);
 int64_t sml_user_rank_scratch_size(int64_t n_pos);
-hipError_t sml_launch_user_rank(int d, int elem_bytes, const void* wu, const void* wi, int64_t n_item, const int64_t* users, int64_t n,
-                                const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos, const int64_t* seen_off,
-                                const int32_t* seen_items, const uint32_t* allow, const float* adj, void* scratch, int32_t* above,
-                                int32_t* pos, hipStream_t st);
+hipError_t sml_launch_user_rank(const SmlCatalogue& c, const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items,
+                                int64_t n_pos, void* scratch, int32_t* above, int32_t* pos, hipStream_t st);
 int64_t sml_item_adjust_pad(int64_t n_item);
 hipError_t sml_launch_item_adjust_fill(const float* scale, const float* offset, int64_t n_item, float* adj, hipStream_t st);
 hipError_t sml_launch_item_adjust_cosine(int d, int elem_bytes, const void* wi, int64_t n_item, float* adj, hipStream_t st);

@@ -178,7 +178,7 @@ def test_128_exact_on_random_halves():
     c = random_half_case(128, seed=928)
     nan_item = plant_specials(c, c["rng"])
     check_exact(engine(128), c["wu"], c["wi"], c["rows"], c["users"], (1, 20, 128), c["seen"])
-    # 161 users: two 128-user groups of k_ur_count_h<128>, every wave of the first with valid users, the second partial
+    # 161 users: two 128-user groups of k_ur_count<128, half, ..>, every wave of the first with valid users, the second partial
     users, off, items = held_out_sets(c, np.random.RandomState(1), 160, extra=(nan_item, 13))
     assert len(users) == 161
     out = check_user_ranks(engine(128), c["wu"], c["wi"], users, off, items, c["seen"])
@@ -203,7 +203,7 @@ def _sweep_users(rng, U, n):
 
 
 def test_128_every_topk_wave_count():
-    """k in {1, 64, 65, 85, 86, 128}: the 4-, 3- and 2-wave blocks of k_topk_slice_h<128>."""
+    """k in {1, 64, 65, 85, 86, 128}: the 4-, 3- and 2-wave blocks of k_topk_slice<128, half, ..>."""
     ks = (1, 64, 65, 85, 86, 128)
     assert {F.topk_waves(k) for k in ks} == {4, 3, 2}
     c = random_half_case(128, seed=929, U=200, I=3001)

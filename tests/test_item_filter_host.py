@@ -3,7 +3,6 @@ and the filter builder, sml_amd.retrieval.ItemFilter, the register report of the
 proof that the filters of the GPU tests change the answers of the CPU references."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -112,21 +111,6 @@ def test_as_filter_forms_agree():
     assert as_filter(None, 4099, "cpu") is None
     f.deny([int(np.nonzero(mask)[0][0])])
     assert f.device("cpu") is not a and len(f) == int(mask.sum()) - 1
-
-
-def test_kernel_resources_report():
-    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_resources.py"),
-                        os.path.join(REPO, "sml_amd", "csrc", "retrieval.hip")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr              # 1: a kernel spills or touches scratch
-    for k in ("k_full_rank", "k_topk_slice", "k_ur_thresholds", "k_ur_count"):
-        for d in (32, 64):
-            assert "%s<%d>" % (k, d) in r.stdout               # the unfiltered kernels keep their names
-            assert "%s_f<%d>" % (k, d) in r.stdout, r.stdout
-        for d in (32, 64, 128):
-            assert "%s_h<%d>" % (k, d) in r.stdout
-            assert "%s_f_h<%d>" % (k, d) in r.stdout, r.stdout
-        assert "%s_f<128>" % k not in r.stdout                 # fp32 at d = 128 does not exist, filtered or not
-    assert "k_filter_from_ids" in r.stdout
 
 
 def test_seen_prime_is_the_union():

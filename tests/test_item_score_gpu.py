@@ -131,6 +131,35 @@ def test_item_score_object_and_engine_builder_give_the_same_table():
             eng.full_rank(c["tu"], c["ti"], rows, adjust=bad)
 
 
+# ---- the dispatch: every (width, element type, filter, terms) cell -------------------------------------------------------
+
+@pytest.mark.parametrize("adjusted", [False, True], ids=["bare", "terms"])
+@pytest.mark.parametrize("filtered", [False, True], ids=["all", "half"])
+@pytest.mark.parametrize("dtype,d", CASES)
+def test_every_instantiation_is_the_one_asked_for(dtype, d, filtered, adjusted):
+    """One selector turns (d, element type, filter given, terms given) into a kernel instantiation; a cell wired to a
+    neighbour's flags is how it can go wrong.  Every cell of 5 x 2 x 2 runs full_rank, topk_items (K = 20) and user_ranks
+    on score_case (4,099 items: 129 tiles, 17 per slice, so the prefetch and the partial last tile run; 96 rows, 64 users, 40
+    held-out sets) against the CPU references -- on Seen' for the filter, on A for the terms, on S without them -- exactly.
+    That ignoring the random 50 % filter or these terms changes the references is what the host tests
+    test_filters_have_teeth_on_the_cpu_references and test_terms_have_teeth_on_the_cpu_references show; here the cell's
+    reference ranks are also checked to differ from those of the two neighbouring cells."""
+    c = dict(case(dtype, d))
+    c["rows"] = c["rows"][:96]
+    assert c["wi"].shape[0] == 4099 and len(c["held"][0]) <= 60
+    mask = random_mask(4099, 0.5, seed=7)
+
+    def reference(f, a):                                    # (Seen or Seen', S or A) of the cell (f, a)
+        return (seen_prime(c["seen"], mask, 300) if f else c["seen"]), (c["A"] if a else C.case_scores(c))
+
+    seen, A = reference(filtered, adjusted)
+    got = run_all(engine(d), c, c["seen"], mask if filtered else None, c["adj"] if adjusted else None, ks=(20,))
+    check_exact(got, c, A, seen, None, ks=(20,))
+    want = C.ref_rank(A, c["rows"], seen)
+    for other in (reference(not filtered, adjusted), reference(filtered, not adjusted)):
+        assert (C.ref_rank(other[1], c["rows"], other[0]) != want).sum() >= 48
+
+
 # ---- neutral adjust ------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("filtered", [False, True], ids=["unfiltered", "filtered"])

@@ -4,7 +4,6 @@ the proof that the terms of the GPU cases change the answers of the CPU referenc
 a fused multiply-add from a multiply followed by an add."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -117,20 +116,6 @@ def test_item_score_refuses_bad_input():
         as_score("euclid", Model())
     t = torch.zeros(2, 64)
     assert as_score(t, Model()) is t
-
-
-def test_kernel_resources_report():
-    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_resources.py"),
-                        os.path.join(REPO, "sml_amd", "csrc", "retrieval.hip")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr              # 1: a kernel spills or touches scratch
-    for k in ("k_full_rank", "k_topk_slice", "k_ur_thresholds", "k_ur_count"):
-        for f in ("false", "true"):
-            for d in (32, 64):
-                assert "%s_a<%d, %s>" % (k, d, f) in r.stdout, r.stdout
-            for d in (32, 64, 128):
-                assert "%s_a_h<%d, %s>" % (k, d, f) in r.stdout, r.stdout
-            assert "%s_a<128, %s>" % (k, f) not in r.stdout     # fp32 at d = 128 does not exist, adjusted or not
-    assert "k_adjust_fill" in r.stdout and "k_adjust_cosine<32>" in r.stdout and "k_adjust_cosine_h<128>" in r.stdout
 
 
 def test_cosine_scale_reference():

@@ -2,6 +2,7 @@
 Seen-items CSR builder, the CPU refusal of the model entry points, and the exact fp32 references (tests/_fp32_chain.py)
 the GPU tests compare with: fma32 against rational arithmetic, the filtered references against brute force, and the
 proof that the GPU tests' data separates the kernels' chain order from other orders."""
+import functools
 import os
 import subprocess
 import sys
@@ -30,12 +31,35 @@ def test_abi_surface():
     assert "retrieval.hip" in build.SOURCES
 
 
+@functools.lru_cache(maxsize=None)
+def _resources_report():
+    """tools/kernel_resources.py over retrieval.hip, run once for the tests below."""
+    return subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_resources.py"),
+                           os.path.join(REPO, "sml_amd", "csrc", "retrieval.hip")], capture_output=True, text=True)
+
+
 def test_kernel_resources_report():
-    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_resources.py"),
-                        os.path.join(REPO, "sml_amd", "csrc", "retrieval.hip")], capture_output=True, text=True)
+    r = _resources_report()
     assert r.returncode == 0, r.stdout + r.stderr
-    for k in ("k_full_rank<32>", "k_full_rank<64>", "k_topk_slice<32>", "k_topk_slice<64>", "k_topk_merge"):
+    for k in ("k_full_rank<32, float, false, false>", "k_full_rank<64, float, false, false>", "k_topk_slice<32, float, false, false>",
+              "k_topk_slice<64, float, false, false>", "k_topk_merge"):
         assert k in r.stdout, r.stdout
+
+
+def test_retrieval_kernel_instantiations_report():
+    """Every table-reading kernel is one template k_x<D, T, F, A>: all 20 instantiations of each family exist, fp32 at
+    d = 128 exists nowhere, and no kernel of the file spills or touches scratch (the tool's exit code)."""
+    r = _resources_report()
+    assert r.returncode == 0, r.stdout + r.stderr              # 1: a kernel spills or touches scratch
+    names = {line.split("  ")[0] for line in r.stdout.splitlines()}
+    for k in ("k_full_rank", "k_topk_slice", "k_ur_thresholds", "k_ur_count"):
+        want = {"%s<%d, %s, %s, %s>" % (k, d, t, f, a) for t, ds in (("float", (32, 64)), ("half", (32, 64, 128))) for d in ds
+                for f in ("false", "true") for a in ("false", "true")}
+        assert len(want) == 20 and want <= names, (sorted(want - names), r.stdout)
+        assert {n for n in names if n.startswith(k + "<")} == want, r.stdout      # nothing else: no fp32 at 128, no stray form
+    assert "<128, float" not in r.stdout
+    for k in ("k_filter_from_ids", "k_adjust_fill", "k_adjust_cosine<32, float>", "k_adjust_cosine<128, half>"):
+        assert k in names, r.stdout
 
 
 def _pairs(rng, m, U, I):
