@@ -671,6 +671,42 @@ int sml_weighted_epoch(sml_ctx* ctx, const int64_t* rows, int64_t n, const int32
                        const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t n_out, uint64_t seed,
                        int64_t* out3, int32_t* failed, void* stream);
 
+/* ---- interaction sets ------------------------------------------------------------------ */
+/* A set over (n_user, n_item), 0 < n_user < 2^31, 0 < n_item < 2^31, is exactly the Seen CSR of the retrieval section:
+ *   off    int64 [n_user + 1], off[0] = 0
+ *   items  int32 [nnz], ascending and unique inside each user's range [off[u], off[u + 1])
+ * so every output of these calls goes to sml_full_rank*, sml_topk_items* and sml_user_rank* as seen_off / seen_items or
+ * pos_off / pos_items without a copy.  m, nnz < 2^31.  Indices are trusted on the device, like every other index of the
+ * library (sml_amd.retrieval.DeviceSeen range-checks them).
+ *
+ * Rules for all of them: integer work only; the output bytes are the same whatever the schedule (the only atomics are
+ * order-free digit counters in LDS); no workgroup waits on another -- every dependency is a launch boundary, so the
+ * calls suit hipGraph capture; the launch functions do no allocation, no copy to the host and no synchronise: the
+ * workspace is the caller's `scratch` (16-byte aligned base; contents not needed afterwards; the _scratch_bytes calls
+ * return its size, < 0: bad argument).  All pointers are device memory.  Asynchronous.
+ *
+ * sml_iset_build: rows int64 [m, n_cols >= 2], column 0 the user, column 1 the item, further columns ignored (a test
+ *   period's rows with their sampled negatives go in as they are).  Duplicates are allowed, in any order; m = 0 is
+ *   allowed.  Writes all of off [n_user + 1] and items[0 .. nnz), nnz = off[n_user] = the number of distinct pairs.  The
+ *   caller gives `items` room for m entries; entries past nnz are unspecified.  A stable LSD radix sort by item and then
+ *   by user (8 bits per pass, only the passes that cover n_item - 1 and n_user - 1), adjacent-unique flags, one scan.
+ * sml_iset_union: out = the union of a and b, user by user, in the same format.  out_items has room for nnz_a + nnz_b
+ *   (nnz_a = a_off[n_user], nnz_b = b_off[n_user], given by the caller); entries past out_off[n_user] are unspecified.
+ *   Outputs must not alias inputs: overlap of an output with an input is refused where the pointers show it.  Either
+ *   side may be empty (its items pointer may then be NULL).  Element-parallel: every element of b bisects its user's
+ *   range of a, every element of a its user's range of b, and each computes its output slot; nobody walks a range.
+ *   One call reads and writes O(nnz_a + nnz_b): the history is copied once per union.
+ * sml_iset_contains: rows as above; out uint8 [m] is 1 exactly when (rows[r][0], rows[r][1]) is in the set. */
+int64_t sml_iset_build_scratch_bytes(sml_ctx* ctx, int64_t m, int64_t n_user, int64_t n_item);
+int sml_iset_build(sml_ctx* ctx, const int64_t* rows, int64_t m, int n_cols, int64_t n_user, int64_t n_item, void* scratch,
+                   int64_t* off, int32_t* items, void* stream);
+int64_t sml_iset_union_scratch_bytes(sml_ctx* ctx, int64_t nnz_a, int64_t nnz_b, int64_t n_user);
+int sml_iset_union(sml_ctx* ctx, int64_t n_user, const int64_t* a_off, const int32_t* a_items, int64_t nnz_a,
+                   const int64_t* b_off, const int32_t* b_items, int64_t nnz_b, void* scratch,
+                   int64_t* out_off, int32_t* out_items, void* stream);
+int sml_iset_contains(sml_ctx* ctx, const int64_t* rows, int64_t m, int n_cols, const int64_t* off, const int32_t* items,
+                      uint8_t* out, void* stream);
+
 /* ---- host helper: batch supply ------------------------------------------------------- */
 /* Sequential rejection sampling of offlineDataset_withsample.__getitem__ (reference
  * data/dataset.py:63-71) over a pre-drawn candidate stream, on the HOST (no GPU involved):

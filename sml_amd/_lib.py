@@ -190,6 +190,13 @@ SIGNATURES = {
                                         c_void]),
     "sml_weighted_epoch": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64,
                                           c_void, ctypes.c_int64, ctypes.c_uint64, c_void, c_void, c_void]),
+    "sml_iset_build_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "sml_iset_build": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_void, c_void, c_void,
+                                      c_void]),
+    "sml_iset_union_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "sml_iset_union": (ctypes.c_int, [c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64, c_void,
+                                      c_void, c_void, c_void]),
+    "sml_iset_contains": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void, c_void, c_void]),
     "sml_selftest": (ctypes.c_int, [ctypes.c_int]),
 }
 

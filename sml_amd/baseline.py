@@ -20,6 +20,9 @@ lines so its recorded runs (fixtures G10 and G16) replay against them:
 - `SPMF.run_one_stage2` (model/baseline.py:306-386), the fine-tune / full-retrain inner loop (G10).
 - `base_train_not_train`, `run` with its summary lines, and `main()` (model/baseline.py:149-160, 505-671): the
   `--method full|fine|spmf` program, plus `--device_batches` and `--pre_model ''` (no checkpoint: fresh tables).
+- `--full_eval 1` (an extension): after the final test line of a stage, `SPMF.full_test` ranks every test user's held-out
+  set against the whole catalogue minus the training history (a retrieval.DeviceSeen grown by one period per stage) and
+  one `full-catalogue test---` line is printed.  No RNG draw: the training trajectory is the one without the flag.
 
 Reference defects resolved here: `run_one_stage` unpacks two values from `test`, which returns four (the reference's
 SPMF path raises as committed): the first two are taken.  `__main__` passes an undefined `start_idx` to
@@ -146,6 +149,8 @@ class SPMF(object):
         self._order = None                          # device rank order of the stage's rows (device_batches)
         self.engine = engine if engine is not None else get_engine(self.device, laten_dim, max(int(args.batch_size), 4096))
         self.MFbase._sml_engine = self.engine
+        self.full_eval = int(getattr(args, "full_eval", 0) or 0)
+        self._seen, self._seen_periods = None, 0    # full_eval: train/0 .. train/(_seen_periods - 1) as a DeviceSeen
 
     def get_next_data(self, stage_id, types="only_new"):
         return self.dataset.get_next(stage_id, types=types)
@@ -192,11 +197,32 @@ class SPMF(object):
         rec, nd, hit_u, hit_i = self.test(now_test)
         print("max result ", best[1], best[2])
         show("FInal test---", rec, nd, "hit user:", hit_u, "hit item:", hit_i)
+        self._show_full(stage_id, now_test)
         self.recall.append(rec)
         self.ndcg.append(nd)
         self.hit_new_user.append(hit_u)
         self.hit_new_item.append(hit_i)
         return True
+
+    def full_test(self, stage_id, now_test, topk=(5, 10, 20)):
+        """evaluation.test_model_users of the period's test rows over the whole catalogue minus everything trained on so
+        far: Seen = train/0 .. train/(stage_id - 1), held on the device and grown by the periods' files that are new since
+        the last call (one per stage in a run).  Makes no RNG draw."""
+        from .evaluation import test_model_users
+        from .retrieval import DeviceSeen
+        if self._seen is None:
+            self._seen = DeviceSeen(self.user_num, self.item_num, self.engine)
+        for p in range(self._seen_periods, stage_id):
+            self._seen.add(np.load(self.dataset.path + "train/" + str(p) + ".npy")[:, :2])
+        self._seen_periods = max(self._seen_periods, stage_id)
+        return test_model_users(self.MFbase, now_test, seen=self._seen, topK=topk)
+
+    def _show_full(self, stage_id, now_test, topk=(5, 10, 20)):
+        if not self.full_eval:
+            return
+        res = self.full_test(stage_id, now_test, topk)
+        print("full-catalogue test---", "recall(5,10,20):", np.array([res["recall"][k] for k in topk]),
+              "ndcg (5,10,20):", np.array([res["ndcg"][k] for k in topk]), "users:", res["users"])
 
     def test(self, test_data, topk=(5, 10, 20)):
         """(recall@k, ndcg@k for every k, share of @topk[-1] hits on new users, ... on new items) over the period's
@@ -339,6 +365,7 @@ class SPMF(object):
         self.updata_reservious(set_t)
         rec, nd, hit_u, hit_i = self.test(now_test)
         show("FInal test---", rec, nd, "hit new user:", hit_u, "hit new item:", hit_i)
+        self._show_full(stage_id, now_test)
         self.recall.append(rec)
         self.ndcg.append(nd)
         return True
@@ -395,7 +422,7 @@ class SPMF(object):
 
 
 def get_parse():
-    """The reference's flags (model/baseline.py:592-626) plus --device_batches."""
+    """The reference's flags (model/baseline.py:592-626) plus --device_batches and --full_eval."""
     parser = argparse.ArgumentParser(description='MF and TR parameters.')
     parser.add_argument('--lr', type=float, default=0.01, help='Learning rate.')
     parser.add_argument('--l2_u', type=float, default=1e-5, help='user l2. should be same to l2_i')
@@ -417,6 +444,8 @@ def get_parse():
     parser.add_argument('--start_idx', type=int, default=30, help='retraining from which period: yelp 30, news(adressa) 48')
     # extension (not a reference flag): SPMF batches drawn on the device -- the same distribution, not the same numpy stream
     parser.add_argument('--device_batches', type=int, default=0, help='1: draw the SPMF epochs on the device (not stream-exact)')
+    parser.add_argument('--full_eval', type=int, default=0,
+                        help='1: after each stage also print the all-ranking metrics over the whole catalogue minus the history')
     return parser
 
 

@@ -2308,6 +2308,67 @@ int sml_weighted_epoch(sml_ctx* ctx, const int64_t* rows, int64_t n, const int32
     return SML_OK;
 }
 
+// ---- interaction sets (interaction_set.hip) ----
+static bool iset_dims_ok(int64_t n_user, int64_t n_item) {
+    return n_user > 0 && n_user < ((int64_t)1 << 31) && n_item > 0 && n_item < ((int64_t)1 << 31);
+}
+static bool iset_count_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 31); }
+static bool iset_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
+    const char *a = (const char*)p, *b = (const char*)q;
+    return a && b && p_bytes > 0 && q_bytes > 0 && a < b + q_bytes && b < a + p_bytes;
+}
+
+int64_t sml_iset_build_scratch_bytes(sml_ctx* ctx, int64_t m, int64_t n_user, int64_t n_item) {
+    if (!ctx || !iset_count_ok(m) || !iset_dims_ok(n_user, n_item))
+        return fail(SML_EINVAL, "sml_iset_build_scratch_bytes", "bad argument (0 <= m < 2^31, 0 < n_user, n_item < 2^31)");
+    return sml_iset_build_scratch_size(m);
+}
+
+int sml_iset_build(sml_ctx* ctx, const int64_t* rows, int64_t m, int n_cols, int64_t n_user, int64_t n_item, void* scratch,
+                   int64_t* off, int32_t* items, void* stream) {
+    if (!ctx || !iset_count_ok(m) || n_cols < 2 || !iset_dims_ok(n_user, n_item))
+        return fail(SML_EINVAL, "sml_iset_build", "bad argument (0 <= m < 2^31, n_cols >= 2, 0 < n_user, n_item < 2^31)");
+    if (!scratch || !off || (m && (!rows || !items))) return fail(SML_EINVAL, "sml_iset_build", "null argument");
+    if (((uintptr_t)scratch & 15) != 0) return fail(SML_EINVAL, "sml_iset_build", "scratch must be 16-byte aligned");
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_iset_build(rows, m, n_cols, n_user, n_item, scratch, off, items, st)));
+    return SML_OK;
+}
+
+int64_t sml_iset_union_scratch_bytes(sml_ctx* ctx, int64_t nnz_a, int64_t nnz_b, int64_t n_user) {
+    if (!ctx || !iset_count_ok(nnz_a) || !iset_count_ok(nnz_b) || !iset_count_ok(nnz_a + nnz_b) || !iset_dims_ok(n_user, 1))
+        return fail(SML_EINVAL, "sml_iset_union_scratch_bytes", "bad argument (0 <= nnz_a, nnz_b, nnz_a + nnz_b < 2^31, 0 < n_user < 2^31)");
+    return sml_iset_union_scratch_size(nnz_b);
+}
+
+int sml_iset_union(sml_ctx* ctx, int64_t n_user, const int64_t* a_off, const int32_t* a_items, int64_t nnz_a, const int64_t* b_off,
+                   const int32_t* b_items, int64_t nnz_b, void* scratch, int64_t* out_off, int32_t* out_items, void* stream) {
+    if (!ctx || !iset_count_ok(nnz_a) || !iset_count_ok(nnz_b) || !iset_count_ok(nnz_a + nnz_b) || !iset_dims_ok(n_user, 1))
+        return fail(SML_EINVAL, "sml_iset_union", "bad argument (0 <= nnz_a, nnz_b, nnz_a + nnz_b < 2^31, 0 < n_user < 2^31)");
+    if (!scratch || !a_off || !b_off || !out_off || (nnz_a && !a_items) || (nnz_b && !b_items) || ((nnz_a + nnz_b) && !out_items))
+        return fail(SML_EINVAL, "sml_iset_union", "null argument");
+    if (((uintptr_t)scratch & 15) != 0) return fail(SML_EINVAL, "sml_iset_union", "scratch must be 16-byte aligned");
+    const int64_t off_bytes = 8 * (n_user + 1), out_bytes = 4 * (nnz_a + nnz_b);
+    if (iset_overlap(out_off, off_bytes, a_off, off_bytes) || iset_overlap(out_off, off_bytes, b_off, off_bytes) ||
+        iset_overlap(out_items, out_bytes, a_items, 4 * nnz_a) || iset_overlap(out_items, out_bytes, b_items, 4 * nnz_b) ||
+        iset_overlap(out_off, off_bytes, a_items, 4 * nnz_a) || iset_overlap(out_off, off_bytes, b_items, 4 * nnz_b) ||
+        iset_overlap(out_items, out_bytes, a_off, off_bytes) || iset_overlap(out_items, out_bytes, b_off, off_bytes))
+        return fail(SML_EINVAL, "sml_iset_union", "an output overlaps an input");
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_iset_union(n_user, a_off, a_items, nnz_a, b_off, b_items, nnz_b, scratch, out_off, out_items, st)));
+    return SML_OK;
+}
+
+int sml_iset_contains(sml_ctx* ctx, const int64_t* rows, int64_t m, int n_cols, const int64_t* off, const int32_t* items, uint8_t* out,
+                      void* stream) {
+    if (!ctx || !iset_count_ok(m) || n_cols < 2) return fail(SML_EINVAL, "sml_iset_contains", "bad argument (0 <= m < 2^31, n_cols >= 2)");
+    if (m == 0) return SML_OK;
+    if (!rows || !off || !out) return fail(SML_EINVAL, "sml_iset_contains", "null argument");
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_iset_contains(rows, m, n_cols, off, items, out, st)));
+    return SML_OK;
+}
+
 int sml_host_resolve_negatives_csr(const int64_t* users, int64_t n, const int64_t* cand, int64_t m,
                                    const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t* negs,
                                    int64_t* consumed, int64_t* resolved) {

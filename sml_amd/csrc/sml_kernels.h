@@ -450,3 +450,13 @@ hipError_t sml_launch_rank_weights(int d, const float* wu, const float* wi, cons
 hipError_t sml_launch_weighted_epoch(const int64_t* rows, int64_t n, const int32_t* order, const int64_t* item_all, int64_t pop,
                                      const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t n_out,
                                      uint64_t seed, int64_t* out3, int* failed, hipStream_t st);
+// interaction_set.hip: build / union / membership of the Seen CSR (m, nnz < 2^31; no allocation, copy or synchronise)
+int64_t sml_iset_build_scratch_size(int64_t m);
+int64_t sml_iset_union_scratch_size(int64_t nnz_b);
+hipError_t sml_launch_iset_build(const int64_t* rows, int64_t m, int n_cols, int64_t n_user, int64_t n_item, void* scratch,
+                                 int64_t* off, int32_t* items, hipStream_t st);
+hipError_t sml_launch_iset_union(int64_t n_user, const int64_t* a_off, const int32_t* a_items, int64_t nnz_a, const int64_t* b_off,
+                                 const int32_t* b_items, int64_t nnz_b, void* scratch, int64_t* out_off, int32_t* out_items,
+                                 hipStream_t st);
+hipError_t sml_launch_iset_contains(const int64_t* rows, int64_t m, int n_cols, const int64_t* off, const int32_t* items, uint8_t* out,
+                                    hipStream_t st);

@@ -586,6 +586,61 @@ class HipEngine(object):
               "sml_weighted_epoch")
         return out, failed
 
+    # ------------------------------------------------------------------ interaction sets (interaction_set.hip)
+    def _iset_rows(self, rows):
+        rows = self._dev(rows, torch.int64)
+        if rows.dim() != 2 or rows.shape[1] < 2:
+            raise ValueError("expected (user, item) rows [m, >= 2], got shape %s" % (tuple(rows.shape),))
+        return rows
+
+    def _iset(self, s):
+        off, items = self._dev(s[0], torch.int64), self._dev(s[1], torch.int32)
+        return off, items, int(items.shape[0])
+
+    def _scratch(self, nbytes, what):
+        if nbytes < 0:
+            check(-1, what)
+        return torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
+
+    def iset_build(self, rows, n_user, n_item):
+        """The set of the distinct (user, item) pairs of rows int [m, >= 2] (columns 0 and 1; duplicates allowed, any
+        order, m = 0 allowed; a device tensor or a host array) as the Seen CSR on the device (sml_iset_build): (off int64
+        [n_user + 1], items int32 [nnz]).  The ids are trusted: DeviceSeen.add checks their range.  One scalar (nnz) is read
+        back to trim `items`."""
+        rows = self._iset_rows(rows)
+        m, n_user, n_item = rows.shape[0], int(n_user), int(n_item)
+        scratch = self._scratch(self.lib.sml_iset_build_scratch_bytes(self._ctx, m, n_user, n_item), "sml_iset_build_scratch_bytes")
+        off = torch.empty(n_user + 1, device=self.device, dtype=torch.int64)
+        items = torch.empty(m, device=self.device, dtype=torch.int32)
+        check(self.lib.sml_iset_build(self._ctx, _ptr(rows), m, rows.shape[1], n_user, n_item, _ptr(scratch), _ptr(off), _ptr(items),
+                                      self._stream()), "sml_iset_build")
+        return off, items[:int(off[-1])] if m else items
+
+    def iset_union(self, a, b, n_user):
+        """The union, user by user, of two sets (off, items) over n_user users (sml_iset_union) as a new pair; the inputs
+        are left alone.  `items` of each input holds exactly its nnz entries.  One scalar (the new nnz) is read back."""
+        n_user = int(n_user)
+        a_off, a_items, nnz_a = self._iset(a)
+        b_off, b_items, nnz_b = self._iset(b)
+        if a_off.shape[0] != n_user + 1 or b_off.shape[0] != n_user + 1:
+            raise ValueError("iset_union: both sets must be over %d users" % n_user)
+        scratch = self._scratch(self.lib.sml_iset_union_scratch_bytes(self._ctx, nnz_a, nnz_b, n_user), "sml_iset_union_scratch_bytes")
+        off = torch.empty(n_user + 1, device=self.device, dtype=torch.int64)
+        items = torch.empty(nnz_a + nnz_b, device=self.device, dtype=torch.int32)
+        check(self.lib.sml_iset_union(self._ctx, n_user, _ptr(a_off), _ptr(a_items), nnz_a, _ptr(b_off), _ptr(b_items), nnz_b,
+                                      _ptr(scratch), _ptr(off), _ptr(items), self._stream()), "sml_iset_union")
+        return off, items[:int(off[-1])] if nnz_a + nnz_b else items
+
+    def iset_contains(self, rows, s):
+        """bool tensor [m]: whether (rows[r][0], rows[r][1]) is in the set s = (off, items) (sml_iset_contains).  The ids
+        are trusted: the users must be inside the set's user range."""
+        rows = self._iset_rows(rows)
+        off, items, _ = self._iset(s)
+        out = torch.empty(rows.shape[0], device=self.device, dtype=torch.uint8)
+        check(self.lib.sml_iset_contains(self._ctx, _ptr(rows), rows.shape[0], rows.shape[1], _ptr(off), _ptr(items), _ptr(out),
+                                         self._stream()), "sml_iset_contains")
+        return out.bool()
+
     # ------------------------------------------------------------------ a2
     def mf_forward(self, w_user, w_item, user, item, norm=False):
         wu, wi = self._table(w_user), self._table(w_item)

@@ -8,6 +8,7 @@ the user interacted with in earlier periods) as a CSR over users:
     seen_items  int32, ascending and unique inside each user's range [seen_off[u], seen_off[u + 1])
 
 It is built on the host with numpy (a unique over the key u * n_item + i) and touches no random number generator.
+DeviceSeen has the same surface with the set built and grown on the device (the interaction-set calls of include/sml_hip.h).
 
 ItemFilter restricts a call to a subset of the catalogue, for every user alike: a bitmap over the items,
 
@@ -85,6 +86,93 @@ class SeenItems(object):
         return seen
 
 
+class DeviceSeen(object):
+    """SeenItems with the set resident on the device: the CSR is built and grown there (HipEngine.iset_build /
+    iset_union, include/sml_hip.h "interaction sets"), so one add moves at most the pairs themselves to the device and
+    reads back a few scalars (the range check, the new nnz); no CSR crosses the bus in either direction.  For any sequence
+    of add calls host() equals SeenItems.host() after the same calls, byte for byte.  Any engine of the device serves: the
+    set kernels do not depend on its d."""
+
+    def __init__(self, n_user, n_item, engine):
+        self.n_user, self.n_item, self.engine = int(n_user), int(n_item), engine
+        if not (0 < self.n_user < 2 ** 31 and 0 < self.n_item < 2 ** 31):
+            raise ValueError("n_user and n_item must be in (0, 2^31), got %d, %d" % (self.n_user, self.n_item))
+        self._off = torch.zeros(self.n_user + 1, device=engine.device, dtype=torch.int64)
+        self._items = torch.empty(0, device=engine.device, dtype=torch.int32)
+
+    def _rows(self, pairs):
+        """pairs (host array or tensor [m, >= 2]) as checked device rows int64, or None when there are none."""
+        if not torch.is_tensor(pairs):
+            pairs = np.asarray(pairs)
+        if (pairs.numel() if torch.is_tensor(pairs) else pairs.size) == 0:
+            return None
+        if pairs.ndim != 2 or pairs.shape[1] < 2:
+            raise ValueError("expected (user, item) pairs [m, 2], got shape %s" % (tuple(pairs.shape),))
+        if not (torch.is_tensor(pairs) and pairs.device == self.engine.device):
+            pairs = pairs[:, :2]                 # only the two columns cross the bus
+        rows = self.engine._dev(pairs, torch.int64)
+        lo, hi = torch.aminmax(rows[:, :2], dim=0)
+        u0, i0, u1, i1 = torch.cat([lo, hi]).tolist()        # the one read-back of the check
+        if u0 < 0 or u1 >= self.n_user or i0 < 0 or i1 >= self.n_item:
+            raise ValueError("pair out of range (n_user=%d, n_item=%d)" % (self.n_user, self.n_item))
+        return rows
+
+    def add(self, pairs):
+        """Union in an int array or tensor [m, >= 2] of (user, item) rows, on the host or already on the device (a
+        DeviceRows' .rows works; further columns are ignored); duplicates are allowed."""
+        rows = self._rows(pairs)
+        if rows is None:
+            return self
+        new = self.engine.iset_build(rows, self.n_user, self.n_item)
+        self._off, self._items = new if len(self) == 0 else self.engine.iset_union((self._off, self._items), new, self.n_user)
+        return self
+
+    def device(self, device=None):
+        """(seen_off, seen_items) on the engine's device; seen_items is trimmed to nnz (one entry when empty, as the
+        retrieval calls expect both arrays)."""
+        if device is not None:
+            d = torch.device(device)
+            if d.type != self.engine.device.type or (d.index is not None and d.index != self.engine.device.index):
+                raise ValueError("this DeviceSeen lives on %s, not on %s" % (self.engine.device, d))
+        items = self._items if len(self) else torch.zeros(1, device=self.engine.device, dtype=torch.int32)
+        return self._off, items
+
+    def host(self):
+        """(seen_off int64 [n_user + 1], seen_items int32) numpy arrays: the pair SeenItems.host() returns."""
+        return self._off.cpu().numpy(), self._items.cpu().numpy()
+
+    def __len__(self):
+        return int(self._items.shape[0])
+
+    def contains(self, pairs):
+        """bool tensor [m] on the device: whether each (user, item) row of `pairs` is in the set."""
+        rows = self._rows(pairs)
+        if rows is None:
+            return torch.zeros(0, device=self.engine.device, dtype=torch.bool)
+        return self.engine.iset_contains(rows, (self._off, self._items))
+
+    @classmethod
+    def from_periods(cls, root, name, periods, engine, n_user=None, n_item=None):
+        """SeenItems.from_periods with the set on the engine's device: one add per period's train/<p>.npy."""
+        base = os.path.join(root, name)
+        if n_user is None or n_item is None:
+            info = np.load(os.path.join(base, "information.npy"))
+            n_user = int(info[1]) if n_user is None else n_user
+            n_item = int(info[2]) if n_item is None else n_item
+        seen = cls(n_user, n_item, engine)
+        for p in periods:
+            seen.add(np.load(os.path.join(base, "train", "%d.npy" % p))[:, :2])
+        return seen
+
+    @classmethod
+    def from_seen(cls, seen, engine):
+        """Continue from a host SeenItems: its CSR is uploaded once."""
+        out = cls(seen.n_user, seen.n_item, engine)
+        off, items = seen.host()
+        out._off, out._items = engine._dev(off, torch.int64), engine._dev(items, torch.int32)
+        return out
+
+
 def held_out(pairs, n_user, n_item):
     """T(u), the held-out items of every user of a test period: the (user, item) columns of `pairs` [m, >= 2] (further
     columns, e.g. sampled negatives, are ignored) as a SeenItems -- a per-user ascending, duplicate-free CSR."""
@@ -95,7 +183,7 @@ def held_out(pairs, n_user, n_item):
 def nonempty_users(sets):
     """(users int64 [n], pos_off int64 [n + 1], pos_items int32 [n_pos]) of the users with at least one item in `sets` (a
     SeenItems or a (off, items) CSR over all users), ascending by user: what HipEngine.user_ranks takes."""
-    off, items = sets.host() if isinstance(sets, SeenItems) else \
+    off, items = sets.host() if isinstance(sets, (SeenItems, DeviceSeen)) else \
         (np.asarray(t.cpu() if torch.is_tensor(t) else t) for t in sets)
     off = np.asarray(off, dtype=np.int64)
     users = np.nonzero(np.diff(off) > 0)[0].astype(np.int64)
@@ -105,10 +193,10 @@ def nonempty_users(sets):
 
 
 def as_csr(exclude, device):
-    """exclude: None, a SeenItems, or a (seen_off, seen_items) pair -> what the engine's retrieval calls take."""
+    """exclude: None, a SeenItems, a DeviceSeen, or a (seen_off, seen_items) pair -> what the engine's retrieval calls take."""
     if exclude is None:
         return None
-    if isinstance(exclude, SeenItems):
+    if isinstance(exclude, (SeenItems, DeviceSeen)):
         return exclude.device(device)
     off, items = exclude
     return torch.as_tensor(off), torch.as_tensor(items)
