@@ -117,7 +117,7 @@ int sml_comm_allgather(sml_ctx* ctx, const float* src, float* dst, int64_t n_per
  *             device.  One process per GPU: export with sml_peer_export (hipIpcGetMemHandle; dmabuf IPC:
  *             HSA_ENABLE_IPC_MODE_LEGACY=0), all-gather the 64-byte handles by any means, sml_peer_open them
  *             (hipIpcOpenMemHandle).  Several ranks inside one process (tests on one GPU): pass the allocations.
- *   push      TR stage: k_transfer_wgrad's epilogue stores every finished gradient tile into slot [step & 1][rank]
+ *   push      TR stage: the epilogue of k_tr_wgrad2's tile workgroups stores every finished gradient tile into slot [step & 1][rank]
  *             of EVERY rank's inbox (system-scope write-through stores), then one system-scope counter increment
  *             per workgroup and destination.  MF stage / bare step: a copy kernel pushes the rank's item-gradient
  *             rows the same way.

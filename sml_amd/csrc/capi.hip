@@ -968,7 +968,7 @@ int sml_transfer_forward(sml_ctx* ctx, const float* theta, int net, const float*
     hipStream_t st = (hipStream_t)stream;
     int rc = ensure_pk(ctx); if (rc) return rc;
     // table-sized calls at d = 32: the bf16x3 kernel (fp32-grade results on the bf16 matrix rate; SML_FWD_BX3=0: the fp32 products)
-    const size_t bx3 = n_rows > 8192 && env_int("SML_FWD_BX3", 1) != 0 && env_int("SML_FWD_MT", 0) == 0 ? sml_bx3_bytes(ctx->d) : 0;
+    const size_t bx3 = n_rows > 8192 && env_int("SML_FWD_BX3", 1) != 0 ? sml_bx3_bytes(ctx->d) : 0;
     if (bx3) {
         HIPCHK(ctx->pkx.ensure(bx3 / sizeof(float) + 4));
         PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack_bx3(ctx->d, theta, ctx->pkx.p, st)));
@@ -990,10 +990,8 @@ int sml_transfer_forward(sml_ctx* ctx, const float* theta, int net, const float*
     s.xt_tab = x_t; s.xh_tab = x_hat; s.n_rows = (int)n_rows; s.out = out;
     a.k2 = ctx->variant == 1; a.unit_rows = (ctx->variant == 1 && net == 0);
     // table-sized calls are bound by streaming the weights through L2 once per workgroup: 32 rows per workgroup
-    // halve that traffic, 48 (d = 32: what the LDS tiles allow) cut it to a third
-    // (SML_FWD_MT overrides for measurements: 3 = the 48-row one-workgroup-per-CU form at d = 32)
-    const int mt_env = env_int("SML_FWD_MT", 0);
-    const int mt = n_rows > 8192 ? ((mt_env == 3 && ctx->d == 32) ? 3 : 2) : 1;
+    // halve that traffic
+    const int mt = n_rows > 8192 ? 2 : 1;
     a.tiles0 = wg_tiles((int)n_rows, mt);
     a.seg[1] = s; a.seg[1].n_rows = 0;
     const bool side = ctx->side && mt == 2 && (ctx->d == 32 || ctx->d == 64);
@@ -1229,11 +1227,20 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
     const bool clip = ctx->clip_max_norm > 0.0f;
     if (clip) HIPCHK(ctx->clip_sumsq.ensure(4));
     float* grad = theta_grad ? theta_grad : ctx->grad.p;
-    const int fns = fwd_split(wg_tiles(batch, 1) + wg_tiles(2 * batch, 1)), bsplit = bwd_split(wg_tiles(batch, 1) + wg_tiles(2 * batch, 1));
-    const int cs = bsplit ? d / 16 : 1;                                 // backward workgroups per row tile
-    // Restructured step (default): backward head (loss -> dOut -> dZ1) + ONE launch with the weight-gradient tiles and
-    // the rest of the backward beside them.  SML_TR_V2=0 runs the round-2 kernels (k_transfer_bwd + k_transfer_wgrad).
-    const bool v2 = env_int("SML_TR_V2", 1) != 0;
+    const int fns = fwd_split(wg_tiles(batch, 1) + wg_tiles(2 * batch, 1));
+    // The step: forward, backward head (loss -> dOut -> dZ1), then ONE launch with the weight-gradient tiles and the rest of
+    // the backward beside them.  What follows the gradient is one of three forms, fixed for the epoch:
+    //   PEER   peer mappings attached: the tile workgroups store their finished tiles into every rank's inbox; the Adam
+    //          launch polls this rank's counters and adds the slots in rank order
+    //   FUSED  one GPU: the tile workgroups take the Adam step for the weights they own
+    //   FLAT   a hook, a communicator or --clip_grad on one GPU: the launch leaves the flat gradient complete; exchange
+    //          and / or norm, then one Adam launch
+    enum { PEER, FUSED, FLAT };
+    const bool native = !grad_hook && ctx->peer.world <= 0 && ctx->comm != nullptr;      // a communicator exists: exchange natively
+    const int form = (!grad_hook && ctx->peer.world > 0) ? PEER : (!grad_hook && !native && !clip) ? FUSED : FLAT;
+    // (PEER / FUSED without clipping and with no gradient buffer asked for: the flat gradient is not written at all --
+    // 0.8 MB less for the launch to leave dirty in L2)
+    const bool write_grad = form == FLAT || clip || theta_grad != nullptr;
     const int lstride = (wg_tiles(batch, 1) + wg_tiles(2 * batch, 1)) * (d / 16 > 4 ? d / 16 : 4);
     const int64_t out_pstride = (int64_t)SML_R * (tiles_of(batch) + tiles_of(2 * batch)) * d;
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
@@ -1241,15 +1248,14 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
     HIPCHK(hipMemsetAsync(ctx->loss_part.p, 0, (size_t)nb * lstride * sizeof(float), st));
     HIPCHK(hipMemsetAsync(grad, 0, (size_t)2 * sml_net_size(d) * sizeof(float), st));
     const int64_t ns = sml_net_size(d);
-    // Deferred conv step (one GPU, fused Adam, restructured step, hidden-split forward): the merged launch of every batch
+    // Deferred conv step (one GPU, fused Adam, hidden-split forward): the merged launch of every batch
     // but the epoch's last leaves the conv-gradient partials to the NEXT batch's forward, which adds them and steps the 190
     // conv parameters in its prologue (SmlFwdArgs).  SML_TR_DEFER=0: the merged launch's last tail workgroup does it.
-    const bool fused_path = !clip && !grad_hook && ctx->peer.world <= 0 && ctx->comm == nullptr;
-    const bool defer = v2 && fns == 4 && fused_path && !plan && nb > 1 && env_int("SML_TR_DEFER", 1) != 0;
+    const bool defer = fns == 4 && form == FUSED && !plan && nb > 1 && env_int("SML_TR_DEFER", 1) != 0;
     // Round 5: the forward saves z1 only; the dW2 tiles of the merged launch apply Gelu to their B operand themselves (x * sigmoid(1.702 x):
     // ten instructions on a VALU that is idle there) -- 1.5 MB less written per step, bit-identical.  SML_TR_A2_RECOMPUTE=0: the forward
     // saves Gelu(z1) as well (A/B tests)
-    const bool a2_recompute = v2 && env_int("SML_TR_A2_RECOMPUTE", 1) != 0;
+    const bool a2_recompute = env_int("SML_TR_A2_RECOMPUTE", 1) != 0;
     int prev_split = 0, prev_total = 0;
     if (defer) {
         HIPCHK(ctx->cstate.ensure((size_t)2 * 2 * 3 * SML_CG));
@@ -1279,33 +1285,24 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
             SmlWgSeg& q = wg.seg[s];
             L.fill(q, s);
             q.a2 = a2_recompute ? L.z1(s) : L.a2(s);
-            // (one GPU, Adam fused into the weight-gradient kernel, no gradient buffer asked for: the flat gradient is
-            // not written at all -- 0.8 MB less for the launch to leave dirty in L2)
-            const bool fused_only = !clip && !grad_hook && (ctx->comm == nullptr || ctx->peer.world > 0) && theta_grad == nullptr;
-            q.grad = fused_only ? nullptr : grad + s * ns;
+            q.grad = write_grad ? grad + s * ns : nullptr;
         }
         L.fill(f, out_pstride, ctx->variant == 1);
         PROFILED(PC_FWD, HIPCHK(sml_launch_fwd(d, 1, fns, f, tiles, st)));
         L.fill(w, loss_kind, fns, out_pstride);
-        w.convg_part = ctx->convg.p; w.tiles_total = tiles;
+        w.tiles_total = tiles;
         w.scale = bw.scale(b, loss_scale); w.loss_part = ctx->loss_part.p + b * lstride;
-        PROFILED(PC_BWD, if (v2) HIPCHK(sml_launch_tr_bwd_head(d, w, tiles, st)); else HIPCHK(sml_launch_bwd(d, bsplit, w, tiles, st)));
+        PROFILED(PC_BWD, HIPCHK(sml_launch_tr_bwd_head(d, w, tiles, st)));
         const SmlSched sc = sched_entry((double)lr, *step + 1 + b);
-        // (v2: tiles0 / tiles_total count ROW tiles, the first n_tail workgroups are the backward's tail)
-        const int wcs = v2 ? 1 : cs;
-        auto launch_wgrad = [&](const SmlWgArgs& g) { return v2 ? sml_launch_tr_wgrad2(d, g, st) : sml_launch_wgrad(d, g, st); };
-        wg.convg_part = ctx->convg.p; wg.tiles0 = L.tiles0 * wcs; wg.tiles_total = tiles * wcs;
+        // (tiles0 / tiles_total count ROW tiles, the first n_tail workgroups are the backward's tail)
+        wg.tiles0 = L.tiles0; wg.tiles_total = tiles;
         wg.n_tail = tiles * (d / 16) > 0 ? tiles * (d / 16) : 1; wg.convg_out = ctx->convg.p; wg.arrive = ctx->arrive.p;
         wg.defer_conv = (defer && b + 1 < nb) ? 1 : 0; wg.gelu_b = a2_recompute ? 1 : 0;
         prev_split = L.tiles0 * (d / 16); prev_total = tiles * (d / 16);
-        const bool peers = !grad_hook && ctx->peer.world > 0;       // peer mappings attached: one-shot push / poll
-        const bool native = !grad_hook && !peers && ctx->comm != nullptr;     // a communicator exists: exchange natively
-        if (peers) {
-            // the weight-gradient workgroups store their finished tiles into every rank's inbox; the Adam launch polls
-            // this rank's counters and adds the slots in rank order
+        if (form == PEER) {
             SmlThetaAdamArgs ad = theta_adam_args(ctx, theta, adam_m, adam_v, grad, weight_decay, sc);
-            peer_step(ctx, 0, v2 ? sml_wgrad2_pushers(d) : sml_wgrad_grid(d), &wg.peer, &ad.peer);
-            PROFILED(PC_WGRAD, HIPCHK(launch_wgrad(wg)));
+            peer_step(ctx, 0, sml_wgrad_tiles(d) + 1, &wg.peer, &ad.peer);      // (every tile workgroup + the last tail workgroup push)
+            PROFILED(PC_WGRAD, HIPCHK(sml_launch_tr_wgrad2(d, wg, st)));
             // every workgroup of the Adam kernel polls the counters itself (SML_PEER_POLL_IN_ADAM=0: a one-wavefront
             // k_peer_wait launch ahead of it instead -- one launch more; same results)
             static const bool poll_in_adam = env_int("SML_PEER_POLL_IN_ADAM", 1) != 0;
@@ -1321,17 +1318,15 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
                 } else if (!poll_in_adam) { HIPCHK(sml_launch_peer_wait(ad.peer, st)); ad.peer.waited = 1; }
                 HIPCHK(sml_launch_theta_adam(d, ad, st));
             });
-        } else if (!grad_hook && !native && !clip) {
-            // one GPU: the weight-gradient workgroups take the Adam step for the tiles they own
-            // (v2: the refreshed images go to the OTHER set -- the launch's tail workgroups are reading this one)
-            wg.theta = theta; wg.m = adam_m; wg.v = adam_v; wg.pk = v2 ? pk_other(ctx) : pk_cur(ctx);
+        } else if (form == FUSED) {
+            // (the refreshed images go to the OTHER set -- the launch's tail workgroups are reading this one)
+            wg.theta = theta; wg.m = adam_m; wg.v = adam_v; wg.pk = pk_other(ctx);
             wg.weight_decay = weight_decay; wg.step_size = sc.step_size; wg.bc2_sqrt = sc.bc2_sqrt;
-            PROFILED(PC_WGRAD, HIPCHK(launch_wgrad(wg)));
-            if (v2) ctx->pk_set ^= 1;
+            PROFILED(PC_WGRAD, HIPCHK(sml_launch_tr_wgrad2(d, wg, st)));
+            ctx->pk_set ^= 1;
         } else {
-            // the weight-gradient launch leaves the flat gradient complete (its conv workgroups sum the backward's
-            // partials): all-reduce it, then one Adam launch
-            PROFILED(PC_WGRAD, HIPCHK(launch_wgrad(wg)));
+            // (the last tail workgroup of the launch sums the conv-gradient partials into the flat gradient)
+            PROFILED(PC_WGRAD, HIPCHK(sml_launch_tr_wgrad2(d, wg, st)));
             SmlThetaAdamArgs ad = theta_adam_args(ctx, theta, adam_m, adam_v, grad, weight_decay, sc);
             if (native) {
                 NCCLCHK(g_rccl.AllReduce(grad, grad, (size_t)(2 * ns), ncclFloat, ncclSum, ctx->comm, st));
@@ -1397,7 +1392,7 @@ int sml_run_mf_grad(sml_ctx* ctx, const float* theta, const float* user_last, co
     w.scale = 1.0f; w.tiles_total = tiles;
     // ---- gradient w.r.t. the x_hat rows: the MF-stage backward (loss partials of this launch are the ones reported)
     if (d_user_hat || d_item_hat || !theta_grad) {
-        w.convg_part = nullptr; w.loss_part = ctx->loss_part.p;
+        w.loss_part = ctx->loss_part.p;
         SmlBwdArgs wx = w;
         wx.seg[0].dz1 = nullptr; wx.seg[1].dz1 = nullptr;
         HIPCHK(sml_launch_bwd(d, bwd_split(tiles), wx, tiles, st));
@@ -1407,10 +1402,10 @@ int sml_run_mf_grad(sml_ctx* ctx, const float* theta, const float* user_last, co
     }
     // ---- gradient w.r.t. theta: backward head + weight-gradient launch WITHOUT the fused Adam (flat gradient only)
     if (theta_grad) {
-        w.convg_part = ctx->convg.p; w.loss_part = ctx->loss_part.p + lstride;
+        w.loss_part = ctx->loss_part.p + lstride;
         w.seg[0].dx = nullptr; w.seg[1].dx = nullptr;
         HIPCHK(sml_launch_tr_bwd_head(d, w, tiles, st));
-        wg.convg_part = ctx->convg.p; wg.tiles0 = tiles0; wg.tiles_total = tiles;
+        wg.tiles0 = tiles0; wg.tiles_total = tiles;
         wg.n_tail = tiles * (d / 16); wg.convg_out = ctx->convg.p; wg.arrive = ctx->arrive.p;
         HIPCHK(hipMemsetAsync(grad, 0, (size_t)2 * ns * sizeof(float), st));       // (the conv block's alignment padding)
         HIPCHK(sml_launch_tr_wgrad2(d, wg, st));

@@ -143,7 +143,6 @@ struct SmlBwdArgs {
     const float* out_all; int B; int ioff; int kind; float scale;
     int out_np; int64_t out_pstride;   // `out_all` is the sum of out_np planes, out_pstride floats apart
     float* loss_part;        // [tiles] this batch's per-workgroup loss partials
-    float* convg_part;       // TR stage: [tiles, SML_CG] per-tile compact conv1/conv2 gradient partials; else null
     int tiles_total;         // k_tr_bwd_head: row tiles of the batch (its grid is padded to the XCD map)
 };
 
@@ -157,13 +156,13 @@ struct SmlWgArgs {
     SmlWgSeg seg[2];
     // fused Adam (single-GPU path): every workgroup owns a fully reduced tile of a weight
     // gradient, so it can take the Adam step for those weights (and refresh their operand-image
-    // entries) on the spot; two extra workgroups finish the conv parameters.  null theta: off.
+    // entries) on the spot; the last tail workgroup (or the next forward) finishes the conv parameters.  null theta: off.
     float* theta; float* m; float* v; float* pk;
-    const float* convg_part; int tiles0, tiles_total;
+    int tiles0, tiles_total;
     float weight_decay, step_size, bc2_sqrt;
     SmlPeerPush peer;        // several GPUs: every finished gradient tile is also stored into the peers' inboxes
     // k_tr_wgrad2: the first n_tail workgroups are the backward's tail (row tile tb / (d/16), coordinate slice tb % (d/16));
-    // tiles0 / tiles_total then count ROW tiles; `arrive` is a device counter (0 between launches) the tail
+    // tiles0 / tiles_total count ROW tiles; `arrive` is a device counter (0 between launches) the tail
     // workgroups use to elect the last arriver, which finishes the conv parameters
     int n_tail; float* convg_out; int* arrive;
     int defer_conv;          // k_tr_wgrad2: 1 = the tail workgroups only leave their partials; the NEXT forward finishes the conv parameters
@@ -183,11 +182,10 @@ hipError_t sml_launch_conv_state_init(int d, const float* theta, const float* m,
 hipError_t sml_launch_fwd(int d, int mt, int ns, const SmlFwdArgs& a, int tiles_total, hipStream_t st, bool side = false);
 // split != 0: d/16 workgroups per row tile (coordinate split); 0: one workgroup per row tile
 hipError_t sml_launch_bwd(int d, int split, const SmlBwdArgs& a, int tiles_total, hipStream_t st);
-hipError_t sml_launch_wgrad(int d, const SmlWgArgs& a, hipStream_t st);
-// restructured TR step: backward head (loss -> dOut -> dZ1) and the merged weight-gradient + backward-tail launch
+// TR step: backward head (loss -> dOut -> dZ1) and the merged weight-gradient + backward-tail launch
 hipError_t sml_launch_tr_bwd_head(int d, const SmlBwdArgs& a, int tiles_total, hipStream_t st);
 hipError_t sml_launch_tr_wgrad2(int d, const SmlWgArgs& a, hipStream_t st);
-int sml_wgrad2_pushers(int d);                   // counter increments one merged launch adds per destination (fixed)
+int sml_wgrad_tiles(int d);                      // weight-gradient tile workgroups of one merged launch; + 1 = the counter increments it adds per destination
 hipError_t sml_launch_theta_adam(int d, const SmlThetaAdamArgs& a, hipStream_t st);
 hipError_t sml_launch_theta_pack(int d, const float* theta, float* pk, hipStream_t st);
 // table-sized forward on bf16 products with fp32-grade results (transfer_net.hip, k_transfer_fwd_bx3): d = 32
@@ -195,7 +193,6 @@ size_t sml_bx3_bytes(int d);                     // operand images of both nets 
 hipError_t sml_launch_theta_pack_bx3(int d, const float* theta, void* pkx, hipStream_t st);
 hipError_t sml_launch_mf_fwd_bx3(int d, const SmlFwdArgs& a, const void* pkx, int tiles, hipStream_t st);      // the MF stage's 16-row forward (both nets' images)
 hipError_t sml_launch_fwd_bx3(int d, const SmlFwdArgs& a, const void* pkx_net, int tiles, hipStream_t st, bool side);
-int sml_wgrad_grid(int d);                       // workgroups (= pushers) of one weight-gradient launch
 // generic push / wait / rank-order sum over peer mappings (mf_kernels.hip)
 int sml_peer_push_blocks(long long n_floats);
 hipError_t sml_launch_peer_push(const float* src, long long n_floats, const SmlPeerPush& p, hipStream_t st);

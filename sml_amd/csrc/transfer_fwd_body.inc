@@ -36,7 +36,7 @@
     constexpr int WT_LOCAL = (NS == 4) ? SML_WT_FWD : SML_WT_FWD_LOCAL;
     // Workgroup b runs on XCD b % 8 (observed dispatch order; affinity only).  In the four-way hidden split, slice h
     // goes to XCDs {2h, 2h+1} -- the XCDs whose weight-gradient workgroups rewrote exactly that slice of the
-    // operand images in the previous batch's Adam step (k_transfer_wgrad's tile map) -- and to no other.
+    // operand images in the previous batch's Adam step (wgrad_tile's map in k_tr_wgrad2) -- and to no other.
     int tile, h;
     if constexpr (NS == 4) {
         const int x = (int)blockIdx.x % 8;

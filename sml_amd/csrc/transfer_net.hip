@@ -793,13 +793,13 @@ __device__ __forceinline__ void fused_row_update(const SmlBwdArgs& a, int sidx, 
 }
 
 // ------------------------------------------------------------------------------------
-// backward, one workgroup per row tile (batches large enough to fill the chip without the
-// coordinate split below): dOut -> (MF stage) dx_hat + l2*x_hat, or (TR stage) dZ1 rows +
-// conv-grad partials.  dx / dz1 scratch is padded to whole tiles (unconditional stores).
+// MF-stage backward, one workgroup per row tile (batches large enough to fill the chip without the
+// coordinate split below): dOut -> dx_hat + l2*x_hat.  dx scratch is padded to whole tiles
+// (unconditional stores).  (The TR stage has its own backward: k_tr_bwd_head + k_tr_wgrad2.)
 // ------------------------------------------------------------------------------------
 // (round 6: the head's first round of loads -- tile header and entries, the conv weights, the partner rows -- reads through 12
 // preloaded dwords; see k_transfer_fwd.  sml_launch_bwd fills them from the struct.)
-template <int D, int MT, bool TR>
+template <int D, int MT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_transfer_bwd_full(const SmlTileHdr* __restrict__ p_hdr, const uint2* __restrict__ p_ent,
         const float* __restrict__ p_theta, const float* __restrict__ p_out_all, int p_tiles0, int p_world, int p_tiles_live, int p_B, SmlBwdArgs a) {
     // (the struct is NOT copied and patched here as in k_transfer_fwd: SmlFusedUpdate's per-table arrays are indexed dynamically, a local
@@ -816,14 +816,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr int PSTR = K1 + 1;
     constexpr int SZ = cmax(R * S2 + R * SD, KSPL * R * PSTR);
     static_assert((K1 / 16) == 5 * TSPL, "5 column tiles per wave");
-    constexpr int CGS = 20;               // conv-grad operand row stride (16-byte aligned)
     __shared__ __attribute__((aligned(16))) float smem[SZ + 104];
-    __shared__ __attribute__((aligned(16))) float cgst[TR ? 2 * 256 * CGS : 4];   // conv-gradient operands of 256 elements (A, B)
-    __shared__ float red[TR ? 8 : 1][256];
     __shared__ float cf[4][SML_TM * MT];
     __shared__ float lred[8];
     // MF stage, distinct-row form (SmlDense): the per-occurrence dOut contributions of one chunk of the tile's entries, and the rows' entry ranges
-    constexpr bool DENSEOK = !TR && MT == 1 && D <= 64;
+    constexpr bool DENSEOK = MT == 1 && D <= 64;
     __shared__ __attribute__((aligned(16))) float Cs[DENSEOK ? SML_TILE_ENT * D : 4];
     __shared__ uint32_t rlen[16], rstart[17];
     __shared__ float Ps[DENSEOK ? 512 : 4];                       // the strided shares of a long row's sum
@@ -838,9 +835,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const SmlBwdSeg& sg = a.seg[sidx];
     const float* __restrict__ sg_theta = p_theta + (sidx ? sml_net_size(D) : 0);       // = sg_theta, from the preloaded parameter
     const int row0 = ((int)blockIdx.x - (sidx ? p_tiles0 : 0)) * R;
-    if constexpr (!TR) {
-        if (p_world > 0 && (int)blockIdx.x >= p_tiles_live) { peer_signal(a.push); return; }     // (a batch shorter than the cap)
-    }
+    if (p_world > 0 && (int)blockIdx.x >= p_tiles_live) { peer_signal(a.push); return; }     // (a batch shorter than the cap)
     if (tid < 104) cws[tid] = sg_theta[tid];
     // both GEMMs' first operand k-steps are on their way before the pair loss starts (they depend on theta alone)
 #ifndef SML_PREB
@@ -849,7 +844,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // (off: round 2 measured no gain from hoisting these under the per-occurrence pair loss; round 5 tried again under the
     // distinct-row head, which is two dependent round trips long -- issued behind the head's first loads: MF step 35.7 -> 36.7 us,
     // the per-occurrence form 38.5 -> 39.3: 28 KB of operands per wave in front of the head's second trip cost more than they hide)
-    constexpr bool PREB = (SML_PREB != 0) && (MT == 1) && (D <= 32) && !TR;
+    constexpr bool PREB = (SML_PREB != 0) && (MT == 1) && (D <= 32);
     const f32x4* __restrict__ p2b = reinterpret_cast<const f32x4*>(sg.pk + sml_pk_p2b(D));
     const f32x4* __restrict__ p1b = reinterpret_cast<const f32x4*>(sg.pk + sml_pk_p1b(D));
     auto tileA2 = [wv](int t) { return wv * 4 + t; };
@@ -1094,7 +1089,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         if (row >= sg.n_rows) g = 0.0f;
         dOs[r * SD + w] = g;
-        if (TR) sg.dout[(int64_t)row * D + w] = g;
     }
     }   // (!dense)
     // the (x_t, x_hat, x_com) rows of the tail: with one element per thread issue the loads now and
@@ -1106,7 +1100,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         x0p = x[tid % D]; x1p = x[D + tid % D]; x2p = x[2 * D + tid % D];
     }
     // MF stage, fused row update: what the step needs besides the gradient is on its way from here
-    constexpr bool FUSABLE = !TR && D <= 64;
+    constexpr bool FUSABLE = D <= 64;
     const bool fused = FUSABLE && a.fu.slot_info != nullptr;           // (kernel-uniform)
     FusedPre fpre;
     fpre.info = SML_SLOT_ONCE; fpre.trow = 0; fpre.m = fpre.v = 0.0f; fpre.r0 = make_uint4(0u, 0u, 0u, 0u); fpre.r1 = fpre.r0;
@@ -1130,7 +1124,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     z[mt][t][q] = PREB ? zpre[mt][t][q] : sg.z1[(int64_t)(row0 + mt * SML_TM + 4 * g4 + q) * SML_HID + (wv * 4 + t) * 16 + l15];
         if constexpr (PREB) mma16_ring<MT, 4, KSD, KSD, false>(acc, ringb2, dOs + l15 * SD + 4 * g4, SML_TM * SD, p2b, KSD, 0, lane, tileA2, nokofs);
         else mma16_rows<MT, 4, KSD, KSD>(acc, dOs + l15 * SD + 4 * g4, SML_TM * SD, p2b, KSD, 0, lane, tileA2);
-        float* dz1 = sg.dz1;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int n = (wv * 4 + t) * 16 + l15;
@@ -1141,7 +1134,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     const int r = mt * SML_TM + 4 * g4 + q;
                     const float dz = acc[mt][t][q] * sml_gelu_grad(z[mt][t][q]);
                     dZs[r * S2 + n] = dz;
-                    if (TR) dz1[(int64_t)(row0 + r) * SML_HID + n] = dz;
                 }
         }
     }
@@ -1170,10 +1162,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();
     TL(4);
     // ---- per-coordinate tail: Gelu'(h2) -> conv2^T -> Gelu'(h1) -> conv1^T (row 1 = x_hat)
-    // TR: the conv1/conv2 parameter gradients are ONE small matrix product over the tile's elements (see
-    // k_transfer_bwd): G = sum_e A[e]^T B[e], accumulated on MFMA across the EPT passes in four registers per
-    // wave -- not 96 per-thread accumulators (which spilled at d = 64 / 128)
-    f32x4 cgacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
     for (int q = 0; q < EPT; ++q) {
         const int e = q * 512 + tid, r = e / D, w = e % D;
@@ -1204,76 +1192,36 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             dh1p[c] = s * sml_gelu_grad(p.h1p[c]);
             dxh += dh1p[c] * cws[SML_OFF_C1W + c * 3 + 1];
         }
-        if constexpr (!TR) {
-            if constexpr (DENSEOK) {
-                if (dense) {
-                    // every row of the tile is a distinct table row: its whole gradient is here -- l2 once per occurrence
-                    // (model/transfer.py:486-488 sums over the gathered rows) -- and the lazy-Adam step runs in place
-                    const bool okd = r < live;
-                    const float nocc = (float)rlen[r];
-                    if constexpr (!PRELOAD) dense_prefetch<D>(a, sidx, row, w, okd, fpre);
-                    if (okd) {
-                        float pnew = x1, mm = fpre.m, vv = fpre.v;
-                        adam_apply(pnew, mm, vv, dxh + nocc * a.l2 * x1, a.fu.sched[a.fu.cur_step]);
-                        const int64_t o = fpre.trow * D + w;
-                        a.fu.w[sidx][o] = pnew; a.fu.m[sidx][o] = mm; a.fu.v[sidx][o] = vv;
-                        if (w == 0) a.fu.last[sidx][fpre.trow] = a.fu.cur_step;
-                        lsum += nocc * 0.5f * a.l2 * x1 * x1;
-                    }
-                    continue;
+        if constexpr (DENSEOK) {
+            if (dense) {
+                // every row of the tile is a distinct table row: its whole gradient is here -- l2 once per occurrence
+                // (model/transfer.py:486-488 sums over the gathered rows) -- and the lazy-Adam step runs in place
+                const bool okd = r < live;
+                const float nocc = (float)rlen[r];
+                if constexpr (!PRELOAD) dense_prefetch<D>(a, sidx, row, w, okd, fpre);
+                if (okd) {
+                    float pnew = x1, mm = fpre.m, vv = fpre.v;
+                    adam_apply(pnew, mm, vv, dxh + nocc * a.l2 * x1, a.fu.sched[a.fu.cur_step]);
+                    const int64_t o = fpre.trow * D + w;
+                    a.fu.w[sidx][o] = pnew; a.fu.m[sidx][o] = mm; a.fu.v[sidx][o] = vv;
+                    if (w == 0) a.fu.last[sidx][fpre.trow] = a.fu.cur_step;
+                    lsum += nocc * 0.5f * a.l2 * x1 * x1;
                 }
-            }
-            if constexpr (D <= 64) {
-                if (fused) {
-                    if constexpr (!PRELOAD) { fused_prefetch<D>(a, sidx, row, w, ok, fpre); fused_prefetch_record(a, sidx, ok, fpre); }
-                    fused_row_update<D>(a, sidx, row, w, ok, x1, dxh + a.l2 * x1, fpre);
-                } else st_out<SML_WT_MFB>(&sg.dx[(int64_t)row * D + w], dxh + a.l2 * x1);
-            } else {
-                st_out<SML_WT_MFB>(&sg.dx[(int64_t)row * D + w], dxh + a.l2 * x1);
-            }
-            if (p_world > 0 && sidx && ok) {                    // several GPUs: the row also goes into every rank's inbox
-                for (int q = 0; q < p_world; ++q) peer_store(a.push.dst[q] + (int64_t)row * D + w, dxh + a.l2 * x1);
-            }
-            if (ok) lsum += 0.5f * a.l2 * x1 * x1;      // + l2 * 0.5 * sum(x_hat^2), model/transfer.py:486-488
-        }
-        if constexpr (TR) {
-            // A[e] = (dh1p[0..9], dh2p[0..4], 0), B[e] = (x0, x1, x2, 1, h1[0..9], 0, 0); 256 elements per round
-            float* cgA = cgst;
-            float* cgB = cgst + 256 * CGS;
-#pragma unroll 1
-            for (int half = 0; half < 2; ++half) {
-                __syncthreads();               // the previous round's MFMA operands have been read
-                if ((tid >> 8) == half) {
-                    const int t8 = tid & 255;
-                    float cga[16], cgb[16];
-#pragma unroll
-                    for (int c = 0; c < SML_C1; ++c) { cga[c] = ok ? dh1p[c] : 0.0f; cgb[4 + c] = p.h1[c]; }
-#pragma unroll
-                    for (int o = 0; o < SML_C2; ++o) cga[10 + o] = ok ? dh2p[o] : 0.0f;
-                    cga[15] = 0.0f;
-                    cgb[0] = x0; cgb[1] = x1; cgb[2] = x2; cgb[3] = 1.0f; cgb[14] = 0.0f; cgb[15] = 0.0f;
-#pragma unroll
-                    for (int i4 = 0; i4 < 4; ++i4) {
-                        f32x4 va, vb;
-#pragma unroll
-                        for (int e4 = 0; e4 < 4; ++e4) { va[e4] = cga[i4 * 4 + e4]; vb[e4] = cgb[i4 * 4 + e4]; }
-                        *reinterpret_cast<f32x4*>(cgA + t8 * CGS + i4 * 4) = va;
-                        *reinterpret_cast<f32x4*>(cgB + t8 * CGS + i4 * 4) = vb;
-                    }
-                }
-                __syncthreads();
-                // wave wv: elements 64*(wv&3) + 32*(wv>>2) .. +31, 4 elements per MFMA
-                const int e0 = 64 * (wv & 3) + 32 * (wv >> 2);
-                float av8[8], bv8[8];
-#pragma unroll
-                for (int s8 = 0; s8 < 8; ++s8) {
-                    av8[s8] = cgA[(e0 + 4 * s8 + g4) * CGS + l15];
-                    bv8[s8] = cgB[(e0 + 4 * s8 + g4) * CGS + l15];
-                }
-#pragma unroll
-                for (int s8 = 0; s8 < 8; ++s8) cgacc = mfma16(av8[s8], bv8[s8], cgacc);
+                continue;
             }
         }
+        if constexpr (D <= 64) {
+            if (fused) {
+                if constexpr (!PRELOAD) { fused_prefetch<D>(a, sidx, row, w, ok, fpre); fused_prefetch_record(a, sidx, ok, fpre); }
+                fused_row_update<D>(a, sidx, row, w, ok, x1, dxh + a.l2 * x1, fpre);
+            } else st_out<SML_WT_MFB>(&sg.dx[(int64_t)row * D + w], dxh + a.l2 * x1);
+        } else {
+            st_out<SML_WT_MFB>(&sg.dx[(int64_t)row * D + w], dxh + a.l2 * x1);
+        }
+        if (p_world > 0 && sidx && ok) {                    // several GPUs: the row also goes into every rank's inbox
+            for (int q = 0; q < p_world; ++q) peer_store(a.push.dst[q] + (int64_t)row * D + w, dxh + a.l2 * x1);
+        }
+        if (ok) lsum += 0.5f * a.l2 * x1 * x1;      // + l2 * 0.5 * sum(x_hat^2), model/transfer.py:486-488
     }
     {   // this workgroup's share of the batch loss: lanes, then waves in index order (deterministic)
         float v = lsum;
@@ -1281,25 +1229,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
         if (lane == 0) lred[wv] = v;
     }
-    if constexpr (TR) {
-        // G[c][0..2] = dW_conv1[c], G[c][3] = db_conv1[c], G[10+o][4+c] = dW_conv2[o][c], G[10+o][3] = db_conv2[o]
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) red[wv][(4 * g4 + q4) * 16 + l15] = cgacc[q4];
-        __syncthreads();
-        if (tid < 95) {
-            int i, j;
-            if (tid < 30) { i = tid / 3; j = tid % 3; }
-            else if (tid < 40) { i = tid - 30; j = 3; }
-            else if (tid < 90) { i = 10 + (tid - 40) / 10; j = 4 + (tid - 40) % 10; }
-            else { i = 10 + (tid - 90); j = 3; }
-            float sacc = 0.0f;
-#pragma unroll
-            for (int w8 = 0; w8 < 8; ++w8) sacc += red[w8][i * 16 + j];
-            a.convg_part[(int64_t)blockIdx.x * SML_CG + tid] = sacc;
-        }
-    } else {
-        __syncthreads();
-    }
+    __syncthreads();
     if (tid == 0) {
         float s = 0.0f;
 #pragma unroll
@@ -1307,21 +1237,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         a.loss_part[blockIdx.x] = s;
         TL(7);
     }
-    if constexpr (!TR) { if (p_world > 0) peer_signal(a.push); }       // this workgroup's rows are acknowledged: +1 on every rank's counter
+    if (p_world > 0) peer_signal(a.push);       // this workgroup's rows are acknowledged: +1 on every rank's counter
     TL_DONE();
 }
 
 // ------------------------------------------------------------------------------------
-// backward: dOut -> (MF stage) dx_hat + l2*x_hat, or (TR stage) dZ1 rows + conv-grad partials.
-// dx / dz1 scratch is padded to whole tiles (unconditional stores).
+// MF-stage backward: dOut -> dx_hat + l2*x_hat.  dx scratch is padded to whole tiles (unconditional stores).
 //
 // CS = D/16 workgroups share a 16-row tile: workgroup (tile, cs) owns the 16 coordinates
 // w in [16cs, 16cs+16) of every conv channel.  The flatten is channel-major (column c*D + w), so
 // those are the five dA1 column tiles {c*D/16 + cs}: the big GEMM dA1 = dZ1 * W1 splits over the
 // CS workgroups by OUTPUT columns -- no cross-workgroup sum -- while the small one (dA2 = dOut * W2,
-// K = D) and the pair loss are simply repeated.  A 768-row TR batch is 96 workgroups at d = 32.
+// K = D) and the pair loss are simply repeated.
 // ------------------------------------------------------------------------------------
-template <int D, bool TR, bool PRE>
+template <int D, bool PRE>
 __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
     constexpr int R = SML_TM;
     constexpr int CS = D / 16;
@@ -1330,11 +1259,9 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
     constexpr int KSD = D / 16;
     constexpr int EPT = R * D / 512;
     constexpr int PSTR = SML_C2 * 16 + 1;
-    constexpr int CGS = 20;                                        // conv-grad operand row stride (16-byte aligned)
-    constexpr int SZ = cmax(cmax(R * S2 + R * SD, 8 * R * PSTR), 2 * 256 * CGS);
+    constexpr int SZ = cmax(R * S2 + R * SD, 8 * R * PSTR);
     static_assert(3 * R * (D + 1) <= SZ, "pair-loss staging fits");
     __shared__ __attribute__((aligned(16))) float smem[SZ + 104];
-    __shared__ float red[TR ? 8 : 1][256];
     __shared__ float cf[4][SML_TM];
     __shared__ float lred[8];
     float* dZs = smem;                    // [R][516]
@@ -1462,7 +1389,6 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
             }
             if (row >= sg.n_rows) g = 0.0f;
             dOs[r * SD + w] = g;
-            if (TR && cs == 0) st_out<SML_WT_BWD>(&sg.dout[(int64_t)row * D + w], g);
         }
     } else {
         __syncthreads();
@@ -1506,7 +1432,6 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
             }
             if (row >= sg.n_rows) g = 0.0f;
             dOs[r * SD + w] = g;
-            if (TR && cs == 0) st_out<SML_WT_BWD>(&sg.dout[(int64_t)row * D + w], g);
         }
     }
     __syncthreads();
@@ -1529,7 +1454,6 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
         zero_acc(acc);
         if constexpr (PRE) mma16_ring<1, 4, KSD, KSD, false>(acc, ring2, dOs + l15 * SD + 4 * g4, 0, p2b, KSD, 0, lane, tile2, nokofs);
         else mma16_rows<1, 4, KSD, KSD>(acc, dOs + l15 * SD + 4 * g4, 0, p2b, KSD, 0, lane, tile2);
-        float* dz1 = sg.dz1;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int n = (wv * 4 + t) * 16 + l15;
@@ -1538,7 +1462,6 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
                 const int r = 4 * g4 + q;
                 const float dz = acc[0][t][q] * sml_gelu_grad(z[t][q]);
                 dZs[r * S2 + n] = dz;
-                if (TR && (t % CS) == cs) st_out<SML_WT_BWD>(&dz1[(int64_t)(row0 + r) * SML_HID + n], dz);   // the CS workgroups share the save
             }
         }
     }
@@ -1559,11 +1482,9 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
     __syncthreads();
     TL(4);
     // ---- per-coordinate tail (threads 0..255, one element each): Gelu'(h2) -> conv2^T -> Gelu'(h1) -> conv1^T (row 1 = x_hat)
-    float cga[16], cgb[16];
     if (tid < 256) {
         const int row = row0 + tr_;
         const bool ok = row < sg.n_rows;
-        const Pro& p = pt;
         float dh2p[SML_C2];
 #pragma unroll
         for (int c = 0; c < SML_C2; ++c) {
@@ -1582,21 +1503,8 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
             dh1p[c] = s * gg1[c];
             dxh += dh1p[c] * cws[SML_OFF_C1W + c * 3 + 1];
         }
-        if (!TR) {
-            sg.dx[(int64_t)row * D + tw] = dxh + a.l2 * x1;
-            if (ok) lsum += 0.5f * a.l2 * x1 * x1;      // + l2 * 0.5 * sum(x_hat^2), model/transfer.py:486-488
-        }
-        if constexpr (TR) {
-            // conv1/conv2 parameter gradients are one small matrix product over the tile's elements e:
-            //   G[i][j] = sum_e A[e][i] * B[e][j],  A[e] = (dh1p[0..9], dh2p[0..4], 0),  B[e] = (x0, x1, x2, 1, h1[0..9], 0, 0)
-            // G[c][0..2] = dW_conv1[c], G[c][3] = db_conv1[c], G[10+o][4+c] = dW_conv2[o][c], G[10+o][3] = db_conv2[o]
-#pragma unroll
-            for (int c = 0; c < SML_C1; ++c) { cga[c] = ok ? dh1p[c] : 0.0f; cgb[4 + c] = p.h1[c]; }
-#pragma unroll
-            for (int o = 0; o < SML_C2; ++o) cga[10 + o] = ok ? dh2p[o] : 0.0f;
-            cga[15] = 0.0f;
-            cgb[0] = x0; cgb[1] = x1; cgb[2] = x2; cgb[3] = 1.0f; cgb[14] = 0.0f; cgb[15] = 0.0f;
-        }
+        sg.dx[(int64_t)row * D + tw] = dxh + a.l2 * x1;
+        if (ok) lsum += 0.5f * a.l2 * x1 * x1;      // + l2 * 0.5 * sum(x_hat^2), model/transfer.py:486-488
     }
     {   // this workgroup's share of the batch loss: lanes, then waves in index order (deterministic)
         float v = lsum;
@@ -1604,50 +1512,7 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
         for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
         if (lane == 0) lred[wv] = v;
     }
-    if constexpr (TR) {
-        float* cgA = smem;                 // [256][CGS]  (the dA1 partials are in registers by now)
-        float* cgB = smem + 256 * CGS;
-        __syncthreads();
-        if (tid < 256) {
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4) {
-                f32x4 va, vb;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { va[e] = cga[i4 * 4 + e]; vb[e] = cgb[i4 * 4 + e]; }
-                *reinterpret_cast<f32x4*>(cgA + tid * CGS + i4 * 4) = va;
-                *reinterpret_cast<f32x4*>(cgB + tid * CGS + i4 * 4) = vb;
-            }
-        }
-        __syncthreads();
-        {   // wave wv: elements 64*(wv&3) .. +63, k-steps 8*(wv>>2) .. +7 (4 elements per MFMA)
-            const int e0 = 64 * (wv & 3) + 32 * (wv >> 2);
-            float av[8], bv[8];
-#pragma unroll
-            for (int s8 = 0; s8 < 8; ++s8) {
-                av[s8] = cgA[(e0 + 4 * s8 + g4) * CGS + l15];
-                bv[s8] = cgB[(e0 + 4 * s8 + g4) * CGS + l15];
-            }
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s8 = 0; s8 < 8; ++s8) acc = mfma16(av[s8], bv[s8], acc);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) red[wv][(4 * g4 + q) * 16 + l15] = acc[q];
-        }
-        __syncthreads();
-        if (tid < 95) {
-            int i, j;
-            if (tid < 30) { i = tid / 3; j = tid % 3; }
-            else if (tid < 40) { i = tid - 30; j = 3; }
-            else if (tid < 90) { i = 10 + (tid - 40) / 10; j = 4 + (tid - 40) % 10; }
-            else { i = 10 + (tid - 90); j = 3; }
-            float sacc = 0.0f;
-#pragma unroll
-            for (int w8 = 0; w8 < 8; ++w8) sacc += red[w8][i * 16 + j];
-            a.convg_part[(int64_t)blockIdx.x * SML_CG + tid] = sacc;
-        }
-    } else {
-        __syncthreads();
-    }
+    __syncthreads();
     if (tid == 0) {
         float sacc = 0.0f;
 #pragma unroll
@@ -1659,7 +1524,7 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
-// TR stage, restructured step (v2): the backward is cut where the weight gradients become computable.
+// TR stage: the backward is cut where the weight gradients become computable.
 //   k_tr_bwd_head   pair loss -> dOut -> dA2 = dOut * W2 -> dZ1 = dA2 * Gelu'(z1): everything the weight-gradient
 //                   tiles need (dOut, dZ1), and nothing else.  HS = 4 workgroups per 16-row tile, one 128-column slice
 //                   of the hidden layer each (pair loss repeated, 16 KB of W2 per workgroup instead of 64 KB + 160 KB
@@ -1866,7 +1731,7 @@ __device__ __forceinline__ void pack_store(float* __restrict__ pk, int off, floa
 // registers by the time the gradient is complete.
 // ------------------------------------------------------------------------------------
 #define SML_WG_TILE_SMEM (8 * 32 * 33 + 8 * 32 + 32 * 33)     // floats of LDS one weight-gradient tile workgroup uses
-// one 32x32 weight-gradient tile (+ fused Adam + operand-image refresh): shared by k_transfer_wgrad and k_tr_wgrad2.
+// one 32x32 weight-gradient tile (+ fused Adam + operand-image refresh): the tile workgroups of k_tr_wgrad2.
 // (xcd, kk): the XCD this workgroup runs on and its index among that XCD's tiles.
 template <int D>
 __device__ __forceinline__ void wgrad_tile(const SmlWgArgs& a, const SmlWgSeg& sg, int xcd, int kk, float* smem_wg, long long* tl_rec) {
@@ -2032,57 +1897,6 @@ __device__ __forceinline__ void wgrad_tile(const SmlWgArgs& a, const SmlWgSeg& s
     TL(7);
 }
 
-template <int D>
-__global__ __launch_bounds__(512) void k_transfer_wgrad(SmlWgArgs a) {
-    __shared__ __attribute__((aligned(16))) float smem_wg[SML_WG_TILE_SMEM];
-    TL_BEGIN(3); TL_PREV();
-    constexpr int NS = sml_net_size(D);
-    const int tid = threadIdx.x;
-    const bool fuse = a.theta != nullptr;
-    SmlSched sc; sc.step_size = a.step_size; sc.bc2_sqrt = a.bc2_sqrt;
-    // Dispatch order = start order (the 194 workgroups start over ~1.3 us) and the work is uneven: the item net has
-    // twice the user net's rows, so its tiles run ~2 us longer, and the two conv-parameter workgroups are a serial
-    // chain of partial sums.  The long ones take the LOW block indices: conv workgroups first, then the item net's
-    // tiles, the user net's last (per-workgroup end times from the in-kernel timeline: median 6.4, max 8.7 us before).
-    if ((int)blockIdx.x < 2) {
-        // conv1/conv2 parameters of one net: sum the backward workgroups' partials in order, then Adam
-        const int net = (int)blockIdx.x;
-        if (tid < 95) {
-            const int off = tid < 30 ? tid : tid < 40 ? tid + 2 : tid < 90 ? tid + 4 : tid + 6;
-            const int t0 = net ? a.tiles0 : 0, t1 = net ? a.tiles_total : a.tiles0;
-            const int64_t i = (int64_t)net * NS + off;
-            float p = 0.f, m = 0.f, v = 0.f;
-            if (fuse) { p = a.theta[i]; m = a.m[i]; v = a.v[i]; }
-            float g = 0.0f;
-            int t = t0;
-            for (; t + 8 <= t1; t += 8) {
-                float x[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) x[u] = a.convg_part[(int64_t)(t + u) * SML_CG + tid];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) g += x[u];
-            }
-            for (; t < t1; ++t) g += a.convg_part[(int64_t)t * SML_CG + tid];
-            if (a.seg[net].grad) a.seg[net].grad[off] = g;    // the flat gradient is complete after this launch (null: nobody reads it)
-            for (int q = 0; q < a.peer.world; ++q) peer_store(a.peer.dst[q] + i, g);
-            if (fuse) {
-                adam_apply(p, m, v, adam_wd(g, a.weight_decay, p), sc);
-                a.theta[i] = p; a.m[i] = m; a.v[i] = v;
-            }
-        }
-        if (a.peer.world > 0) peer_signal(a.peer);
-        TL(7);
-        TL_DONE();
-        return;
-    }
-    {
-        const int kk = ((int)blockIdx.x - 2) / 8;
-        const SmlWgSeg sg = (kk / (2 * (SML_C2 * D / 32 + D / 32))) ? a.seg[0] : a.seg[1];      // net = 1 - kk / PER (wgrad_tile's map)
-        wgrad_tile<D>(a, sg, (int)blockIdx.x % 8, kk, smem_wg, tl_rec);    // (8 consecutive blocks: one per XCD)
-    }
-    TL_DONE();
-}
-
 // The merged launch of the restructured TR step (see k_tr_bwd_head).  Workgroups [0, n_tail) are the backward's
 // tail -- they have the longest chain and are dispatched first --, the rest are the weight-gradient tiles.
 // (round 6: the first round of loads' operands as 14 preloaded dwords, as k_transfer_fwd -- both segments' operand arrays are one
@@ -2120,7 +1934,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     if ((int)blockIdx.x >= h_n_tail) {
         const int vb = (int)blockIdx.x - h_n_tail;
         const SmlWgSeg sgt = ((vb / 8) / (2 * (SML_C2 * D / 32 + D / 32))) ? SmlWgSeg(seg0) : SmlWgSeg(seg1);      // (by value: net = 1 - kk / PER, wgrad_tile's map)
-        wgrad_tile<D>(a, sgt, (int)blockIdx.x % 8, vb / 8, smem, tl_rec);
+        // wgrad_tile has this one caller, so the compiler's interprocedural constant propagation, which runs BEFORE inlining, would
+        // put the address of `smem` into the not yet inlined function and shape the tile's LDS addressing around a constant base:
+        // +2 VALU per tile workgroup, and the TR step measured 0.3-0.7 % slower with it.  The offset below is zero, but only the
+        // instruction combiner sees that, after the inlining -- the tile's code is then what a pointer parameter gives.
+        float* const smem_tile = smem + (vb * 3 - vb - vb - vb);
+        wgrad_tile<D>(a, sgt, (int)blockIdx.x % 8, vb / 8, smem_tile, tl_rec);
         TL_DONE();
         return;
     }
@@ -2470,14 +2289,13 @@ hipError_t sml_launch_fwd(int d, int mt, int ns, const SmlFwdArgs& a, int tiles_
     else if (mt == 1 && ns == 4) { SML_DISPATCH_D(d, k_transfer_fwd<DD, 1, 4><<<dim3(((tiles_total + 1) / 2) * 8), dim3(512), 0, st>>>(SML_FWD_HOT_ARGS)); }
     else if (mt == 1 && ns == 2) { SML_DISPATCH_D(d, k_transfer_fwd<DD, 1, 2><<<dim3(tiles_total * 2), dim3(512), 0, st>>>(SML_FWD_HOT_ARGS)); }
     else if (mt == 2 && ns == 1) {
-        // table-sized calls: two hidden passes, two workgroups per CU (SML_FWD_HSEQ=1: the one-pass form)
-        static const bool hseq = !(getenv("SML_FWD_HSEQ") && atoi(getenv("SML_FWD_HSEQ")) == 1);
+        // table-sized calls: two hidden passes, two workgroups per CU
         // (d = 128: the two-pass form still needs 118 KB of LDS -- one workgroup per CU either way -- so it keeps one pass)
-        if (hseq && d == 32) k_transfer_fwd<32, 2, 1, 2><<<dim3(tiles_total), dim3(512), 0, st>>>(SML_FWD_HOT_ARGS);
-        else if (hseq && d == 64) k_transfer_fwd<64, 2, 1, 2><<<dim3(tiles_total), dim3(512), 0, st>>>(SML_FWD_HOT_ARGS);
-        else { SML_DISPATCH_D(d, k_transfer_fwd<DD, 2, 1><<<dim3(tiles_total), dim3(512), 0, st>>>(SML_FWD_HOT_ARGS)); }
+        if (d == 32) k_transfer_fwd<32, 2, 1, 2><<<dim3(tiles_total), dim3(512), 0, st>>>(SML_FWD_HOT_ARGS);
+        else if (d == 64) k_transfer_fwd<64, 2, 1, 2><<<dim3(tiles_total), dim3(512), 0, st>>>(SML_FWD_HOT_ARGS);
+        else if (d == 128) k_transfer_fwd<128, 2, 1><<<dim3(tiles_total), dim3(512), 0, st>>>(SML_FWD_HOT_ARGS);
+        else return hipErrorInvalidValue;
     }
-    else if (mt == 3 && ns == 1 && d == 32) { k_transfer_fwd<32, 3, 1><<<dim3(tiles_total), dim3(512), 0, st>>>(SML_FWD_HOT_ARGS); }
     else return hipErrorInvalidValue;
 #undef SML_FWD_HOT_ARGS
     return hipGetLastError();
@@ -2492,24 +2310,18 @@ hipError_t sml_launch_bwd(int d, int split, const SmlBwdArgs& a, int tiles_total
         // (d = 64 measured both ways on MI355X, TR batch 256: 39.09 us/batch preloaded vs 39.12 on demand -- no
         // difference, so the form with 124 registers instead of 224 is the default)
         const bool pre = d == 32 || (d == 64 && force_pre > 0);
-        const bool tr = a.convg_part != nullptr;
-#define SML_BWD_LAUNCH(DD, TRV, PREV) k_transfer_bwd<DD, TRV, PREV><<<dim3(grid), dim3(512), 0, st>>>(a)
-        if (d == 32) { if (tr) SML_BWD_LAUNCH(32, true, true); else SML_BWD_LAUNCH(32, false, true); }
-        else if (d == 64 && pre) { if (tr) SML_BWD_LAUNCH(64, true, true); else SML_BWD_LAUNCH(64, false, true); }
-        else if (d == 64) { if (tr) SML_BWD_LAUNCH(64, true, false); else SML_BWD_LAUNCH(64, false, false); }
-        else if (d == 128) { if (tr) SML_BWD_LAUNCH(128, true, false); else SML_BWD_LAUNCH(128, false, false); }
+        if (d == 32) k_transfer_bwd<32, true><<<dim3(grid), dim3(512), 0, st>>>(a);
+        else if (d == 64 && pre) k_transfer_bwd<64, true><<<dim3(grid), dim3(512), 0, st>>>(a);
+        else if (d == 64) k_transfer_bwd<64, false><<<dim3(grid), dim3(512), 0, st>>>(a);
+        else if (d == 128) k_transfer_bwd<128, false><<<dim3(grid), dim3(512), 0, st>>>(a);
         else return hipErrorInvalidValue;
-#undef SML_BWD_LAUNCH
     } else {
         if (a.seg[1].theta != a.seg[0].theta + sml_net_size(d)) return hipErrorInvalidValue;      // (what the kernel's preloaded parameters assume)
-#define SML_BWDF_HOT a.dn.hdr, a.dn.ent, a.seg[0].theta, a.out_all, a.tiles0, a.push.world, a.tiles_live, a.B, a
-        if (a.convg_part != nullptr) { SML_DISPATCH_D(d, k_transfer_bwd_full<DD, 1, true><<<dim3(tiles_total), dim3(512), 0, st>>>(SML_BWDF_HOT)); }
-        else { SML_DISPATCH_D(d, k_transfer_bwd_full<DD, 1, false><<<dim3(tiles_total), dim3(512), 0, st>>>(SML_BWDF_HOT)); }
-#undef SML_BWDF_HOT
+        SML_DISPATCH_D(d, k_transfer_bwd_full<DD, 1><<<dim3(tiles_total), dim3(512), 0, st>>>(a.dn.hdr, a.dn.ent, a.seg[0].theta, a.out_all, a.tiles0, a.push.world,
+                                                                                                a.tiles_live, a.B, a));
     }
     return hipGetLastError();
 }
-int sml_wgrad_grid(int d);
 hipError_t sml_launch_tr_bwd_head(int d, const SmlBwdArgs& a, int tiles_total, hipStream_t st) {
     if (tiles_total <= 0) return hipSuccess;
     // (leading scalars = the struct's own fields; the kernel derives each segment's z1 / pk / n_rows from them: slot0 = ioff, pk + net * size)
@@ -2522,9 +2334,11 @@ hipError_t sml_launch_tr_bwd_head(int d, const SmlBwdArgs& a, int tiles_total, h
                                                                                                    a.B, a.ioff, a.tiles0, a.tiles_total, a.out_np, a));
     return hipGetLastError();
 }
-int sml_wgrad2_pushers(int d) { return sml_wgrad_grid(d) - 2 + 1; }      // every tile workgroup + the last tail workgroup
+// 32x32 tiles of dW1 [512 x 5d] and dW2 [d x 512], both nets (wgrad_tile's map): the tile workgroups of one merged launch.
+// Each of them pushes its finished tile to the peers, and the last tail workgroup the conv gradients: tiles + 1 pushers.
+int sml_wgrad_tiles(int d) { return 2 * (16 * (SML_C2 * d / 32) + (d / 32) * 16); }
 hipError_t sml_launch_tr_wgrad2(int d, const SmlWgArgs& a, hipStream_t st) {
-    const int tiles = sml_wgrad_grid(d) - 2;
+    const int tiles = sml_wgrad_tiles(d);
     // the layout the kernel's preloaded leading parameters stand for: refuse anything else loudly
     const SmlWgSeg& s0 = a.seg[0]; const SmlWgSeg& s1 = a.seg[1];
     const int B = s0.n_rows;
@@ -2534,15 +2348,6 @@ hipError_t sml_launch_tr_wgrad2(int d, const SmlWgArgs& a, hipStream_t st) {
         a.tiles0 != (B + SML_TM - 1) / SML_TM || a.tiles_total != a.tiles0 + (2 * B + SML_TM - 1) / SML_TM)
         return hipErrorInvalidValue;
     SML_DISPATCH_D(d, k_tr_wgrad2<DD><<<dim3(a.n_tail + tiles), dim3(512), 0, st>>>(s0.dz1, s0.a1, s0.dout, s0.a2, s0.pk_net, s0.xin, B, a.n_tail, a));
-    return hipGetLastError();
-}
-int sml_wgrad_grid(int d) {
-    const int tn = 16 * (SML_C2 * d / 32) + (d / 32) * 16;
-    const int extra = 2;        // + one conv-parameter workgroup per net (sums the backward's partials; Adam when fused)
-    return 2 * tn + extra;
-}
-hipError_t sml_launch_wgrad(int d, const SmlWgArgs& a, hipStream_t st) {
-    SML_DISPATCH_D(d, k_transfer_wgrad<DD><<<dim3(sml_wgrad_grid(d)), dim3(512), 0, st>>>(a));
     return hipGetLastError();
 }
 hipError_t sml_launch_theta_adam(int d, const SmlThetaAdamArgs& a, hipStream_t st) {

@@ -24,12 +24,6 @@ TR_SHAPES = [(32, 17), (32, 336), (32, 337), (32, 400), (32, 680), (32, 681), (3
 TR_BPR_SHAPES = [(32, 17), (32, 400), (32, 768), (64, 100), (64, 400), (64, 681), (128, 17), (128, 400), (128, 699)]
 # (d, B, loss, special, env): special is None, "conv" (the ConvTransfer nets), "plan" or "clip"
 TR_CASES = [(d, B, "bce", None, {}) for d, B in TR_SHAPES] + [(d, B, "bpr", None, {}) for d, B in TR_BPR_SHAPES] + [
-    (32, 768, "bce", None, {"SML_TR_V2": "0"}),
-    (64, 400, "bce", None, {"SML_TR_V2": "0", "SML_BWD_PRE": "0"}),
-    (64, 400, "bce", None, {"SML_TR_V2": "0", "SML_BWD_PRE": "1"}),
-    (128, 699, "bce", None, {"SML_TR_V2": "0"}),
-    (32, 400, "bce", None, {"SML_TR_V2": "0", "SML_BWD_SPLIT": "0"}),
-    (64, 681, "bce", None, {"SML_TR_V2": "0", "SML_BWD_SPLIT": "1"}),
     (32, 336, "bce", None, {"SML_TR_DEFER": "0"}),
     (32, 768, "bce", None, {"SML_TR_A2_RECOMPUTE": "0"}),
     (32, 256, "bpr", "conv", {}),

@@ -867,13 +867,29 @@ def test_no_kernel_spills_or_uses_scratch_memory():
     """Round 6: several kernels patch a local copy of (part of) their by-value argument struct with preloaded parameters; a copy
     that is indexed dynamically anywhere cannot live in registers and lands in scratch memory (560 bytes per lane in the first attempt
     at k_transfer_bwd_full) -- slow, and silent.  The compiler's resource remarks for every kernel of transfer_net.hip / mf_kernels.hip
-    with the product's flags: no spilled VGPR, no scratch (tools/kernel_resources.py; hipcc cross-compiles without a GPU)."""
+    with the product's flags: no spilled VGPR, no scratch (tools/kernel_resources.py; hipcc cross-compiles without a GPU).
+
+    The same report pins the instantiation sets of the transfer net's forward and MF backward: every form has a launch site that some
+    input reaches by default, the TR stage's backward is k_tr_bwd_head + k_tr_wgrad2 alone (no TR flag on the MF kernels, no
+    k_transfer_wgrad), and a form that only a switch could select does not come back unnoticed."""
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(repo, "tools", "kernel_resources.py")], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:]
-    assert "k_tr_wgrad2<32>" in p.stdout and "k_transfer_bwd_full<32, 1, false>" in p.stdout       # (the report really covered the kernels)
+    names = {line.split("  ")[0] for line in p.stdout.splitlines()}
+    assert "k_tr_wgrad2<32>" in names and "k_tr_bwd_head<32>" in names                              # (the report really covered the kernels)
+
+    def family(k):
+        return {n for n in names if n.startswith(k + "<")}
+    fwd = {"k_transfer_fwd<%d, 1, %d, 1>" % (d, ns) for d in (32, 64, 128) for ns in (1, 2, 4)}
+    fwd |= {"k_transfer_fwd<32, 2, 1, 2>", "k_transfer_fwd<64, 2, 1, 2>", "k_transfer_fwd<128, 2, 1, 1>"}
+    assert family("k_transfer_fwd") == fwd, sorted(family("k_transfer_fwd") ^ fwd)
+    bwd = {"k_transfer_bwd<32, true>", "k_transfer_bwd<64, false>", "k_transfer_bwd<64, true>", "k_transfer_bwd<128, false>"}     # <D, PRE>
+    assert family("k_transfer_bwd") == bwd, sorted(family("k_transfer_bwd") ^ bwd)
+    full = {"k_transfer_bwd_full<%d, 1>" % d for d in (32, 64, 128)}
+    assert family("k_transfer_bwd_full") == full, sorted(family("k_transfer_bwd_full") ^ full)
+    assert not [n for n in names if "k_transfer_wgrad" in n]
 
 
 def test_tr_with_mf_bias_fails_like_the_reference_does(tmp_path, monkeypatch):

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Time of one `updata` (the transfer net over every user and item row, reference model/transfer.py:884-902) at the
-Yelp shape, on the whole chip and on the training partition (192 CUs).  Geometry overrides for A/B runs:
-SML_FWD_MT=3 (48-row tiles, one workgroup per CU), SML_FWD_HSEQ=1 (32-row tiles, one hidden pass);
-default: 32-row tiles, two hidden passes, two workgroups per CU."""
+Yelp shape, on the whole chip and on the training partition (192 CUs).  SML_FWD_BX3=0 gives the fp32-product kernel
+(32-row tiles, two hidden passes, two workgroups per CU) for A/B runs."""
 import contextlib, io, json, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
