@@ -1,2 +1,2 @@
 """reference data/dataset2.py surface -> sml_amd.datasets."""
-from sml_amd.datasets import transfer_data, testDataset, trainDataset_withPreSample  # noqa: F401
+from sml_amd.datasets import transfer_data, testDataset, trainDataset_withPreSample, select_neg_forinteraction  # noqa: F401

@@ -707,6 +707,34 @@ int sml_iset_union(sml_ctx* ctx, int64_t n_user, const int64_t* a_off, const int
 int sml_iset_contains(sml_ctx* ctx, const int64_t* rows, int64_t m, int n_cols, const int64_t* off, const int32_t* items,
                       uint8_t* out, void* stream);
 
+/* ---- test-set negatives ---------------------------------------------------------------- */
+/* The negatives of a test period's rows -- the device form of the reference's data/dataset2.py select_neg_forinteraction:
+ * the same distribution, NOT numpy's random stream (the contract of sml_sample_negatives and sml_weighted_epoch).
+ *
+ * The stream is every period's rows one after the other; row g (a global position, < 2^31) is (u, i).  C(g) is the set of
+ * items of rows 0..g and H(g) the set of items of user u in rows 0..g, row g included in both.  A row's negatives are a
+ * uniformly random neg_num-subset of C(g) \ H(g) in uniformly random order, fixed to the byte as follows.
+ *   order   int32: the items by first appearance; C(g) = order[0 .. n_cat(g)), n_cat(g) = |C(g)|
+ *   H       a CSR over the users: h_off int64 [n_user + 1], h_items int32 ascending and unique per user, h_since int32 the
+ *           global position of the pair's first row; H(g) = the entries of u's range with h_since <= g
+ *   draws   row g owns the stream s0 = neg_stream(seed, g); candidate number c = 0, 1, 2, ... is
+ *             order[umul64hi(mix(s0 + (c + 1) * 0x9e3779b97f4a7c15), n_cat(g))]
+ *           -- the c-th output of splitmix64 from state s0, addressed by c.  Walking c upwards, a candidate in H(g) or equal
+ *           to an earlier accepted candidate of the row is rejected, anything else accepted; the negatives are the first
+ *           neg_num accepted candidates in acceptance order.
+ *   fails   a row with n_cat(g) - |H(g)| < neg_num (decided before any draw), or with fewer than neg_num accepted among
+ *           262,144 candidates, keeps -1 in every slot it did not fill and adds 1 to *failed.
+ * sml_neg_sets: rows int64 [n, n_cols >= 2] are the rows g0 .. g0 + n - 1 of the stream (column 0 the user, column 1 the item),
+ *   n_cat int32 [n] their catalogue sizes.  out int64 [n, 2 + neg_num]: out[r] = (rows[r][0], rows[r][1], negatives...), the
+ *   format of a test/<p>.npy file and of the evaluation calls.  1 <= neg_num <= 4096; anything else is refused, and so is an
+ *   out that overlaps an input where the pointers show it.  One wavefront per row takes 64 candidates per round; rows are
+ *   walked grid-stride, max_workgroups = 0 leaves the grid to the call, and any grid gives the same bytes whatever the
+ *   schedule.  *failed (device int32) is zeroed by the call.  No allocation, no copy to the host, no synchronise.  Indices
+ *   are trusted on the device (sml_amd.prepare.Timeline range-checks them).  All pointers are device memory.  Asynchronous. */
+int sml_neg_sets(sml_ctx* ctx, const int64_t* rows, int64_t n, int n_cols, int64_t g0, const int32_t* n_cat, const int32_t* order,
+                 const int64_t* h_off, int64_t n_user, const int32_t* h_items, const int32_t* h_since, int neg_num, uint64_t seed,
+                 int max_workgroups, int64_t* out, int32_t* failed, void* stream);
+
 /* ---- host helper: batch supply ------------------------------------------------------- */
 /* Sequential rejection sampling of offlineDataset_withsample.__getitem__ (reference
  * data/dataset.py:63-71) over a pre-drawn candidate stream, on the HOST (no GPU involved):
@@ -731,6 +759,13 @@ int sml_host_gather_column(const void* mat, int64_t n_rows, int64_t row_stride_b
 int sml_host_resolve_negatives_csr(const int64_t* users, int64_t n, const int64_t* cand, int64_t m,
                                    const int64_t* user_ptr, int64_t n_users, const int64_t* user_items,
                                    int64_t* negs, int64_t* consumed, int64_t* resolved);
+
+/* sml_neg_sets (test-set negatives) over HOST memory: a single-threaded walk of the same definition, one candidate at a
+ * time, drawing through the same candidate function as the kernel -- the same bytes in out and the same count in *failed
+ * (host int32).  The route of a machine without a GPU. */
+int sml_host_neg_sets(const int64_t* rows, int64_t n, int n_cols, int64_t g0, const int32_t* n_cat, const int32_t* order,
+                      const int64_t* h_off, int64_t n_user, const int32_t* h_items, const int32_t* h_since, int neg_num, uint64_t seed,
+                      int64_t* out, int32_t* failed);
 
 /* ---- self test ------------------------------------------------------------------ */
 /* Checks the MFMA operand/accumulator lane maps this library assumes against a

@@ -197,6 +197,10 @@ SIGNATURES = {
     "sml_iset_union": (ctypes.c_int, [c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int64, c_void,
                                       c_void, c_void, c_void]),
     "sml_iset_contains": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void, c_void, c_void]),
+    "sml_neg_sets": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void, ctypes.c_int64,
+                                    c_void, c_void, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, c_void, c_void, c_void]),
+    "sml_host_neg_sets": (ctypes.c_int, [c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void, ctypes.c_int64,
+                                         c_void, c_void, ctypes.c_int, ctypes.c_uint64, c_void, c_void]),
     "sml_selftest": (ctypes.c_int, [ctypes.c_int]),
 }
 

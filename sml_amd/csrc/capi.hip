@@ -2364,6 +2364,48 @@ int sml_iset_contains(sml_ctx* ctx, const int64_t* rows, int64_t m, int n_cols, 
     return SML_OK;
 }
 
+// ---- test-set negatives (neg_sets.hip) ----
+static const char* const kNegSetsArgs = "bad argument (n >= 0, n_cols >= 2, g0 >= 0, g0 + n < 2^31, 0 < n_user < 2^31, 1 <= neg_num <= 4096)";
+static bool neg_sets_dims_ok(int64_t n, int n_cols, int64_t g0, int64_t n_user, int neg_num) {
+    return iset_count_ok(n) && n_cols >= 2 && iset_count_ok(g0) && iset_count_ok(g0 + n) && iset_dims_ok(n_user, 1) && neg_num >= 1 &&
+           neg_num <= 4096;
+}
+// out against every input, as far as the pointers show it: the arrays whose length only the device knows count as one entry
+static bool neg_sets_overlap(const int64_t* rows, int64_t n, int n_cols, const int32_t* n_cat, const int32_t* order, const int64_t* h_off,
+                             int64_t n_user, const int32_t* h_items, const int32_t* h_since, int neg_num, const int64_t* out,
+                             const int32_t* failed) {
+    const int64_t out_bytes = 8 * n * (2 + (int64_t)neg_num);
+    return iset_overlap(out, out_bytes, rows, 8 * n * n_cols) || iset_overlap(out, out_bytes, n_cat, 4 * n) ||
+           iset_overlap(out, out_bytes, h_off, 8 * (n_user + 1)) || iset_overlap(out, out_bytes, order, 4) ||
+           iset_overlap(out, out_bytes, h_items, 4) || iset_overlap(out, out_bytes, h_since, 4) || iset_overlap(out, out_bytes, failed, 4);
+}
+
+int sml_neg_sets(sml_ctx* ctx, const int64_t* rows, int64_t n, int n_cols, int64_t g0, const int32_t* n_cat, const int32_t* order,
+                 const int64_t* h_off, int64_t n_user, const int32_t* h_items, const int32_t* h_since, int neg_num, uint64_t seed,
+                 int max_workgroups, int64_t* out, int32_t* failed, void* stream) {
+    if (!ctx || !neg_sets_dims_ok(n, n_cols, g0, n_user, neg_num) || max_workgroups < 0) return fail(SML_EINVAL, "sml_neg_sets", kNegSetsArgs);
+    if (!failed || !h_off || (n && (!rows || !n_cat || !order || !out))) return fail(SML_EINVAL, "sml_neg_sets", "null argument");
+    if (neg_sets_overlap(rows, n, n_cols, n_cat, order, h_off, n_user, h_items, h_since, neg_num, out, failed))
+        return fail(SML_EINVAL, "sml_neg_sets", "out overlaps an input");
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(failed, 0, sizeof(int32_t), st));
+    if (n == 0) return SML_OK;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_neg_sets(rows, n, n_cols, g0, n_cat, order, h_off, h_items, h_since, neg_num, seed, max_workgroups,
+                                                 out, failed, st)));
+    return SML_OK;
+}
+
+int sml_host_neg_sets(const int64_t* rows, int64_t n, int n_cols, int64_t g0, const int32_t* n_cat, const int32_t* order,
+                      const int64_t* h_off, int64_t n_user, const int32_t* h_items, const int32_t* h_since, int neg_num, uint64_t seed,
+                      int64_t* out, int32_t* failed) {
+    if (!neg_sets_dims_ok(n, n_cols, g0, n_user, neg_num)) return fail(SML_EINVAL, "sml_host_neg_sets", kNegSetsArgs);
+    if (!failed || !h_off || (n && (!rows || !n_cat || !order || !out))) return fail(SML_EINVAL, "sml_host_neg_sets", "null argument");
+    if (neg_sets_overlap(rows, n, n_cols, n_cat, order, h_off, n_user, h_items, h_since, neg_num, out, failed))
+        return fail(SML_EINVAL, "sml_host_neg_sets", "out overlaps an input");
+    *failed = (int32_t)sml_neg_sets_host_walk(rows, n, n_cols, g0, n_cat, order, h_off, h_items, h_since, neg_num, seed, out);
+    return SML_OK;
+}
+
 int sml_host_resolve_negatives_csr(const int64_t* users, int64_t n, const int64_t* cand, int64_t m,
                                    const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t* negs,
                                    int64_t* consumed, int64_t* resolved) {

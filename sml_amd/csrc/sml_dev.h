@@ -31,14 +31,28 @@ __device__ __forceinline__ float mf_dot(const float (&u)[4], const float (&it)[4
 
 // Counter-based generator of the device batch supply: element e of a draw keyed by `seed` starts from
 // neg_stream(seed, e) and advances with splitmix64, whatever the launch shape.
-__device__ __forceinline__ uint64_t splitmix64(uint64_t& s) {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+#define SML_SPLITMIX_GAMMA 0x9e3779b97f4a7c15ull
+__host__ __device__ __forceinline__ uint64_t splitmix64_mix(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
     z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
     return z ^ (z >> 31);
 }
-__device__ __forceinline__ uint64_t neg_stream(uint64_t seed, int64_t e) {
+__device__ __forceinline__ uint64_t splitmix64(uint64_t& s) { return splitmix64_mix(s += SML_SPLITMIX_GAMMA); }
+__host__ __device__ __forceinline__ uint64_t neg_stream(uint64_t seed, int64_t e) {
     return seed ^ ((uint64_t)e * 0xd1342543de82ef95ull + 0x632be59bd9b4e019ull);
+}
+// Test-set negatives (neg_sets.hip, include/sml_hip.h "test-set negatives"): candidate number c = 0, 1, 2, ... of the row at
+// global position g is order[neg_set_index(neg_stream(seed, g), c, n_cat)] -- the c-th output of splitmix64 from the row's
+// state, addressed by c without walking the state, scaled to [0, n_cat).  The kernel and sml_host_neg_sets both draw
+// through this one function.
+#define SML_NEG_SET_CAP 262144          // candidates a row may look at before it is counted as failed
+__host__ __device__ __forceinline__ uint32_t neg_set_index(uint64_t s0, uint64_t c, uint32_t n_cat) {
+    const uint64_t z = splitmix64_mix(s0 + (c + 1) * SML_SPLITMIX_GAMMA);
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__umul64hi(z, (uint64_t)n_cat);
+#else
+    return (uint32_t)(((unsigned __int128)z * (uint64_t)n_cat) >> 64);
+#endif
 }
 // One negative for user u: candidates uniform over item_all[0, pop), redrawn while the candidate is one of u's own items
 // (CSR user_ptr [n_users + 1] into ascending user_items), at most 4096 draws (reference data/dataset.py:63-71 and

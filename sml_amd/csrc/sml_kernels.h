@@ -457,3 +457,11 @@ hipError_t sml_launch_iset_union(int64_t n_user, const int64_t* a_off, const int
                                  hipStream_t st);
 hipError_t sml_launch_iset_contains(const int64_t* rows, int64_t m, int n_cols, const int64_t* off, const int32_t* items, uint8_t* out,
                                     hipStream_t st);
+// neg_sets.hip: test-set negatives (1 <= neg_num <= 4096, stream positions < 2^31; no allocation, copy or synchronise) and the
+// same definition as a single-threaded walk over host memory (returns the number of failed rows)
+hipError_t sml_launch_neg_sets(const int64_t* rows, int64_t n, int n_cols, int64_t g0, const int32_t* n_cat, const int32_t* order,
+                               const int64_t* h_off, const int32_t* h_items, const int32_t* h_since, int neg_num, uint64_t seed,
+                               int max_workgroups, int64_t* out, int32_t* failed, hipStream_t st);
+int64_t sml_neg_sets_host_walk(const int64_t* rows, int64_t n, int n_cols, int64_t g0, const int32_t* n_cat, const int32_t* order,
+                               const int64_t* h_off, const int32_t* h_items, const int32_t* h_since, int neg_num, uint64_t seed,
+                               int64_t* out);

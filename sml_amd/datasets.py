@@ -14,6 +14,8 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+from .prepare import select_neg_forinteraction  # noqa: F401  (reference data/dataset2.py:356-414, on the device)
+
 
 _TORCH_DRAWS = [0]          # draws this module made from torch's global generator (EpochSpeculation predicts the next pass's shuffle from it)
 

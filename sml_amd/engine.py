@@ -641,6 +641,27 @@ class HipEngine(object):
                                          self._stream()), "sml_iset_contains")
         return out.bool()
 
+    # ------------------------------------------------------------------ test-set negatives (neg_sets.hip)
+    def neg_sets(self, rows, g0, timeline, neg_num, seed, max_workgroups=0):
+        """The negatives of the stream rows g0 .. g0 + n - 1 (sml_neg_sets): rows int [n, >= 2] (columns 0 and 1; a device
+        tensor or a host array), timeline a sml_amd.prepare.Timeline of this device built from the whole stream.  Returns
+        (out int64 [n, 2 + neg_num] on the device, failed device int32 [1]); a failed row keeps -1 in the slots it did not
+        fill.  The ids are trusted: the Timeline checked their range.  Nothing is read back."""
+        rows = self._iset_rows(rows)
+        n, g0, neg_num = rows.shape[0], int(g0), int(neg_num)
+        if g0 < 0 or g0 + n > timeline.total:
+            raise ValueError("neg_sets: rows %d .. %d are outside the timeline's %d" % (g0, g0 + n, timeline.total))
+        if timeline.order.device != self.device:
+            raise ValueError("neg_sets: the timeline lives on %s, not on %s" % (timeline.order.device, self.device))
+        n_cat = timeline.n_cat_all[g0:g0 + n]
+        out = torch.empty((n, 2 + max(neg_num, 0)), device=self.device, dtype=torch.int64)
+        failed = torch.empty(1, device=self.device, dtype=torch.int32)
+        check(self.lib.sml_neg_sets(self._ctx, _ptr(rows), n, rows.shape[1], g0, _ptr(n_cat), _ptr(timeline.order), _ptr(timeline.h_off),
+                                    timeline.n_user, _ptr(timeline.h_items), _ptr(timeline.h_since), neg_num,
+                                    ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(max_workgroups), _ptr(out), _ptr(failed),
+                                    self._stream()), "sml_neg_sets")
+        return out, failed
+
     # ------------------------------------------------------------------ a2
     def mf_forward(self, w_user, w_item, user, item, norm=False):
         wu, wi = self._table(w_user), self._table(w_item)
