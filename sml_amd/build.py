@@ -3,6 +3,8 @@ import os
 import subprocess
 import sys
 
+from . import switches
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsml_hip.so")
@@ -12,7 +14,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
          # leading scalar / pointer kernel parameters arrive in SGPRs with the wavefront (up to 16 SGPRs) instead of behind a
          # scalar-load round trip of the argument segment: 0.22-0.24 us per dependent kernel (tools/launch_boundary_probe.hip)
          "-mllvm", "-amdgpu-kernarg-preload-count=16"]
-FLAGS += os.environ.get("SML_EXTRA_FLAGS", "").split()      # measurement builds, e.g. -DSML_TIMELINE (tools/timeline_probe.py)
+FLAGS += switches.get("SML_EXTRA_FLAGS").split()      # measurement builds, e.g. -DSML_TIMELINE (tools/timeline_probe.py)
 
 
 def _stale(target, deps):

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import torch
 
+from . import switches
+
 # (flag, kwargs) in the reference's order.  Quirks kept on purpose: the type=bool flags are
 # True for ANY non-empty string, and Load_W_hat / clip_grad / need_adaptive have no type at
 # all (a value given on the command line arrives as a non-empty, hence truthy, string).
@@ -94,10 +96,10 @@ def _banner(args, which):
 
 
 def main(which, argv=None):
-    if os.environ.get("SML_FAULT_DUMP_S"):          # debugging aid: every thread's Python stack to stderr after that many seconds (a hung job says where)
+    if switches.get("SML_FAULT_DUMP_S"):          # debugging aid: every thread's Python stack to stderr after that many seconds (a hung job says where)
         import faulthandler
         import sys
-        faulthandler.dump_traceback_later(float(os.environ["SML_FAULT_DUMP_S"]), repeat=False, file=sys.stderr)
+        faulthandler.dump_traceback_later(float(switches.get("SML_FAULT_DUMP_S")), repeat=False, file=sys.stderr)
     from data import dataset2
     from model import transfer
 
@@ -110,7 +112,7 @@ def main(which, argv=None):
         import sys
         script = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "main_%s.py" % which)
         rest = list(sys.argv[1:] if argv is None else argv)
-        code, _ = launch.spawn_ranks([sys.executable, script] + rest, args.gpus, one_device=os.environ.get("SML_ONE_DEVICE") == "1",
+        code, _ = launch.spawn_ranks([sys.executable, script] + rest, args.gpus, one_device=switches.get("SML_ONE_DEVICE") == "1",
                                       timeout=launch.job_timeout(args.job_timeout))
         raise SystemExit(code)
     if which == "yelp" and "LOCAL_RANK" not in os.environ:
@@ -132,7 +134,7 @@ def main(which, argv=None):
     # The host side of this process only draws random numbers and slices index arrays; torch's CPU
     # thread pool costs tens of ms per randperm(n > 32768) to wake (it splits the arange fill), so keep
     # host torch ops on the calling thread.  Results do not depend on the thread count.
-    torch.set_num_threads(int(os.environ.get("SML_HOST_THREADS", "1")))
+    torch.set_num_threads(int(switches.get("SML_HOST_THREADS")))
     if which == "yelp":
         print("###(multi num,l2)", 10, 1e-06)                     # the reference's (unused) sweep banner
     # seeding order of the reference (main_yelp.py:137-139)

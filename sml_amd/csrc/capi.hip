@@ -361,22 +361,40 @@ int wg_tiles(int rows, int mt) { const int r = SML_TM * mt; return (rows + r - 1
 // latency-bound on the per-tile chain: split the hidden dimension of the forward over 4 (or 2)
 // workgroups per row tile and the backward over d/16 coordinate slices.  Once the row tiles alone
 // fill the chip the splits only repeat the gather/prologue work, so large batches keep one
-// workgroup per tile.  (SML_FWD_NS / SML_BWD_SPLIT override the policy for measurements.)
+// workgroup per tile.  (Switches::fwd_ns / bwd_split override the policy for measurements.)
 int env_int(const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; }
-// closed-form replay (sml_dev.h): a launch that replays rows up to step `to` uses the tables behind the schedule when the
-// bias-correction term has flattened (to >= SML_RP_K0; SML_REPLAY_K0 overrides for tests) -- SML_REPLAY_CLOSED=0: the loop everywhere
-int replay_len(const sml_ctx* c, int64_t to) {
-    const int on = env_int("SML_REPLAY_CLOSED", 1), k0 = env_int("SML_REPLAY_K0", SML_RP_K0);
-    return (on != 0 && to >= k0 && to - SML_RP_N >= 1 && to + 1 < c->sched_len) ? c->sched_len : 0;
+const char* env_str(const char* name, const char* dflt) { const char* v = getenv(name); return v ? v : dflt; }
+// Every environment switch of the library, one line each: field, variable, default, meaning (the source of INTEGRATION.md's table).  An entry point
+// that depends on one reads them ALL once, at its top, and passes the value down: per call (A/B tests flip switches inside one process), never per batch.
+struct Switches {
+    bool replay_closed = env_int("SML_REPLAY_CLOSED", 1) != 0;        // 0: a row's pending zero-gradient Adam steps are always walked one by one
+    int fwd_ns = env_int("SML_FWD_NS", 0);                            // 1 | 2 | 4: workgroups per row tile of the training forward (0: the policy)
+    int bwd_split = env_int("SML_BWD_SPLIT", -1);                     // 0 | 1: the backward's d/16 coordinate split off / on (-1: the policy)
+    bool fwd_bx3 = env_int("SML_FWD_BX3", 1) != 0;                    // 0: table-sized forwards at d = 32 on fp32 products instead of bf16x3
+    bool mf_bx3 = env_int("SML_MF_BX3", 1) != 0;                      // 0: the MF-stage forward's fc1 / fc2 on fp32 products instead of bf16x3
+    bool mf_fused_update = env_int("SML_MF_FUSED_UPDATE", 1) != 0;    // 0: the MF row update as its own k_run_update launch
+    bool mf_distinct = env_int("SML_MF_DISTINCT", 1) != 0;            // 0: the MF step runs the net once per occurrence, not per distinct row
+    bool peer_push_launch = env_int("SML_PEER_PUSH_LAUNCH", 0) != 0;  // 1: the MF exchange's push as its own launch (k_peer_push)
+    bool peer_wait_launch = env_int("SML_PEER_WAIT_LAUNCH", 0) != 0;  // 1: the MF exchange's wait as its own launch (k_peer_wait)
+    bool tr_defer = env_int("SML_TR_DEFER", 1) != 0;                  // 0: the merged launch's last tail workgroup takes the conv step itself
+    bool tr_a2_recompute = env_int("SML_TR_A2_RECOMPUTE", 1) != 0;    // 0: the TR forward saves Gelu(z1) as well as z1
+    bool trace = env_int("SML_TRACE", 0) != 0;                        // 1: one stderr line per MF epoch naming the form that ran
+    bool prep_cub = !strcmp(env_str("SML_PREP", ""), "cub");          // cub: the library-sort reference of the index lists (test build only)
+    bool prep_ballot = !strcmp(env_str("SML_PREP_RANK", ""), "ballot");     // ballot: ranks by ballots whatever the start-up probe found
+    const char* peer_mem = env_str("SML_PEER_MEM", "");               // finegrained | plain: the first kind sml_peer_alloc tries (default: uncached)
+    bool debug_peer = env_str("SML_DEBUG_PEER", nullptr) != nullptr;  // set: sml_peer_alloc reports the kind of memory it got
+    static Switches read() { return Switches(); }
+};
+// closed-form replay (sml_dev.h): a launch that replays rows up to step `to` uses the tables behind the schedule once the bias correction has flattened
+int replay_len(const Switches& sw, const sml_ctx* c, int64_t to) {
+    return (sw.replay_closed && to >= SML_RP_K0 && to - SML_RP_N >= 1 && to + 1 < c->sched_len) ? c->sched_len : 0;
 }
-int fwd_split(int row_tiles) {
-    const int forced = env_int("SML_FWD_NS", 0);
-    if (forced == 1 || forced == 2 || forced == 4) return forced;
+int fwd_split(const Switches& sw, int row_tiles) {
+    if (sw.fwd_ns == 1 || sw.fwd_ns == 2 || sw.fwd_ns == 4) return sw.fwd_ns;
     return row_tiles <= 64 ? 4 : row_tiles <= 128 ? 2 : 1;
 }
-int bwd_split(int row_tiles) {
-    const int forced = env_int("SML_BWD_SPLIT", -1);
-    if (forced == 0 || forced == 1) return forced;
+int bwd_split(const Switches& sw, int row_tiles) {
+    if (sw.bwd_split == 0 || sw.bwd_split == 1) return sw.bwd_split;
     return row_tiles <= 128 ? 1 : 0;
 }
 
@@ -506,10 +524,10 @@ SmlRunArgs run_args_compact(const IndexSet& X, int64_t b) {
 }
 // ... and the Adam half of a row update at step `cur`: the rows continue from the replayed copies the gradient pass left
 // in xin / mrep / vrep (the user list's always; rep_i, rep_x_stride and rep_x_off are the caller's)
-void run_args_adam(SmlRunArgs& u, const sml_mf_tables* t, const sml_ctx* ctx, int cur, float lr) {
+void run_args_adam(SmlRunArgs& u, const sml_mf_tables* t, const sml_ctx* ctx, int cur, float lr, const Switches& sw) {
     u.w_user = t->w_user; u.w_item = t->w_item;
     u.m_user = t->m_user; u.v_user = t->v_user; u.m_item = t->m_item; u.v_item = t->v_item;
-    u.last_user = t->step_user; u.last_item = t->step_item; u.sched = ctx->sched.p; u.cur_step = cur; u.lr = lr; u.sched_len = replay_len(ctx, cur - 1);
+    u.last_user = t->step_user; u.last_item = t->step_item; u.sched = ctx->sched.p; u.cur_step = cur; u.lr = lr; u.sched_len = replay_len(sw, ctx, cur - 1);
     u.rep_x = ctx->xin.p; u.rep_m = ctx->mrep.p; u.rep_v = ctx->vrep.p; u.rep_u = 1;
 }
 SmlThetaAdamArgs theta_adam_args(const sml_ctx* ctx, float* theta, float* m, float* v, float* grad, float weight_decay, const SmlSched& sc) {
@@ -562,22 +580,6 @@ void peer_step(sml_ctx* c, int kind, int incr, SmlPeerPush* push, SmlPeerPoll* p
     poll->timeout = c->peer.timeout;
     poll->err = c->peer.err;
 }
-
-// SML_PREP=cub keeps the library sort (A/B tests); default: index_prep.hip
-static bool prep_by_hand() {
-    const char* e = getenv("SML_PREP");          // (read per call: the A/B test flips it inside one process)
-    return !(e && !strcmp(e, "cub"));
-}
-// ... and the by-hand preparation's own debug switches, read once per preparation (per call: the A/B tests flip them inside one process)
-struct PrepSwitches {
-    bool nowave;     // SML_PREP_NOWAVE (set): no one-wavefront-per-bucket kernels (k_prep_wave, k_prep_count)
-    bool count;      // SML_PREP_COUNT=0 clears it: no counter-per-row kernel (k_prep_count)
-    bool ballot;     // SML_PREP_RANK=ballot: the ballot ranking whatever the start-up probe found
-    static PrepSwitches read() {
-        const char* rk = getenv("SML_PREP_RANK");
-        return {getenv("SML_PREP_NOWAVE") != nullptr, env_int("SML_PREP_COUNT", 1) != 0, rk && !strcmp(rk, "ballot")};
-    }
-};
 
 // a completed read-back of the sorted-order violation count that is not zero: some earlier list of this index set was wrong
 int sort_order_check(IndexSet* c) {
@@ -666,8 +668,7 @@ private:
 
 // Job 1 of a preparation: the bit widths and the bucket geometry -- every scalar of the kernels' arguments; returns the entry
 // width in bytes.  Pure: no HIP call, no IndexSet.
-int prep_geometry(SmlPrepArgs& a, const PrepSource& s, int64_t n, int64_t nb, const sml_batch_plan* plan, bool dups, bool want_dense,
-                  const PrepSwitches& sw) {
+int prep_geometry(SmlPrepArgs& a, const PrepSource& s, int64_t n, int64_t nb, const sml_batch_plan* plan, bool dups, bool want_dense) {
     const int batch = s.batch, nis = s.nis;
     a.tri = s.tri; a.n = n; a.batch = batch; a.nb = (int)nb; a.tpb = (batch + SML_PREP_TT - 1) / SML_PREP_TT;
     a.boff = plan ? plan->batch_off_dev : nullptr; a.pad_tiles = s.pad_tiles; a.records = dups ? 0 : 1;
@@ -695,10 +696,10 @@ int prep_geometry(SmlPrepArgs& a, const PrepSource& s, int64_t n, int64_t nb, co
         t.allruns = (T == 1 && s.allruns_i) ? 1 : 0; t.rshift = t.allruns ? 0 : 1;
         t.lmul = T ? nis : 1;
         t.ntile = T ? nis * a.tpb : (s.has_users ? a.tpb : 0);
-        const bool by_wave = dups && !t.allruns && !sw.nowave;
+        const bool by_wave = dups && !t.allruns;
         t.wave = (by_wave && per_bucket <= 256) ? 1 : 0;
         // few row bits left inside a bucket: a counter per row instead of a sort (k_prep_count)
-        if (by_wave && t.nbk > 1 && (1 << t.hb) <= SML_PREP_CROWS && per_bucket <= 1024 && sw.count) t.wave = 2;
+        if (by_wave && t.nbk > 1 && (1 << t.hb) <= SML_PREP_CROWS && per_bucket <= 1024) t.wave = 2;
     }
     a.large_cap = (int)((n + (int64_t)nis * n) / SML_PREP_SMALL) + 8;
     if (dups) {
@@ -724,7 +725,7 @@ int prep_geometry(SmlPrepArgs& a, const PrepSource& s, int64_t n, int64_t nb, co
 
 // Job 2: the buffers of index set `c` sized for that geometry, and their pointers in the kernels' arguments.  (Its one stream
 // operation clears the spill counters of the distinct-row form.)
-int prep_buffers(IndexSet* c, SmlPrepArgs& a, const PrepSource& s, bool dups, const PrepSwitches& sw, hipStream_t st) {
+int prep_buffers(IndexSet* c, SmlPrepArgs& a, const PrepSource& s, bool dups, const Switches& sw, hipStream_t st) {
     const size_t n = (size_t)a.n, n_items = (size_t)s.nis * n, nb = (size_t)a.nb, batch = (size_t)a.batch;
     HIPCHK(c->key_u.ensure(n + 1)); HIPCHK(c->key_u2.ensure(n + 1));
     HIPCHK(c->key_i.ensure(n_items + 1)); HIPCHK(c->key_i2.ensure(n_items + 1));
@@ -773,7 +774,7 @@ int prep_buffers(IndexSet* c, SmlPrepArgs& a, const PrepSource& s, bool dups, co
     // stable ranks from one returning LDS atomic per occurrence -- only where this device hands them out in lane order (the
     // start-up probe's count, which the kernels read)
     HIPCHK(c->rank_viol.ensure(4));
-    a.rank_viol = sw.ballot ? nullptr : c->rank_viol.p;
+    a.rank_viol = sw.prep_ballot ? nullptr : c->rank_viol.p;
     a.order_viol = c->rank_viol.p + 1;             // (word 1 of the probe's block: zeroed with it, never reset)
     return SML_OK;
 }
@@ -816,15 +817,14 @@ int prep_readbacks(IndexSet* c, int64_t nb, bool dups, bool lists, hipStream_t s
 // The index lists of `n` triples (PAIRS: occurrences) from source `s` into index set `c`, by index_prep.hip: per batch the
 // occurrences sorted by row (stable), run records (dups: compact records of the duplicated runs + "row occurs once" marks; else
 // one record per sorted position), all queued on `st`.
-int prep_epoch(IndexSet* c, const PrepSource& s, int64_t n, const sml_batch_plan* plan, bool dups, bool want_dense, hipStream_t st) {
+int prep_epoch(const Switches& sw, IndexSet* c, const PrepSource& s, int64_t n, const sml_batch_plan* plan, bool dups, bool want_dense, hipStream_t st) {
     const int64_t nb = plan ? plan->n_batches : (n + s.batch - 1) / s.batch;
     int rc = sort_order_check(c); if (rc) return rc;
     c->by_hand = true; c->slot_stride = 0; c->dense_stride = 0; c->dense = false;
     if (n == 0) { c->n = 0; c->batch = s.batch; c->triples = s.origin(); return SML_OK; }
     if ((int64_t)s.nis * n > 0x7fffffff) return fail(SML_EINVAL, "index preparation", "too many item occurrences in one epoch");
-    const PrepSwitches sw = PrepSwitches::read();
     SmlPrepArgs a = zeroed<SmlPrepArgs>();
-    const int ent_bytes = prep_geometry(a, s, n, nb, plan, dups, want_dense, sw);
+    const int ent_bytes = prep_geometry(a, s, n, nb, plan, dups, want_dense);
     if ((rc = prep_buffers(c, a, s, dups, sw, st))) return rc;
     if (!c->rank_probed) {       // measured once per index set, on the stream, ahead of its first preparation (no host wait)
         HIPCHK(hipMemsetAsync(c->rank_viol.p, 0, 4 * sizeof(int), st));
@@ -841,7 +841,7 @@ int prep_epoch(IndexSet* c, const PrepSource& s, int64_t n, const sml_batch_plan
 #include "../../tests/csrc/prep_cub_reference.inc"
 #endif
 
-// SML_PREP=cub asks for the library-sort REFERENCE implementation of the lists instead: that lives under tests/csrc and is
+// Switches::prep_cub asks for the library-sort REFERENCE implementation of the lists instead: that lives under tests/csrc and is
 // compiled only into the test build of this library (tests/build_reference.py, -DSML_TEST_PREP_REFERENCE); the product has no
 // library sort and says so.
 int no_prep_reference() {
@@ -849,10 +849,10 @@ int no_prep_reference() {
 }
 
 // The index lists of an epoch of one GPU's triples (prep_epoch).  bx (bare step on several GPUs): the item lists are the JOB's.
-int sort_epoch(IndexSet* c, const int64_t* tri, int64_t n, int batch, int pad_tiles, int64_t n_user, int64_t n_item,
+int sort_epoch(const Switches& sw, IndexSet* c, const int64_t* tri, int64_t n, int batch, int pad_tiles, int64_t n_user, int64_t n_item,
                bool dups, hipStream_t st, const sml_batch_plan* plan = nullptr, const sml_bare_exchange* bx = nullptr, bool want_dense = false) {
-    if (prep_by_hand())
-        return prep_epoch(c, bx ? PrepSource::replicated(tri, bx, n_user, n_item, batch, pad_tiles) : PrepSource::own(tri, n_user, n_item, batch, pad_tiles),
+    if (!sw.prep_cub)
+        return prep_epoch(sw, c, bx ? PrepSource::replicated(tri, bx, n_user, n_item, batch, pad_tiles) : PrepSource::own(tri, n_user, n_item, batch, pad_tiles),
                           n, plan, dups, want_dense, st);
 #ifdef SML_TEST_PREP_REFERENCE
     return sort_epoch_reference(c, tri, n, batch, pad_tiles, n_user, n_item, dups, st, plan, bx);
@@ -864,11 +864,11 @@ int sort_epoch(IndexSet* c, const int64_t* tri, int64_t n, int batch, int pad_ti
 // Index lists of the item-sharded bare step.  A: this rank's users (as in sort_epoch) and the JOB's occurrences of the
 // tail rows this rank owns (every run is applied by the run kernel).  Bset: this rank's own occurrences of head rows
 // (summed into the dense partial).
-int sort_epoch_sharded(IndexSet* A, IndexSet* Bset, const int64_t* tri, int64_t n, int batch, int64_t n_user, const sml_bare_shard* sh,
+int sort_epoch_sharded(const Switches& sw, IndexSet* A, IndexSet* Bset, const int64_t* tri, int64_t n, int batch, int64_t n_user, const sml_bare_shard* sh,
                        int64_t rows_cap, hipStream_t st) {
-    if (prep_by_hand()) {
-        int rc = prep_epoch(A, PrepSource::shard_tail(tri, sh, rows_cap, n_user, batch), n, nullptr, true, false, st);
-        if (!rc && sh->head_rows > 0) rc = prep_epoch(Bset, PrepSource::shard_head(tri, sh, n_user, batch), n, nullptr, true, false, st);
+    if (!sw.prep_cub) {
+        int rc = prep_epoch(sw, A, PrepSource::shard_tail(tri, sh, rows_cap, n_user, batch), n, nullptr, true, false, st);
+        if (!rc && sh->head_rows > 0) rc = prep_epoch(sw, Bset, PrepSource::shard_head(tri, sh, n_user, batch), n, nullptr, true, false, st);
         return rc;
     }
 #ifdef SML_TEST_PREP_REFERENCE
@@ -964,11 +964,12 @@ int sml_transfer_forward(sml_ctx* ctx, const float* theta, int net, const float*
     if (n_rows == 0) return SML_OK;
     if (!ctx || !theta || !x_t || !x_hat || !out || (net != 0 && net != 1) || n_rows < 0 || n_rows > 0x7fffffff)
         return fail(SML_EINVAL, "sml_transfer_forward", "bad argument");
+    const Switches sw = Switches::read();
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     int rc = ensure_pk(ctx); if (rc) return rc;
-    // table-sized calls at d = 32: the bf16x3 kernel (fp32-grade results on the bf16 matrix rate; SML_FWD_BX3=0: the fp32 products)
-    const size_t bx3 = n_rows > 8192 && env_int("SML_FWD_BX3", 1) != 0 ? sml_bx3_bytes(ctx->d) : 0;
+    // table-sized calls at d = 32: the bf16x3 kernel (fp32-grade results on the bf16 matrix rate; Switches::fwd_bx3 off: the fp32 products)
+    const size_t bx3 = n_rows > 8192 && sw.fwd_bx3 ? sml_bx3_bytes(ctx->d) : 0;
     if (bx3) {
         HIPCHK(ctx->pkx.ensure(bx3 / sizeof(float) + 4));
         PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack_bx3(ctx->d, theta, ctx->pkx.p, st)));
@@ -1004,6 +1005,7 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
                        const sml_mf_exchange* xchg, const sml_batch_plan* plan, void* stream) {
     if (!ctx || !theta || !t || !step || !batch_loss || batch <= 0 || (plan ? n < 0 : n <= 0) || (n > 0 && !triples))
         return fail(SML_EINVAL, "sml_mf_stage_epoch", "bad argument");
+    const Switches sw = Switches::read();
     int rc;
     if (plan && !plan->batch_off_dev) return fail(SML_EINVAL, "sml_mf_stage_epoch", "batch plan does not cover the triples");     // (the index preparation reads the offsets on the device)
     if (plan && (rc = check_plan("sml_mf_stage_epoch", plan, n, batch))) return rc;
@@ -1029,26 +1031,26 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
     if ((rc = ensure_sched(ctx, lr, *step + nb + 1, st))) return rc;
     const int lstride = (wg_tiles(batch, 1) + wg_tiles(2 * batch, 1)) * (d / 16);     // one loss partial per backward workgroup
     const int64_t out_pstride = (int64_t)SML_R * (tiles_of(batch) + tiles_of(2 * batch)) * d;
-    const int fns = fwd_split(wg_tiles(batch, 1) + wg_tiles(2 * batch, 1)), bsplit = bwd_split(wg_tiles(batch, 1) + wg_tiles(2 * batch, 1));
+    const int fns = fwd_split(sw, wg_tiles(batch, 1) + wg_tiles(2 * batch, 1)), bsplit = bwd_split(sw, wg_tiles(batch, 1) + wg_tiles(2 * batch, 1));
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
     PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack(d, theta, pk_cur(ctx), st)));
-    // d = 32, one workgroup per row tile: the forward's fc1 / fc2 on bf16x3 products (k_mf_fwd_bx3; SML_MF_BX3=0: fp32 products);
+    // d = 32, one workgroup per row tile: the forward's fc1 / fc2 on bf16x3 products (k_mf_fwd_bx3; Switches::mf_bx3 off: fp32 products);
     // theta is fixed during the MF stage: its bf16 planes are packed once per epoch
-    const bool mf_bx3 = fns == 1 && sml_bx3_bytes(d) > 0 && env_int("SML_MF_BX3", 1) != 0;
+    const bool mf_bx3 = fns == 1 && sml_bx3_bytes(d) > 0 && sw.mf_bx3;
     if (mf_bx3) {
         HIPCHK(ctx->pkx.ensure(sml_bx3_bytes(d) / sizeof(float) + 4));
         PROFILED(PC_PACK, HIPCHK(sml_launch_theta_pack_bx3(d, theta, ctx->pkx.p, st)));
     }
     // One GPU, the one-workgroup-per-tile backward, a row inside one wavefront (d <= 64): the backward takes the row update itself
-    // (SmlFusedUpdate; SML_MF_FUSED_UPDATE=0: the k_run_update launch, A/B tests) -- and, round 5, the net runs once per DISTINCT
-    // row of the batch (SmlDense; SML_MF_DISTINCT=0: one pass per occurrence, A/B tests) when the lists allow it
-    const bool can_fuse = !xchg && !bsplit && d <= 64 && ctx->adaptive_beta <= 0.0f && env_int("SML_MF_FUSED_UPDATE", 1) != 0;
-    const bool want_dense = can_fuse && fns == 1 && env_int("SML_MF_DISTINCT", 1) != 0;
+    // (SmlFusedUpdate; Switches::mf_fused_update off: the k_run_update launch, A/B tests) -- and, round 5, the net runs once per DISTINCT
+    // row of the batch (SmlDense; Switches::mf_distinct off: one pass per occurrence, A/B tests) when the lists allow it
+    const bool can_fuse = !xchg && !bsplit && d <= 64 && ctx->adaptive_beta <= 0.0f && sw.mf_fused_update;
+    const bool want_dense = can_fuse && fns == 1 && sw.mf_distinct;
     const int64_t x_total = !xchg ? 0 : xchg->item_off ? xchg->item_off[nb] : (int64_t)xchg->world * 2 * n;
     const int64_t x_stride = !xchg ? 0 : xchg->slot_stride > 0 ? xchg->slot_stride : (int64_t)2 * batch;
     const bool x_by_hand = xchg && xchg->lists_unsorted != 0;
     PROFILED(PC_SORT, {
-    rc = sort_epoch(&ctx->ix[0], triples, n, batch, 1, t->n_user, t->n_item, false, st, plan, nullptr, want_dense);
+    rc = sort_epoch(sw, &ctx->ix[0], triples, n, batch, 1, t->n_user, t->n_item, false, st, plan, nullptr, want_dense);
     if (!rc && xchg && x_total > 0 && x_by_hand) {
         // the job's item occurrences arrive batch-major and UNSORTED: every batch's run list by index_prep.hip (occurrence source 4:
         // one stream of explicit (key, value) pairs; records mode) -- no library sort anywhere on this path since round 5
@@ -1066,7 +1068,7 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
             px.n_batches = nb; px.batch_off_dev = ctx->xoff.p;
         }
         if (x_seg > 0x3fffffff) return fail(SML_EINVAL, "sml_mf_stage_epoch", "a batch's job-wide item list is too long");
-        rc = prep_epoch(&ctx->ix[1], PrepSource::pairs(xchg->key_items, xchg->val_items, (int64_t)xchg->world * x_stride, t->n_item, (int)x_seg),
+        rc = prep_epoch(sw, &ctx->ix[1], PrepSource::pairs(xchg->key_items, xchg->val_items, (int64_t)xchg->world * x_stride, t->n_item, (int)x_seg),
                         x_total, xchg->item_off ? &px : nullptr, false, false, st);
     } else if (!rc && xchg && x_total > 0) {   // ... or run records over the caller's sorted keys
         HIPCHK(ctx->rec_x.ensure((size_t)x_total));
@@ -1078,7 +1080,7 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
     float* dx_buf = xchg ? xchg->dx_local : ctx->dx.p;
     const bool dense = want_dense && ctx->ix[0].by_hand && ctx->ix[0].dense;
     const bool fused = can_fuse && !dense && ctx->ix[0].by_hand && ctx->ix[0].slot_stride > 0;
-    if (env_int("SML_TRACE", 0))        // (tests assert WHICH form ran: an A/B that silently compares a form with itself proves nothing)
+    if (sw.trace)        // (tests assert WHICH form ran: an A/B that silently compares a form with itself proves nothing)
         fprintf(stderr, "[sml] mf_stage_epoch: form=%s batches=%lld batch=%d d=%d\n", dense ? "distinct-rows" : fused ? "per-occurrence+fused-update" : "per-occurrence+run-update",
                 (long long)nb, batch, d);
     if (fused) {
@@ -1111,7 +1113,7 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
             w.seg[s].dx = L.dx(s, dx_buf);
         }
         L.fill(f, out_pstride, ctx->variant == 1);
-        f.cur_step = cur; f.sched = ctx->sched.p; f.sched_len = replay_len(ctx, cur - 1);
+        f.cur_step = cur; f.sched = ctx->sched.p; f.sched_len = replay_len(sw, ctx, cur - 1);
         PROFILED(PC_FWD, if (mf_bx3) HIPCHK(sml_launch_mf_fwd_bx3(d, f, ctx->pkx.p, tiles, st)); else HIPCHK(sml_launch_fwd(d, 1, fns, f, tiles, st)));
         L.fill(w, loss_kind, fns, out_pstride);
         w.l2 = l2; w.scale = bw.scale(b, xchg ? xchg->loss_scale : 1.0f); w.loss_part = ctx->loss_part.p + b * lstride;
@@ -1135,8 +1137,8 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
             fu.mrep = ctx->mrep.p; fu.vrep = ctx->vrep.p; fu.sched = ctx->sched.p; fu.cur_step = cur;
         }
         // several GPUs, one-shot exchange, the one-workgroup-per-tile backward: its item tiles push their rows themselves and every
-        // workgroup signals -- the grid is cut for the batch CAP (the same on every rank).  SML_PEER_PUSH_LAUNCH=1: A/B (k_peer_push)
-        const bool push_fused = mf_peers && !bsplit && !env_int("SML_PEER_PUSH_LAUNCH", 0) &&
+        // workgroup signals -- the grid is cut for the batch CAP (the same on every rank).  Switches::peer_push_launch: A/B (k_peer_push)
+        const bool push_fused = mf_peers && !bsplit && !sw.peer_push_launch &&
                                 (xchg->push_rows > 0 ? xchg->push_rows : x_stride) >= 2 * (int64_t)B;
         SmlPeerPush push_f; SmlPeerPoll poll_f;
         int bwd_grid = tiles;
@@ -1170,7 +1172,7 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
                         peer_step(ctx, 1, sml_peer_push_blocks(x_push * d), &push, &poll);
                         HIPCHK(sml_launch_peer_push(L.dx(1, dx_buf), x_push * d, push, st));
                     }
-                    if (env_int("SML_PEER_WAIT_LAUNCH", 0)) HIPCHK(sml_launch_peer_wait(poll, st));      // (A/B: the wait as its own launch)
+                    if (sw.peer_wait_launch) HIPCHK(sml_launch_peer_wait(poll, st));      // (A/B: the wait as its own launch)
                     else u.wait = poll;                                                               // ... or at the head of the row update
                 });
                 gathered = poll.slot0;
@@ -1183,7 +1185,7 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
             u.n_i = xchg->item_off ? (int)(xchg->item_off[b + 1] - x0) : xchg->world * 2 * B;
             u.dx_i = gathered;
         }
-        run_args_adam(u, t, ctx, cur, lr);
+        run_args_adam(u, t, ctx, cur, lr, sw);
         // rows continue from the forward's replayed copies (local scratch; the multi-GPU item list's slots index the
         // all-gathered buffer instead, so item rows are replayed from the table there)
         u.rep_i = xchg ? 0 : 1; u.rep_x_stride = 3 * d; u.rep_x_off = d;
@@ -1197,12 +1199,13 @@ int sml_mf_stage_epoch(sml_ctx* ctx, const float* theta, const sml_mf_tables* t,
 int sml_mf_adam_flush(sml_ctx* ctx, const sml_mf_tables* t, float lr, int64_t step, void* stream) {
     if (!ctx || !t || step < 0) return fail(SML_EINVAL, "sml_mf_adam_flush", "bad argument");
     if (step == 0) return SML_OK;
+    const Switches sw = Switches::read();
     DevGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = ensure_sched(ctx, lr, step + 1, st))) return rc;
-    PROFILED(PC_FLUSH, HIPCHK(sml_launch_adam_flush(ctx->d, t->w_user, t->m_user, t->v_user, t->step_user, t->n_user, ctx->sched.p, (int)step, replay_len(ctx, step), st));
-             HIPCHK(sml_launch_adam_flush(ctx->d, t->w_item, t->m_item, t->v_item, t->step_item, t->n_item, ctx->sched.p, (int)step, replay_len(ctx, step), st)));
+    PROFILED(PC_FLUSH, HIPCHK(sml_launch_adam_flush(ctx->d, t->w_user, t->m_user, t->v_user, t->step_user, t->n_user, ctx->sched.p, (int)step, replay_len(sw, ctx, step), st));
+             HIPCHK(sml_launch_adam_flush(ctx->d, t->w_item, t->m_item, t->v_item, t->step_item, t->n_item, ctx->sched.p, (int)step, replay_len(sw, ctx, step), st)));
     return SML_OK;
 }
 
@@ -1212,6 +1215,7 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
                        sml_grad_hook grad_hook, void* hook_user, const sml_batch_plan* plan, void* stream) {
     if (!ctx || !theta || !adam_m || !adam_v || !t || !step || !batch_loss || batch <= 0 || (plan ? n < 0 : n <= 0) || (n > 0 && !triples))
         return fail(SML_EINVAL, "sml_tr_stage_epoch", "bad argument");
+    const Switches sw = Switches::read();
     int rc;
     if (plan && (rc = check_plan("sml_tr_stage_epoch", plan, n, batch))) return rc;
     if ((rc = check_sizes(ctx, "sml_tr_stage_epoch", batch, 0))) return rc;
@@ -1227,7 +1231,7 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
     const bool clip = ctx->clip_max_norm > 0.0f;
     if (clip) HIPCHK(ctx->clip_sumsq.ensure(4));
     float* grad = theta_grad ? theta_grad : ctx->grad.p;
-    const int fns = fwd_split(wg_tiles(batch, 1) + wg_tiles(2 * batch, 1));
+    const int fns = fwd_split(sw, wg_tiles(batch, 1) + wg_tiles(2 * batch, 1));
     // The step: forward, backward head (loss -> dOut -> dZ1), then ONE launch with the weight-gradient tiles and the rest of
     // the backward beside them.  What follows the gradient is one of three forms, fixed for the epoch:
     //   PEER   peer mappings attached: the tile workgroups store their finished tiles into every rank's inbox; the Adam
@@ -1250,12 +1254,11 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
     const int64_t ns = sml_net_size(d);
     // Deferred conv step (one GPU, fused Adam, hidden-split forward): the merged launch of every batch
     // but the epoch's last leaves the conv-gradient partials to the NEXT batch's forward, which adds them and steps the 190
-    // conv parameters in its prologue (SmlFwdArgs).  SML_TR_DEFER=0: the merged launch's last tail workgroup does it.
-    const bool defer = fns == 4 && form == FUSED && !plan && nb > 1 && env_int("SML_TR_DEFER", 1) != 0;
+    // conv parameters in its prologue (SmlFwdArgs).  Switches::tr_defer off: the merged launch's last tail workgroup does it.
+    const bool defer = fns == 4 && form == FUSED && !plan && nb > 1 && sw.tr_defer;
     // Round 5: the forward saves z1 only; the dW2 tiles of the merged launch apply Gelu to their B operand themselves (x * sigmoid(1.702 x):
-    // ten instructions on a VALU that is idle there) -- 1.5 MB less written per step, bit-identical.  SML_TR_A2_RECOMPUTE=0: the forward
+    // ten instructions on a VALU that is idle there) -- 1.5 MB less written per step, bit-identical.  Switches::tr_a2_recompute off: the forward
     // saves Gelu(z1) as well (A/B tests)
-    const bool a2_recompute = env_int("SML_TR_A2_RECOMPUTE", 1) != 0;
     int prev_split = 0, prev_total = 0;
     if (defer) {
         HIPCHK(ctx->cstate.ensure((size_t)2 * 2 * 3 * SML_CG));
@@ -1279,12 +1282,12 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
             L.fill(sg, s, bw.tri(b));
             sg.xt_tab = s ? t->last_item : t->last_user;
             sg.xh_tab = s ? t->hat_item : t->hat_user;
-            sg.a1 = L.a1(s); sg.a2 = a2_recompute ? nullptr : L.a2(s);
+            sg.a1 = L.a1(s); sg.a2 = sw.tr_a2_recompute ? nullptr : L.a2(s);
             L.fill(w.seg[s], s);
             w.seg[s].dz1 = L.dz1(s);
             SmlWgSeg& q = wg.seg[s];
             L.fill(q, s);
-            q.a2 = a2_recompute ? L.z1(s) : L.a2(s);
+            q.a2 = sw.tr_a2_recompute ? L.z1(s) : L.a2(s);
             q.grad = write_grad ? grad + s * ns : nullptr;
         }
         L.fill(f, out_pstride, ctx->variant == 1);
@@ -1297,15 +1300,12 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
         // (tiles0 / tiles_total count ROW tiles, the first n_tail workgroups are the backward's tail)
         wg.tiles0 = L.tiles0; wg.tiles_total = tiles;
         wg.n_tail = tiles * (d / 16) > 0 ? tiles * (d / 16) : 1; wg.convg_out = ctx->convg.p; wg.arrive = ctx->arrive.p;
-        wg.defer_conv = (defer && b + 1 < nb) ? 1 : 0; wg.gelu_b = a2_recompute ? 1 : 0;
+        wg.defer_conv = (defer && b + 1 < nb) ? 1 : 0; wg.gelu_b = sw.tr_a2_recompute ? 1 : 0;
         prev_split = L.tiles0 * (d / 16); prev_total = tiles * (d / 16);
         if (form == PEER) {
             SmlThetaAdamArgs ad = theta_adam_args(ctx, theta, adam_m, adam_v, grad, weight_decay, sc);
             peer_step(ctx, 0, sml_wgrad_tiles(d) + 1, &wg.peer, &ad.peer);      // (every tile workgroup + the last tail workgroup push)
             PROFILED(PC_WGRAD, HIPCHK(sml_launch_tr_wgrad2(d, wg, st)));
-            // every workgroup of the Adam kernel polls the counters itself (SML_PEER_POLL_IN_ADAM=0: a one-wavefront
-            // k_peer_wait launch ahead of it instead -- one launch more; same results)
-            static const bool poll_in_adam = env_int("SML_PEER_POLL_IN_ADAM", 1) != 0;
             PROFILED(PC_THETA_ADAM, {
                 if (clip) {
                     // --clip_grad on the peer carrier: the rank-order sum of the slots is materialised once (k_peer_sum polls
@@ -1315,7 +1315,7 @@ int sml_tr_stage_epoch(sml_ctx* ctx, float* theta, float* adam_m, float* adam_v,
                     HIPCHK(sml_launch_grad_sumsq(grad, 2 * ns, ctx->clip_sumsq.p, st));
                     ad.peer.world = 0;
                     ad.clip_sumsq = ctx->clip_sumsq.p; ad.clip_max_norm = ctx->clip_max_norm;
-                } else if (!poll_in_adam) { HIPCHK(sml_launch_peer_wait(ad.peer, st)); ad.peer.waited = 1; }
+                }
                 HIPCHK(sml_launch_theta_adam(d, ad, st));
             });
         } else if (form == FUSED) {
@@ -1353,6 +1353,7 @@ int sml_run_mf_grad(sml_ctx* ctx, const float* theta, const float* user_last, co
                     float* theta_grad, void* stream) {
     if (!ctx || !theta || !user_last || !user_hat || !item_last || !item_hat || !loss || B <= 0)
         return fail(SML_EINVAL, "sml_run_mf_grad", "bad argument");
+    const Switches sw = Switches::read();
     int rc;
     if ((rc = check_sizes(ctx, "sml_run_mf_grad", B, 0))) return rc;
     if ((rc = check_loss_kind(ctx, "sml_run_mf_grad", loss_kind))) return rc;
@@ -1365,7 +1366,7 @@ int sml_run_mf_grad(sml_ctx* ctx, const float* theta, const float* user_last, co
     const int64_t ns = sml_net_size(d);
     const BatchSlots L(ctx, theta, B);
     const int tiles0 = L.tiles0, tiles = L.tiles;
-    const int fns = fwd_split(tiles);
+    const int fns = fwd_split(sw, tiles);
     const int lstride = tiles * (d / 16 > 4 ? d / 16 : 4);
     const int64_t out_pstride = (int64_t)SML_R * (tiles_of(B) + tiles_of(2 * B)) * d;
     HIPCHK(ctx->loss_part.ensure((size_t)2 * lstride));
@@ -1395,7 +1396,7 @@ int sml_run_mf_grad(sml_ctx* ctx, const float* theta, const float* user_last, co
         w.loss_part = ctx->loss_part.p;
         SmlBwdArgs wx = w;
         wx.seg[0].dz1 = nullptr; wx.seg[1].dz1 = nullptr;
-        HIPCHK(sml_launch_bwd(d, bwd_split(tiles), wx, tiles, st));
+        HIPCHK(sml_launch_bwd(d, bwd_split(sw, tiles), wx, tiles, st));
         if (d_user_hat) HIPCHK(hipMemcpyAsync(d_user_hat, ctx->dx.p, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (d_item_hat) HIPCHK(hipMemcpyAsync(d_item_hat, L.dx(1, ctx->dx.p), (size_t)2 * B * d * sizeof(float), hipMemcpyDeviceToDevice, st));
         HIPCHK(sml_launch_loss_finalize(ctx->loss_part.p, 1, lstride, nullptr, loss, st));
@@ -1421,7 +1422,7 @@ int sml_embed_loss_sgd_prepare(sml_ctx* ctx, const int64_t* triples, int64_t n, 
     if (xchg && (xchg->world < 1 || !xchg->items_all)) return fail(SML_EINVAL, "sml_embed_loss_sgd_prepare", "incomplete exchange descriptor");
     { const int rc = check_sizes(ctx, "sml_embed_loss_sgd_prepare", batch, n); if (rc) return rc; }
     DevGuard g(ctx->device);
-    return sort_epoch(&ctx->ix[slot], triples, n, batch, 0, n_user, n_item, true, (hipStream_t)stream, nullptr, xchg);
+    return sort_epoch(Switches::read(), &ctx->ix[slot], triples, n, batch, 0, n_user, n_item, true, (hipStream_t)stream, nullptr, xchg);
 }
 
 int64_t sml_index_lists_read(sml_ctx* ctx, int slot, int which, void* host, int64_t bytes) {
@@ -1463,6 +1464,7 @@ int sml_embed_loss_sgd_epoch(sml_ctx* ctx, void* w_user, void* w_item, int64_t n
                              int loss_kind, float* batch_loss, int prepared_slot, const sml_bare_exchange* xchg, void* stream) {
     if (!ctx || !w_user || !w_item || !triples || !batch_loss || n <= 0 || batch <= 0 || n_user <= 0 || n_item <= 0)
         return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch", "bad argument");
+    const Switches sw = Switches::read();
     if (xchg && (xchg->world < 1 || !xchg->items_all || !xchg->dx_items_all || !xchg->dx_local))
         return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch", "incomplete exchange descriptor");
     if (xchg && !xchg->hook && (!ctx->comm || ctx->comm_world != xchg->world))
@@ -1484,7 +1486,7 @@ int sml_embed_loss_sgd_epoch(sml_ctx* ctx, void* w_user, void* w_item, int64_t n
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
     IndexSet* X = &ctx->ix[prepared_slot < 0 ? 0 : prepared_slot];
     if (prepared_slot < 0) {
-        PROFILED(PC_SORT, rc = sort_epoch(X, triples, n, batch, 0, n_user, n_item, true, st, nullptr, xchg));
+        PROFILED(PC_SORT, rc = sort_epoch(sw, X, triples, n, batch, 0, n_user, n_item, true, st, nullptr, xchg));
         if (rc) return rc;
     } else if (X->n != n || X->batch != batch || X->triples != triples || X->world != (xchg ? xchg->world : 1)) {
         return fail(SML_ESTATE, "sml_embed_loss_sgd_epoch", "index set was prepared for other triples");
@@ -1518,7 +1520,7 @@ int sml_embed_loss_sgd_epoch(sml_ctx* ctx, void* w_user, void* w_item, int64_t n
         }
         SmlRunArgs u = run_args_compact(*X, b);
         int64_t max_rec = xchg ? (int64_t)B / 2 + (int64_t)world * 2 * B : (int64_t)3 * B / 2;
-        if (known && X->by_hand && !xchg && X->lists_nb == nb && env_int("SML_A3_KNOWN_LISTS", 1)) {
+        if (known && X->by_hand && !xchg && X->lists_nb == nb) {
             // the prepared epoch's list slices are on the host: plain arguments, an exact grid
             const int* h = X->lists_host;
             const int ou = h[b], oi = h[(nb + 1) + b];
@@ -1546,6 +1548,7 @@ int sml_embed_loss_sgd_epoch_sharded(sml_ctx* ctx, void* w_user, int64_t n_user,
                                      int loss_kind, float* batch_loss, const sml_bare_shard* sh, void* stream) {
     if (!ctx || !w_user || !triples || !batch_loss || !sh || n <= 0 || batch <= 0 || n_user <= 0 || n_item <= 0)
         return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch_sharded", "bad argument");
+    const Switches sw = Switches::read();
     if (dtype_bytes != 4 && dtype_bytes != 2) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch_sharded", "dtype_bytes must be 4 or 2");
     if (loss_kind != SML_LOSS_BCE && loss_kind != SML_LOSS_BPR) return fail(SML_EINVAL, "sml_embed_loss_sgd_epoch_sharded", "loss_kind");
     int rc;
@@ -1571,7 +1574,7 @@ int sml_embed_loss_sgd_epoch_sharded(sml_ctx* ctx, void* w_user, int64_t n_user,
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
     if (H > 0) HIPCHK(ctx->head_part.ensure((size_t)H * d));
     HIPCHK(ctx->ptr_tab.ensure(16));
-    PROFILED(PC_SORT, rc = sort_epoch_sharded(&ctx->ix[0], &ctx->ix[1], triples, n, batch, n_user, sh, ctx->peer.rows_cap, st));
+    PROFILED(PC_SORT, rc = sort_epoch_sharded(sw, &ctx->ix[0], &ctx->ix[1], triples, n, batch, n_user, sh, ctx->peer.rows_cap, st));
     if (rc) return rc;
     void* inboxes[8];
     for (int q = 0; q < 8; ++q) inboxes[q] = q < W ? ctx->peer.inbox[q] : nullptr;
@@ -1629,6 +1632,7 @@ int sml_embed_loss_adam_epoch(sml_ctx* ctx, const sml_mf_tables* t, const int64_
     if (!ctx || !t || !t->w_user || !t->w_item || !t->m_user || !t->v_user || !t->m_item || !t->v_item || !t->step_user ||
         !t->step_item || !triples || !step || !batch_loss || n <= 0 || batch <= 0)
         return fail(SML_EINVAL, "sml_embed_loss_adam_epoch", "bad argument");
+    const Switches sw = Switches::read();
     if (loss_kind != SML_LOSS_BCE && loss_kind != SML_LOSS_BPR) return fail(SML_EINVAL, "sml_embed_loss_adam_epoch", "loss_kind");
     int rc;
     if ((rc = check_sizes(ctx, "sml_embed_loss_adam_epoch", batch, n))) return rc;
@@ -1642,7 +1646,7 @@ int sml_embed_loss_adam_epoch(sml_ctx* ctx, const sml_mf_tables* t, const int64_
     HIPCHK(ctx->xin.ensure((size_t)3 * batch * d)); HIPCHK(ctx->mrep.ensure((size_t)3 * batch * d)); HIPCHK(ctx->vrep.ensure((size_t)3 * batch * d));
     const int lstride = (int)(((int64_t)batch * (d / 4) + 255) / 256);
     HIPCHK(ctx->loss_part.ensure((size_t)nb * lstride));
-    PROFILED(PC_SORT, rc = sort_epoch(&ctx->ix[0], triples, n, batch, 0, t->n_user, t->n_item, false, st));
+    PROFILED(PC_SORT, rc = sort_epoch(sw, &ctx->ix[0], triples, n, batch, 0, t->n_user, t->n_item, false, st));
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(ctx->loss_part.p, 0, (size_t)nb * lstride * sizeof(float), st));
     for (int64_t b = 0; b < nb; ++b) {
@@ -1655,7 +1659,7 @@ int sml_embed_loss_adam_epoch(sml_ctx* ctx, const sml_mf_tables* t, const int64_
         PROFILED(PC_BARE_GRAD, HIPCHK(sml_launch_bare_grad(d, 4, a, nullptr, st)));
         SmlRunArgs u = run_args_records(ctx->ix[0], bw.off0(b), B);
         u.dx = ctx->dx.p; u.dx_i = ctx->dx.p;
-        run_args_adam(u, t, ctx, cur, lr);
+        run_args_adam(u, t, ctx, cur, lr, sw);
         u.rep_i = 1; u.rep_x_stride = d; u.rep_x_off = 0;
         PROFILED(PC_SEG_ADAM, HIPCHK(sml_launch_run_adam(d, u, (int64_t)3 * B, st)));
     }
@@ -2077,19 +2081,18 @@ int sml_peer_mem_kind(void* ptr) {
 }
 int sml_peer_alloc(int device, int64_t bytes, void** ptr) {
     if (!ptr || bytes <= 0) return fail(SML_EINVAL, "sml_peer_alloc", "bad argument");
+    const Switches sw = Switches::read();
     DevGuard g(device);
     void* p = nullptr;
     // uncached device memory: stores from peers land in HBM and the owner's loads never hit a stale L2 line;
     // fine-grained if the runtime refuses that flag; plain device memory as a last resort (one-device tests)
-    // (SML_PEER_MEM = uncached | finegrained | plain picks the first kind tried: measurements)
-    const char* kind = getenv("SML_PEER_MEM");
-    const int first = kind && !strcmp(kind, "finegrained") ? 1 : kind && !strcmp(kind, "plain") ? 2 : 0;
+    const int first = !strcmp(sw.peer_mem, "finegrained") ? 1 : !strcmp(sw.peer_mem, "plain") ? 2 : 0;
     hipError_t e = hipErrorUnknown;
     int got = -1;
     if (first <= 0) { e = hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocUncached); got = 0; }
     if (e != hipSuccess && first <= 1) { (void)hipGetLastError(); e = hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocFinegrained); got = 1; }
     if (e != hipSuccess) { (void)hipGetLastError(); e = hipMalloc(&p, (size_t)bytes); got = 2; }
-    if (getenv("SML_DEBUG_PEER")) fprintf(stderr, "[sml] sml_peer_alloc(%lld bytes): kind %d (0 uncached, 1 fine-grained, 2 plain), %s\n",
+    if (sw.debug_peer) fprintf(stderr, "[sml] sml_peer_alloc(%lld bytes): kind %d (0 uncached, 1 fine-grained, 2 plain), %s\n",
                                           (long long)bytes, got, hipGetErrorString(e));
     if (e != hipSuccess) return fail(SML_ENOMEM, "sml_peer_alloc", hipGetErrorString(e));
     e = hipMemset(p, 0, (size_t)bytes);
@@ -2485,10 +2488,8 @@ int sml_stream_wait_stream(void* waiter, void* signaler) {
     // work queued on `waiter` after this call starts after everything queued on `signaler` so far.  The event is
     // device-scope (no system fence: nothing on the host reads what the signaler wrote) -- a default event makes the
     // signalling stream write back and invalidate the L2s for the host's benefit
-    static const unsigned flags = getenv("SML_EVENT_FLAGS") ? (unsigned)strtoul(getenv("SML_EVENT_FLAGS"), nullptr, 0)
-                                                            : (hipEventDisableTiming | hipEventDisableSystemFence);
     hipEvent_t ev;
-    HIPCHK(hipEventCreateWithFlags(&ev, flags));
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence));
     hipError_t e = hipEventRecord(ev, (hipStream_t)signaler);
     if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)waiter, ev, 0);
     (void)hipEventDestroy(ev);                   // released once it has completed

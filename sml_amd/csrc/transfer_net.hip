@@ -1282,9 +1282,7 @@ __global__ __launch_bounds__(512) void k_transfer_bwd(SmlBwdArgs a) {
     // Both GEMMs' operand images fit a register ring whole at d <= 64 (dA2: D/16 k-steps x 4 tiles, dA1: 4 k-steps
     // x 5 tiles per wave): they are fetched right after the pair-loss inputs below (loads return in issue order,
     // so the loss stage does not wait for them) and neither GEMM starts with an L2 round trip
-    // (PRE is the launcher's choice: d = 32 always; d = 64 by default -- 220 registers, one workgroup per CU, which is
-    // all a small batch's grid asks for -- with the on-demand form (<= 128 registers, two workgroups per CU) kept
-    // for grids larger than the chip; d = 128: the rings do not fit)
+    // (PRE: d = 32 only.  d = 64 would need 224 registers and measured no faster than fetching on demand with 124; d = 128: no fit)
     static_assert(!PRE || D <= 64, "operand rings fit the register file at d <= 64 only");
     const f32x4* __restrict__ p2b = reinterpret_cast<const f32x4*>(sg.pk + sml_pk_p2b(D));
     const f32x4* __restrict__ p1b = reinterpret_cast<const f32x4*>(sg.pk + sml_pk_p1b(D));
@@ -2173,7 +2171,7 @@ __global__ __launch_bounds__(256) void k_theta_adam(SmlThetaAdamArgs a) {
     constexpr int NS = sml_net_size(D);
     static_assert(NS % 4 == 0, "a thread's four floats belong to one net");
     // several GPUs, one-shot exchange: wait until every rank's gradient tiles have landed in this rank's inbox
-    if constexpr (PEER) { if (!a.peer.waited) peer_wait(a.peer); }
+    if constexpr (PEER) peer_wait(a.peer);
     // four consecutive parameters per thread: 16-byte loads of gradient / theta / m / v, 16-byte stores
     const int i0 = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (i0 >= 2 * NS) return;
@@ -2304,14 +2302,10 @@ hipError_t sml_launch_bwd(int d, int split, const SmlBwdArgs& a, int tiles_total
     if (tiles_total <= 0) return hipSuccess;
     if (split) {      // d/16 workgroups per row tile
         // operand rings preloaded at d = 32 (one memory round trip for the whole kernel); fetched on demand at d >= 64
-        const char* fp = d == 64 ? getenv("SML_BWD_PRE") : nullptr;           // (measurement / test override, d = 64 only)
-        const int force_pre = fp && *fp ? atoi(fp) : -1;
-        const int grid = tiles_total * (d / 16);
         // (d = 64 measured both ways on MI355X, TR batch 256: 39.09 us/batch preloaded vs 39.12 on demand -- no
-        // difference, so the form with 124 registers instead of 224 is the default)
-        const bool pre = d == 32 || (d == 64 && force_pre > 0);
+        // difference, so d = 64 has the form with 124 registers instead of 224 only)
+        const int grid = tiles_total * (d / 16);
         if (d == 32) k_transfer_bwd<32, true><<<dim3(grid), dim3(512), 0, st>>>(a);
-        else if (d == 64 && pre) k_transfer_bwd<64, true><<<dim3(grid), dim3(512), 0, st>>>(a);
         else if (d == 64) k_transfer_bwd<64, false><<<dim3(grid), dim3(512), 0, st>>>(a);
         else if (d == 128) k_transfer_bwd<128, false><<<dim3(grid), dim3(512), 0, st>>>(a);
         else return hipErrorInvalidValue;

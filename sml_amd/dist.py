@@ -30,6 +30,8 @@ SUMS -> scale 1.
 import numpy as np
 import torch
 
+from . import switches
+
 LOSS_BCE = 0       # sml_hip.h: the only mean-type loss kind
 
 
@@ -442,11 +444,10 @@ class _PeerSetup(object):
     mappings are remembered so that a fall-back can release them."""
 
     def __init__(self, engine, dist, group, rows_cap, timeout_s):
-        import os
         self.e, self.dist, self.group = engine, dist, group
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
         self.rows_cap = int(rows_cap)
-        self.timeout_s = float(os.environ.get("SML_PEER_TIMEOUT_S", "120")) if timeout_s is None else float(timeout_s)
+        self.timeout_s = float(switches.get("SML_PEER_TIMEOUT_S")) if timeout_s is None else float(timeout_s)
         self.same_process = dist.get_backend(group) == "threads"
         self.inbox = self.flags = None
         self.opened = []
@@ -461,14 +462,13 @@ class _PeerSetup(object):
             return False
 
     def run(self):
-        import os
         import sys
         e, dist, group = self.e, self.dist, self.group
         dev = e.device
 
         def vote(ok, step):
             good = _vote(dist, group, dev, ok)
-            if not good and self.why and os.environ.get("SML_DEBUG_PEER"):
+            if not good and self.why and switches.get("SML_DEBUG_PEER"):
                 print("[sml_amd.dist] rank %d, peer set-up step %r: %s" % (self.rank, step, self.why), file=sys.stderr)
             return good
 
@@ -521,7 +521,7 @@ class _PeerSetup(object):
         # 4. self-check: SML_PEER_CHECK_ROUNDS (default 6 = three per parity) one-shot all-reduces with a pattern that
         #    changes every round -- a slot served from a stale cache line, or a counter that lags, shows as the previous
         #    round's values; a short hang guard of its own
-        rounds = max(2, int(os.environ.get("SML_PEER_CHECK_ROUNDS", "6")))
+        rounds = max(2, int(switches.get("SML_PEER_CHECK_ROUNDS")))
         n = 4096
         base = torch.arange(n, device=dev, dtype=torch.float32)
         state = {"ok": True}
@@ -683,9 +683,8 @@ def attach(engine, state, dist, hp=None, group=None, rows_cap=None):
     ctx = DistContext(dist, engine.device if hasattr(engine, "device") else "cpu", group)
     engine.dist = ctx
     engine.grad_hook = ctx.tr_grad_hook
-    import os
     import sys
-    want = os.environ.get("SML_COMM", "peer")
+    want = switches.get("SML_COMM")
     ctx.wanted = want
 
     if want == "peer" and hasattr(engine, "peer_attach"):

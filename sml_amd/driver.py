@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import datasets as D
+from . import switches
 from .conv_transfer import ConvTransfer, ConvTransfer_com
 from .evaluation import DeviceRows, test_model
 from .mf import MFbasemode
@@ -86,8 +87,7 @@ class meta_train(object):
         if table_dim != laten_dim:
             raise ValueError("--laten %d does not match the checkpoint's embedding width %d" % (laten_dim, table_dim))
         self.dist = None
-        import os
-        use_dist = dist is not None and (dist.get_world_size() > 1 or os.environ.get("SML_FORCE_DIST") == "1")   # (forced: tests drive the exchange path on one GPU)
+        use_dist = dist is not None and (dist.get_world_size() > 1 or switches.get("SML_FORCE_DIST") == "1")   # (forced: tests drive the exchange path on one GPU)
         if use_dist:
             # keep this rank's user rows only (the checkpoint holds the whole table)
             from . import dist as smldist
@@ -474,8 +474,7 @@ class meta_train(object):
         predicted inputs turn out right, so the reference's random streams are untouched).  Next = the following epoch of
         this call, or the first epoch of the next phase of this stage -- before which the driver draws two torch seeds per
         MF epoch and the pre-sampled MF dataset's constructor shuffles its columns.  SML_TR_SPECULATE=0: off."""
-        import os
-        if os.environ.get("SML_TR_SPECULATE", "1") == "0" or not isinstance(train_set, D.offlineDataset_withsample):
+        if switches.get("SML_TR_SPECULATE") == "0" or not isinstance(train_set, D.offlineDataset_withsample):
             return
         ph = getattr(self, "_phase", None)               # (phase, phases of the stage, columns the MF dataset shuffles)
         if ph is None:
@@ -639,11 +638,10 @@ class meta_train(object):
         (its sampler was built by _prefetch_next).  Between here and that pass the driver makes the torch draws the same
         stretch took one stage earlier (counted) and the MF dataset's constructor shuffles its columns once; a wrong guess
         -- a test stage that trains no transfer, the first stages -- is discarded (datasets.EpochSpeculation)."""
-        import os
         self._tr_first_mark = D.torch_draws()
         nxt, data = getattr(self, "_sample_cache_next", None), getattr(self, "_next_data", (None, None, (None,)))[2]
         draws = self.__dict__.get("_tr_gaps", {}).get("first")
-        if (os.environ.get("SML_TR_SPECULATE", "1") == "0" or nxt is None or draws is None or data[0] is None
+        if (switches.get("SML_TR_SPECULATE") == "0" or nxt is None or draws is None or data[0] is None
                 or self.MF_TrainDataset is not PreSampleDatast or not isinstance(nxt[1], D.offlineDataset_withsample)):
             return
         self._tr_spec = D.EpochSpeculation(nxt[1], draws, (int(data[0].shape[1]) - 1,))

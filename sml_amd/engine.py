@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, switches
 from ._lib import check
 
 NET_PARAM_ORDER = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias",
@@ -405,13 +405,12 @@ class HipEngine(object):
         exchange: several GPUs (DistContext.bare_exchange): the item lists are then the job's.
         Returns a handle for bare_epoch(prepared=...)."""
         if getattr(self, "_prep", None) is None:
-            import os
-            k = int(os.environ.get("SML_PREP_CUS", "0"))
+            k = int(switches.get("SML_PREP_CUS"))
             if k > 0:                                    # the preparation confined to the last k compute units
                 self._prep = self._masked_stream(self._n_cus() - k, self._n_cus())
-            elif os.environ.get("SML_PREP_PRIO", "") in ("low", "high"):
+            elif switches.get("SML_PREP_PRIO") in ("low", "high"):
                 lo, hi = torch.cuda.Stream.priority_range()
-                self._prep = torch.cuda.Stream(device=self.device, priority=int(lo if os.environ["SML_PREP_PRIO"] == "low" else hi))
+                self._prep = torch.cuda.Stream(device=self.device, priority=int(lo if switches.get("SML_PREP_PRIO") == "low" else hi))
             else:
                 self._prep = self._plain_stream()
         tri = self._dev(triples, torch.int64)
@@ -728,7 +727,7 @@ class HipEngine(object):
     # partition (1.38 against 2.55 ms per Yelp-shaped evaluation) and leaves that stream 45 % busy instead of 86 %, but the period
     # is 0.5-1 ms LONGER with it in a same-box A/B (the training kernels beside it run 1 % slower: profiles/r05s_*): the
     # evaluation stream is not the critical path, so the cheaper-to-sit-beside kernel stays the default.
-    EVAL_MODE = __import__("os").environ.get("SML_EVAL", "blocked")
+    EVAL_MODE = switches.get("SML_EVAL")
 
     def eval_ranks(self, user_tab, item_tab, rows, blocked=None, max_workgroups=0, sliced=None):
         wu, wi = self._table(user_tab), self._table(item_tab)
@@ -1006,8 +1005,8 @@ class HipEngine(object):
     # training loop may run on the rest (`training_stream()`); the evaluation then neither shares SIMD issue slots
     # nor a CU's L2 port with the latency-bound training kernels.  SML_SIDE_EVAL_CUS=0 falls back to a low-priority
     # stream over all CUs with a capped grid.
-    SIDE_EVAL_CUS = int(__import__("os").environ.get("SML_SIDE_EVAL_CUS", "-1"))      # -1: a quarter of the chip (64 of 256 CUs)
-    SIDE_EVAL_WORKGROUPS = int(__import__("os").environ.get("SML_SIDE_EVAL_WGS", "0"))   # grid cap of a side-stream evaluation
+    SIDE_EVAL_CUS = int(switches.get("SML_SIDE_EVAL_CUS"))      # -1: a quarter of the chip (64 of 256 CUs)
+    SIDE_EVAL_WORKGROUPS = int(switches.get("SML_SIDE_EVAL_WGS"))   # grid cap of a side-stream evaluation
 
     def _n_cus(self):
         return int(torch.cuda.get_device_properties(self.device).multi_processor_count)
@@ -1046,7 +1045,7 @@ class HipEngine(object):
 
         @contextlib.contextmanager
         def scope():
-            ts = self.training_stream() if os.environ.get("SML_TRAIN_PARTITION", "1") != "0" else None
+            ts = self.training_stream() if switches.get("SML_TRAIN_PARTITION") != "0" else None
             if ts is None:
                 yield
                 return
@@ -1121,7 +1120,7 @@ class HipEngine(object):
         (a flag kernel behind the copies, a polling kernel ahead of the side stream's work) instead of an event: a
         cross-queue barrier packet cost the training stream 2-4 ms per period (31 of them), the two tiny kernels cost
         nothing measurable."""
-        mode = __import__("os").environ.get("SML_SIDE_SYNC", "flag")
+        mode = switches.get("SML_SIDE_SYNC")
         if mode == "event":
             check(self.lib.sml_stream_wait_stream(ctypes.c_void_p(side.cuda_stream), ctypes.c_void_p(cur.cuda_stream)),
                   "sml_stream_wait_stream")
@@ -1164,11 +1163,11 @@ class HipEngine(object):
     # 21 table-sized forwards, 5 ms of its 110.  eval_submit_transferred snapshots what that forward READS (the four tables
     # and theta, one copy launch) and queues the forward itself, into the snapshot slot's own tables, ahead of the rank pass on
     # the evaluation stream's CUs.  Same kernels, same rows, same bits -- the tables the caller holds are not written.
-    TRANSFERRED_MAX_BYTES = int(__import__("os").environ.get("SML_TRANSFERRED_MAX_BYTES", str(24 << 30)))   # ring budget
+    TRANSFERRED_MAX_BYTES = int(switches.get("SML_TRANSFERRED_MAX_BYTES"))   # ring budget
 
     def can_submit_transferred(self, user_tab, item_tab):
         """Whether the ring's six table copies per slot fit the budget (config-4-sized tables keep the in-place order)."""
-        if __import__("os").environ.get("SML_EVAL_TRANSFERRED", "1") == "0":
+        if switches.get("SML_EVAL_TRANSFERRED") == "0":
             return False
         per_slot = 3 * (user_tab.numel() + item_tab.numel()) * 4
         return per_slot * self.SNAPSHOTS <= self.TRANSFERRED_MAX_BYTES
@@ -1226,8 +1225,7 @@ class HipEngine(object):
 
     @staticmethod
     def _flag_timeout():
-        import os
-        return float(os.environ.get("SML_FLAG_TIMEOUT_S", "300"))
+        return float(switches.get("SML_FLAG_TIMEOUT_S"))
 
     def side_sync_check(self, block=True):
         """Raise if a side-stream evaluation gave up waiting for its table snapshot since the last check (its ranks

@@ -28,6 +28,8 @@ import sys
 import threading
 import time
 
+from . import switches
+
 
 def free_port():
     s = socket.socket()
@@ -51,7 +53,7 @@ def rank_env(rank, world, port, one_device=False, base=None):
 
 def is_rank_process():
     """True inside a process that spawn_ranks (or torchrun) started as a rank."""
-    return os.environ.get("SML_LAUNCHED") == "1" or int(os.environ.get("WORLD_SIZE", "1")) > 1
+    return switches.get("SML_LAUNCHED") == "1" or int(os.environ.get("WORLD_SIZE", "1")) > 1
 
 
 def prepare_rank_env():
@@ -61,7 +63,7 @@ def prepare_rank_env():
 
 
 def one_device():
-    return os.environ.get("SML_ONE_DEVICE") == "1"
+    return switches.get("SML_ONE_DEVICE") == "1"
 
 
 def backend():
@@ -98,7 +100,7 @@ def visible_gpus():
 
 def job_timeout(flag_value=None, default=None):
     """Seconds a launched job may run: the command line's value, else SML_JOB_TIMEOUT_S, else `default`; <= 0: no limit."""
-    v = flag_value if flag_value is not None else os.environ.get("SML_JOB_TIMEOUT_S")
+    v = flag_value if flag_value is not None else switches.get("SML_JOB_TIMEOUT_S")
     if v is None or v == "":
         v = default
     if v is None:

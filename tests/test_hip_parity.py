@@ -1085,6 +1085,32 @@ def test_mf_stage_once_per_distinct_row_equals_once_per_occurrence(case, monkeyp
             assert np.mean(err > 2e-4 * np.abs(ref) + 2e-5 * 0.01 * 12) < 5e-3 and err.max() < 0.05 * 0.01 * 12, (err.max(),)
 
 
+@pytest.mark.gpu
+def test_library_switches_are_read_per_call_not_per_process(monkeypatch, capfd):
+    """The library reads its switch table at the top of every entry point: ONE engine, two mf_stage_epoch calls with
+    SML_MF_DISTINCT flipped between them, must run the distinct-row form and then the per-occurrence form.  A table cached per
+    process (or per engine) would run the first form twice -- and every A/B test that flips a switch with monkeypatch.setenv
+    would compare a form with itself.  Batch 1024 is the smallest at which the default policy picks the distinct-row form."""
+    d, U, I, B = 32, 300, 200, 1024
+    rng = np.random.RandomState(3)
+    tri = torch.from_numpy(np.stack([rng.randint(0, U, 2 * B), rng.randint(0, I, 2 * B), rng.randint(0, I, 2 * B)], 1))
+    wu0, wi0 = rng.randn(U, d).astype(np.float32) * 0.3, rng.randn(I, d).astype(np.float32) * 0.3
+    monkeypatch.setenv("SML_TRACE", "1")
+    monkeypatch.delenv("SML_MF_DISTINCT", raising=False)
+    eng = engine(d, B)
+    mf = make_mf(U, I, d, wu0, wi0, device=DEV)
+    torch.manual_seed(11)
+    net = make_transfer(d, device=DEV)
+    lu, li = T(wu0 * 0.9, DEV), T(wi0 * 0.9, DEV)
+    eng.mf_stage_epoch(mf, net, lu, li, tri, B, 0.01, 1e-6)
+    monkeypatch.setenv("SML_MF_DISTINCT", "0")
+    eng.mf_stage_epoch(mf, net, lu, li, tri, B, 0.01, 1e-6)
+    torch.cuda.synchronize()
+    eng.close()
+    forms = [l.split("form=")[1].split()[0] for l in capfd.readouterr().err.splitlines() if "mf_stage_epoch: form=" in l]
+    assert forms == ["distinct-rows", "per-occurrence+fused-update"], forms
+
+
 
 def test_evaluation_with_its_table_sized_forward_queued_on_the_side_stream():
     """HipEngine.eval_submit_transferred (round 4): the ranks under the tables updata() WOULD write -- forward and rank pass

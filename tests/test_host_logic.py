@@ -885,7 +885,7 @@ def test_no_kernel_spills_or_uses_scratch_memory():
     fwd = {"k_transfer_fwd<%d, 1, %d, 1>" % (d, ns) for d in (32, 64, 128) for ns in (1, 2, 4)}
     fwd |= {"k_transfer_fwd<32, 2, 1, 2>", "k_transfer_fwd<64, 2, 1, 2>", "k_transfer_fwd<128, 2, 1, 1>"}
     assert family("k_transfer_fwd") == fwd, sorted(family("k_transfer_fwd") ^ fwd)
-    bwd = {"k_transfer_bwd<32, true>", "k_transfer_bwd<64, false>", "k_transfer_bwd<64, true>", "k_transfer_bwd<128, false>"}     # <D, PRE>
+    bwd = {"k_transfer_bwd<32, true>", "k_transfer_bwd<64, false>", "k_transfer_bwd<128, false>"}     # <D, PRE>
     assert family("k_transfer_bwd") == bwd, sorted(family("k_transfer_bwd") ^ bwd)
     full = {"k_transfer_bwd_full<%d, 1>" % d for d in (32, 64, 128)}
     assert family("k_transfer_bwd_full") == full, sorted(family("k_transfer_bwd_full") ^ full)
