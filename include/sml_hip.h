@@ -599,6 +599,42 @@ int sml_user_rank_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item,
                            const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items, int64_t n_pos,
                            const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
                            void* scratch, int32_t* above, int32_t* pos, void* stream);
+/* PER-USER CANDIDATE LISTS: "order these candidates for this user" -- the top k of a list of item ids given per user, without
+ * a walk of the catalogue.  Tables, elem_bytes (4: d = 32 / 64; 2: d = 32 / 64 / 128; any other pair is refused), Seen, allow
+ * and adj are exactly those of sml_topk_items_adjusted, except that here adj == NULL is accepted and means the bare score S (no
+ * fmaf is applied: the unadjusted scores' bits are returned), as allow == NULL means no filter.  1 <= k <= 128.  users int64
+ * [n]; a user may repeat.  cand holds int32 or int64 entries, cand_elem_bytes = 4 or 8.  The list of users[x] is
+ *   ragged form  cand[cand_off[x] .. cand_off[x + 1]), cand_off int64 [n + 1], non-decreasing, from 0;
+ *   dense form   (cand_off == NULL) cand[x * cand_stride + cand_first .. + cand_cols): rows [user, positive, negatives] of a
+ *                test file go in as they are with cand_stride = 2 + neg_num, cand_first = 1, cand_cols = 1 + neg_num.
+ * A list may be empty and may hold any id more than once, in any order.
+ * Padding rule: an entry c outside [0, n_item) is padding and is skipped -- negative ids are how a dense matrix carries short
+ * lists, and ids at or above n_item never touch memory (no address is formed from them).
+ * An entry c is ELIGIBLE when 0 <= c < n_item, c is not in Seen(u), c is allowed and A(u, c) is not NaN, where A is S (the
+ * fmaf chain above, fp16 entries widened exactly) or, with adj, one explicit fmaf(S, scale[c], offset[c]).
+ * items[x] / scores[x] (int32 / float [n, k]) hold the DISTINCT eligible ids of list x in the top-K order (A descending, then
+ * id ascending), at most k of them, then (-1, -inf).
+ * Repeat rule: a repeated id appears once (the same id always scores the same bits, so an entry equal in score and id to one
+ * already listed is dropped).
+ * n_elig[x] (int32 [n]; may be NULL) = the number of eligible entries of list x, repeats counted as they occur.
+ * Defining identity: row x equals, byte for byte in items and scores, row 0 of sml_topk_items_adjusted for the single user
+ * users[x] with the same Seen and adj and the filter (allow AND bitmap(list x)) -- with adj == NULL, of
+ * sml_topk_items_filtered[_f16].
+ * The bytes are the same for every launch geometry: max_workgroups = 0 leaves the grid to the call, a positive value caps it
+ * (lists are walked grid-stride, one wavefront per list).  No scratch, no allocation, no copy to the host, no synchronise.
+ * Refused (sml_last_error): exactly one of seen_off / seen_items NULL; a (d, elem_bytes) pair the kernels do not exist for;
+ * cand_elem_bytes other than 4 / 8; negative dense geometry; k out of range; max_workgroups < 0; a misaligned adj or table;
+ * an output that overlaps an input or another output as far as the pointers and the sizes known to the call show it.
+ * n == 0 is a valid call that launches nothing.  Indices (users, cand_off) are trusted.
+ * Known limit: one wavefront walks a whole list, however long; a single list of hundreds of thousands of candidates belongs
+ * to sml_topk_items_filtered with an item filter. */
+int sml_topk_candidates(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item,
+                        const int64_t* users, int64_t n,
+                        const void* cand, int cand_elem_bytes, const int64_t* cand_off,
+                        int64_t cand_stride, int64_t cand_first, int64_t cand_cols,
+                        int k, const int64_t* seen_off, const int32_t* seen_items,
+                        const uint32_t* allow, const float* adj, int max_workgroups,
+                        int32_t* items, float* scores, int32_t* n_elig, void* stream);
 /* Per-user metrics from pos (as sml_user_rank writes it; any value < 0 is never a hit) over the ranges of pos_off,
  * n < 2^31.  ks: HOST int32 [n_k], 1 <= n_k <= 8, every K >= 1.  For user x with m = |T(x)| and each K (outputs [n, n_k], row-major):
  *   hits = #{p : 0 <= pos(p) < K};  dcg = sum over hits of 1/log2(pos + 2), fp32, summed in ascending pos;

@@ -139,6 +139,9 @@ SIGNATURES = {
                                                c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "sml_user_rank_adjusted": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void,
                                               ctypes.c_int64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    "sml_topk_candidates": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, c_void, ctypes.c_int,
+                                           c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_void, c_void, c_void, c_void,
+                                           ctypes.c_int, c_void, c_void, c_void, c_void]),
     "sml_user_metrics": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,
                                         c_void]),
     "sml_stream_create_cu_range": (ctypes.c_int, [ctypes.POINTER(c_void), ctypes.c_int, ctypes.c_int, ctypes.c_int]),

@@ -1956,6 +1956,48 @@ int sml_user_rank_adjusted(sml_ctx* ctx, const void* w_user, const void* w_item,
                           pos_off, pos_items, n_pos, scratch, above, pos, stream);
 }
 
+static bool iset_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes);      // (defined with the interaction sets)
+
+// per-user candidate lists: allow and adj are both optional here (adj == NULL: the bare score, no fmaf)
+int sml_topk_candidates(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* users, int64_t n,
+                        const void* cand, int cand_elem_bytes, const int64_t* cand_off, int64_t cand_stride, int64_t cand_first,
+                        int64_t cand_cols, int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                        int max_workgroups, int32_t* items, float* scores, int32_t* n_elig, void* stream) {
+    const char* what = "sml_topk_candidates";
+    SmlCatalogue c = {0, elem_bytes, w_user, w_item, n_item, seen_off, seen_items, allow, adj};
+    if (!elem_ok(elem_bytes)) return fail(SML_EINVAL, what, "bad argument (elem_bytes must be 4 or 2)");
+    if (adj && ((uintptr_t)adj & 15)) return fail(SML_EINVAL, what, "adj must be 16-byte aligned");
+    if (cand_elem_bytes != 4 && cand_elem_bytes != 8) return fail(SML_EINVAL, what, "bad argument (cand_elem_bytes must be 4 or 8)");
+    if (!cand_off && (cand_stride < 0 || cand_first < 0 || cand_cols < 0))
+        return fail(SML_EINVAL, what, "bad argument (dense candidates: cand_stride, cand_first and cand_cols must not be negative)");
+    if (int rc = catalogue_ok(what, ctx, c, false, k >= 1 && k <= 128 && n >= 0 && max_workgroups >= 0,
+                              "bad argument (d must be 32/64, or 128 for fp16 tables; 1 <= k <= 128, 0 < n_item < 2^31, n >= 0, max_workgroups >= 0, seen_off and seen_items both or neither)"))
+        return rc;
+    if (n == 0) return SML_OK;
+    const bool empty = !cand_off && cand_cols == 0;              // dense lists of no columns: cand is never read
+    if (!w_user || !w_item || !users || (!cand && !empty) || !items || !scores) return fail(SML_EINVAL, what, "null argument");
+    if (((uintptr_t)w_user | (uintptr_t)w_item) & 15) return fail(SML_EINVAL, what, "the tables must be 16-byte aligned");
+    // the inputs' extents as far as the arguments give them: a ragged cand and the tables of unknown height count from their
+    // first byte only
+    const int64_t out_bytes = 4 * n * (int64_t)k;
+    const int64_t cand_bytes = cand_off ? cand_elem_bytes : ((n - 1) * cand_stride + cand_first + cand_cols) * cand_elem_bytes;
+    const int64_t n_pad = sml_item_adjust_pad(n_item);
+    const struct { const void* p; int64_t bytes; } in[] = {
+        {users, 8 * n}, {cand, cand_bytes}, {cand_off, 8 * (n + 1)}, {w_user, (int64_t)ctx->d * elem_bytes},
+        {w_item, n_item * ctx->d * elem_bytes}, {seen_off, 8}, {seen_items, 4}, {allow, n_pad / 8}, {adj, 8 * n_pad}};
+    const struct { const void* p; int64_t bytes; } out[] = {{items, out_bytes}, {scores, out_bytes}, {n_elig, 4 * n}};
+    for (const auto& o : out)
+        for (const auto& i : in)
+            if (iset_overlap(o.p, o.bytes, i.p, i.bytes)) return fail(SML_EINVAL, what, "an output overlaps an input");
+    if (iset_overlap(items, out_bytes, scores, out_bytes) || iset_overlap(items, out_bytes, n_elig, 4 * n) ||
+        iset_overlap(scores, out_bytes, n_elig, 4 * n))
+        return fail(SML_EINVAL, what, "the outputs overlap each other");
+    const SmlCandidates l = {cand, cand_elem_bytes, cand_off, cand_stride, cand_first, cand_cols};
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_topk_candidates(c, users, n, l, k, max_workgroups, items, scores, n_elig, st)));
+    return SML_OK;
+}
+
 int64_t sml_item_adjust_len(int64_t n_item) {
     if (n_item <= 0 || n_item >= ((int64_t)1 << 31)) return fail(SML_EINVAL, "sml_item_adjust_len", "bad argument (0 < n_item < 2^31)");
     return sml_item_adjust_pad(n_item);

@@ -72,6 +72,11 @@
 // The thresholds (k_full_rank's thr, k_ur_thresholds' key) are the same expression on score_chain.  A skipped
 // tile loads no adj; the last tile's loads end at n_pad, whose pad entries belong to items the eligibility word masks.
 // The adjusted kernels are instantiations of their own (A = true).  k_adjust_fill / k_adjust_cosine build the table.
+//
+// Per-user candidate lists (sml_topk_candidates): k_topk_cand<D, T> at the end of the file orders each user's OWN list of item
+// ids instead of walking the catalogue -- one wavefront per list, a lane per candidate, the row gathered whole and scored by
+// score_chain on the VALU, the K best in the wave's LDS.  It shares score_chain, better, adjusted, offset_plane and
+// lower_bound with the kernels above and changes none of them.
 #include <climits>
 #include <cmath>
 #include <type_traits>
@@ -864,6 +869,155 @@ __global__ __launch_bounds__(kUrBlock) void k_ur_metrics(const int32_t* __restri
     if (threadIdx.x == 0) first[x] = fmin == INT_MAX ? -1 : fmin;
 }
 
+// ---- per-user candidate lists (sml_topk_candidates) ------------------------------------------------------------------------
+
+constexpr int kCandWaves = 4;      // lists per workgroup: one wavefront each
+constexpr int kCandRounds = 2;     // rounds of 64 candidates whose rows a lane has in flight at once
+constexpr int kCandMaxK = 128;
+
+// one table row in a lane's registers, as its 16-byte loads bring it (fp16: packed, D/2 VGPRs); v is what score_chain reads
+template <int D, class T>
+struct FullRow {
+    alignas(16) T v[D];
+    __device__ __forceinline__ void load(const T* __restrict__ row) {
+        typedef f32x4 __attribute__((may_alias)) piece;      // 16 bytes of the row, whatever T is
+        constexpr int N = D * (int)sizeof(T) / 16;
+        const piece* p = reinterpret_cast<const piece*>(row);
+        piece* q = reinterpret_cast<piece*>(v);
+#pragma unroll
+        for (int c = 0; c < N; ++c) q[c] = p[c];
+    }
+    // the same row by a whole wave, one 16-byte piece per lane (an LDS copy of a wave-uniform row)
+    __device__ __forceinline__ void load_by_wave(const T* __restrict__ row, int lane) {
+        typedef f32x4 __attribute__((may_alias)) piece;
+        constexpr int N = D * (int)sizeof(T) / 16;
+        if (lane < N) reinterpret_cast<piece*>(v)[lane] = reinterpret_cast<const piece*>(row)[lane];
+    }
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int s = 0; s < D; ++s) v[s] = (T)0;
+    }
+};
+
+// The whole wave inserts the wave-uniform (s, i) into its sorted list ls / li (cnt live entries of k slots, `better` order);
+// lane l holds slots l and l + 64.  An entry equal to it in score and id is a repeat: nothing changes.  Otherwise its place
+// is the number of better entries (the list is sorted, so those are a prefix), every entry behind moves one slot down (the
+// one in slot k - 1 leaves) and lane 0 writes the new one.  Reads come before writes in program order and a wave's LDS
+// operations are served in order, so the two need no more than the compiler keeping that order.
+__device__ __forceinline__ void cand_insert(float* ls, int32_t* li, int k, int lane, int& cnt, float s, int i) {
+    const bool h0 = lane < cnt, h1 = lane + 64 < cnt;
+    const float s0 = h0 ? ls[lane] : 0.0f, s1 = h1 ? ls[lane + 64] : 0.0f;
+    const int i0 = h0 ? li[lane] : -1, i1 = h1 ? li[lane + 64] : -1;
+    if (__any((h0 && s0 == s && i0 == i) || (h1 && s1 == s && i1 == i))) return;
+    const bool b0 = h0 && better(s0, i0, s, i), b1 = h1 && better(s1, i1, s, i);
+    const int pos = __popcll(__ballot(b0)) + __popcll(__ballot(b1));
+    __builtin_amdgcn_wave_barrier();
+    if (h0 && !b0 && lane + 1 < k) { ls[lane + 1] = s0; li[lane + 1] = i0; }
+    if (h1 && !b1 && lane + 65 < k) { ls[lane + 65] = s1; li[lane + 65] = i1; }
+    if (lane == 0 && pos < k) { ls[pos] = s; li[pos] = i; }
+    __builtin_amdgcn_wave_barrier();
+    if (cnt < k) ++cnt;
+}
+
+// One wavefront per list, lists walked grid-stride; 64 candidates per round, kCandRounds rounds per step.  A lane reads its
+// entry, tests range, filter bit and Seen (a bisection of the user's ascending range) and, if the entry survives, gathers
+// the item's whole row with 16-byte loads -- the rows of all rounds of a step are requested before the first is scored.
+// The score is score_chain on the VALU against the user row, which is wave-uniform and loaded once per list; with adj one
+// explicit fmaf follows (adjusted<true>), without it none.  The K best live in the wave's LDS (cand_insert); a copy of the
+// K-th entry is the threshold, only lanes that beat it insert, in lane order, and the survivors are tested again whenever
+// the threshold moves.  allow, adj, Seen and the candidates' form and width are wave-uniform branches on the arguments.
+// A list of any length is walked by its one wave.
+template <int D, class T>
+__global__ __launch_bounds__(64 * kCandWaves) void k_topk_cand(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                                                const int64_t* __restrict__ users, int64_t n,
+                                                                const void* __restrict__ cand, int cand_wide,
+                                                                const int64_t* __restrict__ cand_off, int64_t cand_stride,
+                                                                int64_t cand_first, int64_t cand_cols, int k,
+                                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                                const uint32_t* __restrict__ allow, const float* __restrict__ adj,
+                                                                int32_t* __restrict__ items, float* __restrict__ scores,
+                                                                int32_t* __restrict__ n_elig) {
+    __shared__ float l_s[kCandWaves][kCandMaxK];
+    __shared__ int32_t l_i[kCandWaves][kCandMaxK];
+    __shared__ FullRow<D, T> l_u[kCandWaves];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    float* const ls = l_s[wave];
+    int32_t* const li = l_i[wave];
+    const float* const offset = adj ? offset_plane(adj, n_item) : nullptr;
+    const int64_t* const c64 = static_cast<const int64_t*>(cand);
+    const int32_t* const c32 = static_cast<const int32_t*>(cand);
+
+    for (int64_t x = (int64_t)blockIdx.x * kCandWaves + wave; x < n; x += (int64_t)gridDim.x * kCandWaves) {
+        const int64_t u = users[x];
+        const int64_t base = cand_off ? cand_off[x] : x * cand_stride + cand_first;
+        const int64_t len = cand_off ? cand_off[x + 1] - base : cand_cols;
+        l_u[wave].load_by_wave(wu + u * D, lane);
+        const int64_t s_lo = seen_off ? seen_off[u] : 0, s_hi = seen_off ? seen_off[u + 1] : 0;
+        int cnt = 0, ne = 0;
+        float thr_s = -INFINITY;              // the K-th entry once the list is full
+        int thr_i = INT_MAX;
+        for (int64_t b = 0; b < len; b += 64 * kCandRounds) {
+            FullRow<D, T> xr[kCandRounds];
+            int ci[kCandRounds];
+            bool ok[kCandRounds];
+            float sc[kCandRounds], of[kCandRounds];
+#pragma unroll
+            for (int r = 0; r < kCandRounds; ++r) {
+                const int64_t e = b + 64 * r + lane;
+                long long c = -1;
+                if (e < len) c = cand_wide ? (long long)c64[base + e] : (long long)c32[base + e];
+                bool good = c >= 0 && c < n_item;         // anything else is padding: no address is formed from it
+                if (good && allow) good = (allow[c >> 5] >> (c & 31)) & 1u;
+                if (good && s_lo < s_hi) {
+                    const int32_t cc = (int32_t)c;
+                    const int64_t at = lower_bound(s_lo, s_hi, [&](int64_t m) { return seen_items[m] < cc; });
+                    good = !(at < s_hi && seen_items[at] == cc);
+                }
+                xr[r].zero();
+                sc[r] = 1.0f;
+                of[r] = 0.0f;
+                if (good) {
+                    xr[r].load(wi + c * D);
+                    if (adj) { sc[r] = adj[c]; of[r] = offset[c]; }
+                }
+                ci[r] = good ? (int)c : -1;
+                ok[r] = good;
+            }
+            // the user row is read from LDS where a value feeds its fmaf (every lane the same address: a broadcast); held in
+            // registers over the loop it would cost D VGPRs (fp16: the widened copy), more than an item row
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int r = 0; r < kCandRounds; ++r) {
+                float s = score_chain<D, T>(l_u[wave].v, xr[r].v);
+                if (adj) s = adjusted<true>(s, &sc[r], &of[r], 0);
+                const bool elig = ok[r] && s == s;
+                ne += __popcll(__ballot(elig));
+                unsigned long long m = __ballot(elig && (cnt < k || better(s, ci[r], thr_s, thr_i)));
+                while (m) {
+                    const int l = __builtin_ctzll(m);
+                    cand_insert(ls, li, k, lane, cnt, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), l)),
+                                __builtin_amdgcn_readlane(ci[r], l));
+                    m &= m - 1;
+                    if (cnt == k) {
+                        thr_s = ls[k - 1];
+                        thr_i = li[k - 1];
+                        m &= __ballot(elig && better(s, ci[r], thr_s, thr_i));
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int q = lane; q < k; q += 64) {
+            const bool live = q < cnt;
+            items[x * k + q] = live ? li[q] : -1;
+            scores[x * k + q] = live ? ls[q] : -INFINITY;
+        }
+        if (n_elig && lane == 0) n_elig[x] = ne;
+        __builtin_amdgcn_wave_barrier();      // the next list's inserts come after these reads
+    }
+}
+
 }  // namespace
 
 bool sml_retrieval_supports(int d, int elem_bytes) {
@@ -960,6 +1114,21 @@ hipError_t sml_launch_user_metrics(const int32_t* pos, const int64_t* pos_off, i
     UrKs k = {};
     for (int q = 0; q < n_k; ++q) k.k[q] = ks[q];
     k_ur_metrics<<<dim3((unsigned)n), dim3(kUrBlock), 0, st>>>(pos, pos_off, k, n_k, hits, dcg, ap, first);
+    return hipGetLastError();
+}
+
+hipError_t sml_launch_topk_candidates(const SmlCatalogue& c, const int64_t* users, int64_t n, const SmlCandidates& l, int k,
+                                      int max_workgroups, int32_t* items, float* scores, int32_t* n_elig, hipStream_t st) {
+    int64_t blocks = (n + kCandWaves - 1) / kCandWaves;
+    if (blocks > 65536) blocks = 65536;                  // beyond this the lists are walked grid-stride
+    if (max_workgroups > 0 && blocks > max_workgroups) blocks = max_workgroups;
+    const dim3 grid((unsigned)blocks), block(64 * kCandWaves);
+    if (!with_width(c, [&](auto dd, auto, auto, auto* tu, auto* ti) {
+        k_topk_cand<dd(), elem_t<decltype(tu)>><<<grid, block, 0, st>>>(
+            tu, ti, c.n_item, users, n, l.cand, l.elem_bytes == 8, l.off, l.stride, l.first, l.cols, k, c.seen_off, c.seen_items, c.allow, c.adj,
+            items, scores, n_elig);
+    }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -430,6 +430,17 @@ hipError_t sml_launch_full_rank(const SmlCatalogue& c, const int64_t* rows, int6
 int64_t sml_topk_scratch_size(int64_t n, int k, int64_t n_item);
 hipError_t sml_launch_topk(const SmlCatalogue& c, const int64_t* users, int64_t n, int k, void* scratch, int32_t* items, float* scores,
                            hipStream_t st);
+// the per-user candidate lists of sml_topk_candidates (include/sml_hip.h): entries of elem_bytes 4 or 8; off != NULL: the
+// ragged form, else list x = cand[x * stride + first .. + cols)
+struct SmlCandidates {
+    const void* cand;
+    int elem_bytes;
+    const int64_t* off;
+    int64_t stride, first, cols;
+};
+// one wavefront per list, no scratch; max_workgroups > 0 caps the grid (lists are walked grid-stride)
+hipError_t sml_launch_topk_candidates(const SmlCatalogue& c, const int64_t* users, int64_t n, const SmlCandidates& l, int k,
+                                      int max_workgroups, int32_t* items, float* scores, int32_t* n_elig, hipStream_t st);
 int64_t sml_user_rank_scratch_size(int64_t n_pos);
 hipError_t sml_launch_user_rank(const SmlCatalogue& c, const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items,
                                 int64_t n_pos, void* scratch, int32_t* above, int32_t* pos, hipStream_t st);

@@ -930,6 +930,37 @@ class HipEngine(object):
                        _ptr(scratch), _ptr(items[c0:]), _ptr(scores[c0:]), self._stream()), name)
         return items.long(), scores
 
+    def topk_candidates(self, user_tab, item_tab, users, candidates, k, seen=None, allow=None, adjust=None, max_workgroups=0):
+        """(int64 items [n, k], float32 scores [n, k], int32 n_elig [n]): for each user the k best DISTINCT eligible ids of
+        that user's own candidate list -- in the list, inside [0, n_item), not in Seen(u), allowed, score not NaN -- score
+        descending then id ascending, missing slots (-1, -inf); n_elig counts the eligible entries, repeats included
+        (include/sml_hip.h, sml_topk_candidates: one wavefront per list, no catalogue walk, no scratch).  candidates: anything
+        sml_amd.retrieval.as_candidates takes; users may be None when the candidates carry their own (CandidateRows).  seen,
+        allow and adjust as in topk_items; row x equals topk_items for users[x] alone with the filter `allow AND list x`.
+        max_workgroups > 0 caps the grid (the bytes do not depend on it)."""
+        from .retrieval import as_candidates
+        wu, wi, _ = self._retrieval_tables(user_tab, item_tab)
+        allow = self._allow(allow, wi.shape[0])
+        adj = self._adjust(adjust, wi)
+        if users is not None:
+            users = self._dev(users, torch.int64).reshape(-1)
+        cl = as_candidates(candidates, None if users is None else users.shape[0], self.device)
+        if users is None:
+            if cl.users is None:
+                raise ValueError("users=None needs candidates that carry their users (a CandidateRows)")
+            users = self._dev(cl.users, torch.int64)
+        n, k = users.shape[0], int(k)
+        off, seen_items = self._seen(seen)
+        cand = cl.items if cl.items.numel() else torch.zeros(1, device=self.device, dtype=cl.items.dtype)   # (never a null pointer)
+        items = torch.empty(n, max(k, 0), device=self.device, dtype=torch.int32)
+        scores = torch.empty(n, max(k, 0), device=self.device, dtype=torch.float32)
+        n_elig = torch.empty(n, device=self.device, dtype=torch.int32)
+        check(self.lib.sml_topk_candidates(self._ctx, _ptr(wu), _ptr(wi), wi.element_size(), wi.shape[0], _ptr(users), n, _ptr(cand),
+                                           cand.element_size(), _ptr(cl.off), cl.stride, cl.first, cl.cols, k, _ptr(off),
+                                           _ptr(seen_items), _ptr(allow), _ptr(adj), int(max_workgroups), _ptr(items), _ptr(scores),
+                                           _ptr(n_elig), self._stream()), "sml_topk_candidates")
+        return items.long(), scores, n_elig
+
     USER_RANK_SCRATCH_BYTES = 256 << 20  # held-out items of one sml_user_rank call are capped so its scratch fits this
 
     def user_ranks(self, user_tab, item_tab, users, pos_off, pos_items, seen=None, ks=(20,), allow=None, adjust=None):

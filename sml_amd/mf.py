@@ -63,25 +63,48 @@ class MFbasemode(nn.Module):
 
     def test2(self, inputs_data, topK=20):
         """model/MF.py:82-106: (hit rows, rank, hits, ndcg_sum); `rank` here is the
-        positive's rank per row (the reference returns the top-k index matrix)."""
+        positive's rank per row (the reference returns the top-k index matrix: test_lists
+        returns those lists)."""
         eng, ranks = self._ranks(inputs_data)
         hits, ndcg = eng.eval_metrics(ranks, topK)
         hit_rows = (ranks < topK).nonzero()[:, 0]
         return hit_rows, ranks, hits * 1.0, (torch.tensor(ndcg) if hits > 0 else 0)
 
-    def recommend(self, users, topK=20, exclude=None, items=None, score=None):
+    def recommend(self, users, topK=20, exclude=None, items=None, score=None, candidates=None):
         """(items int64 [n, topK], scores float32 [n, topK]): each user's topK items over the whole catalogue by the score
         test() uses (no bias terms), score descending then item id ascending, leaving out `exclude` (a
         sml_amd.retrieval.SeenItems or a (seen_off, seen_items) CSR); missing slots are (-1, -inf).  items: restrict the
         lists to a subset of the catalogue (a sml_amd.retrieval.ItemFilter, a bool mask [item_num] or int32 filter words).
         score: rank by A(u, i) = fmaf(S(u, i), scale[i], offset[i]) instead (sml_amd.retrieval.as_score): "bias" adds
         item_bais, "cosine" divides by the item row's norm, an ItemScore gives any per-item terms; None / "dot" is the bare
-        dot product.  The returned scores are A."""
+        dot product.  The returned scores are A.  candidates: the same call restricted PER USER -- each user's own list of
+        item ids (anything sml_amd.retrieval.as_candidates takes: a matrix [n, C] padded with -1, a (cand_off, cand_items)
+        pair, a list of sequences, a CandidateRows); the lists hold the distinct eligible candidates only, and no catalogue
+        walk is made (HipEngine.topk_candidates).  users may be None when candidates is a CandidateRows."""
         from .retrieval import as_csr, as_filter, as_score
         eng = _engine_for(self)
         w = self.user_laten.weight
+        if candidates is not None:
+            it, sc, _ = eng.topk_candidates(w.data, self.item_laten.weight.data, users, candidates, topK, as_csr(exclude, w.device),
+                                            as_filter(items, self.item_laten.weight.shape[0], w.device), as_score(score, self))
+            return it, sc
         return eng.topk_items(w.data, self.item_laten.weight.data, users, topK, as_csr(exclude, w.device),
                               as_filter(items, self.item_laten.weight.shape[0], w.device), as_score(score, self))
+
+    def test_lists(self, inputs_data, topK=20, exclude=None, score=None):
+        """inputs_data [n, 2 + neg] as test() takes it (user, positive, negatives; an array, a tensor or a DeviceRows) ->
+        (items int64 [n, topK], scores float32 [n, topK]): the top-K matrix of each row's 1 + neg candidates, as item ids
+        -- what the reference's test2 returns as indices (model/MF.py:82-106).  The order is the retrieval family's, not
+        torch.topk's: the score is the fmaf chain of include/sml_hip.h (score_chain; with score=, the adjusted score of
+        recommend), descending, ties broken by the smaller item id; an id a row repeats is listed once, (-1, -inf) fills a
+        short list.  It is not claimed equal to eval_ranks' arithmetic, which sums the same products in another order.
+        The rows are read where they lie (sml_amd.retrieval.CandidateRows): no copy of the candidate matrix is made."""
+        from .retrieval import CandidateRows
+        if not isinstance(inputs_data, CandidateRows):
+            if not hasattr(inputs_data, "wait_ready"):                       # (a DeviceRows goes in as it is)
+                inputs_data = torch.as_tensor(inputs_data).long()            # (int64 already: the same tensor)
+            inputs_data = CandidateRows(inputs_data, 1)
+        return self.recommend(None, topK, exclude=exclude, score=score, candidates=inputs_data)
 
     def similar_items(self, items, topK=20, metric="cosine", among=None, exclude_self=True):
         """(int64 [n, topK], float32 [n, topK]): for each query item its topK most similar items of the catalogue, the item

@@ -22,6 +22,10 @@ the bare dot product S (include/sml_hip.h, the sml_*_adjusted entry points) -- a
 On the device the terms are one padded table,
 
     adj  float32 [2, n_pad], n_pad = 32 * ceil(n_item / 32): plane 0 scale, plane 1 offset (pad entries are ignored)
+
+Candidates / CandidateRows / as_candidates describe per-user candidate lists, the allow list of one user each that
+sml_topk_candidates orders (HipEngine.topk_candidates, MFbasemode.recommend(candidates=), MFbasemode.test_lists): a ragged
+(cand_off, cand_items) pair or a dense matrix read in place, e.g. the rows [user, positive, negatives] of a test set.
 """
 import os
 
@@ -399,6 +403,132 @@ def as_score(x, model):
             return eng.item_adjust_cosine(model.item_laten.weight.data)
         return eng.item_adjust(model.item_laten.weight.shape[0], offset=model.item_bais.weight.data[:, 0].float())
     raise ValueError('score= is None, "dot", "cosine", "bias", an ItemScore or a float32 [2, n_pad] table, got %r' % (x,))
+
+
+class CandidateRows(object):
+    """Rows of a test set -- [user, positive, negatives ...], an int64 array / tensor [n, 2 + neg] or a
+    sml_amd.evaluation.DeviceRows -- as per-user candidate lists: row x's list is rows[x, first_col:], its user rows[x, 0].
+    The rows are read where they are (sml_topk_candidates' dense form): no copy, no int32 conversion."""
+
+    def __init__(self, rows, first_col=1):
+        if hasattr(rows, "wait_ready") and hasattr(rows, "rows"):          # a DeviceRows: order behind its upload
+            rows.wait_ready()
+            rows = rows.rows
+        if isinstance(rows, np.ndarray):
+            rows = torch.from_numpy(np.ascontiguousarray(rows))
+        rows = torch.as_tensor(rows)
+        if rows.dim() != 2 or rows.dtype != torch.int64:
+            raise ValueError("expected int64 rows [n, 2 + neg], got %s %s" % (rows.dtype, tuple(rows.shape)))
+        self.first_col = int(first_col)
+        if not 0 <= self.first_col <= rows.shape[1] or rows.shape[1] < 1:
+            raise ValueError("first_col %d is outside the %d columns of the rows" % (self.first_col, rows.shape[1]))
+        self.rows = rows
+
+    @property
+    def users(self):
+        return self.rows[:, 0]
+
+    @property
+    def geometry(self):
+        """(stride, first, cols) of the dense form."""
+        return self.rows.shape[1], self.first_col, self.rows.shape[1] - self.first_col
+
+
+class Candidates(object):
+    """Per-user candidate lists as sml_topk_candidates takes them (as_candidates makes one).  items: the int32 / int64 entries
+    on the device, contiguous.  Ragged form: off int64 [n + 1], list x = items[off[x] : off[x + 1]].  Dense form (off None):
+    list x = items.reshape(-1)[x * stride + first : ... + cols].  users: the rows' own users (CandidateRows) or None."""
+
+    def __init__(self, n, items, off=None, stride=0, first=0, cols=0, users=None):
+        self.n, self.items, self.off, self.users = int(n), items, off, users
+        self.stride, self.first, self.cols = int(stride), int(first), int(cols)
+
+    def lists(self):
+        """The n lists as host int64 arrays (tests, small inputs)."""
+        flat = self.items.reshape(-1).cpu().numpy().astype(np.int64)
+        if self.off is None:
+            return [flat[x * self.stride + self.first:x * self.stride + self.first + self.cols] for x in range(self.n)]
+        off = self.off.cpu().numpy()
+        return [flat[off[x]:off[x + 1]] for x in range(self.n)]
+
+
+def _cand_items(x, device):
+    """An int array / tensor as contiguous int32 or int64 entries on `device`; a tensor already there is not copied."""
+    if not torch.is_tensor(x):
+        x = np.asarray(x)
+        if x.dtype.kind not in "iu":
+            raise ValueError("candidate ids must be integers, got %s" % x.dtype)
+        if x.dtype not in (np.int32, np.int64):
+            x = x.astype(np.int64)
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if x.dtype not in (torch.int32, torch.int64):
+        if x.dtype.is_floating_point or x.dtype == torch.bool or x.dtype.is_complex:
+            raise ValueError("candidate ids must be integers, got %s" % x.dtype)
+        x = x.long()
+    x = x.to(device)
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def as_candidates(x, n, device):
+    """Per-user candidate lists in any accepted form -> a Candidates on `device`.  x is one of
+
+      a 2-D int32 / int64 array or tensor [n, C]    row x is the list of user x (entries outside [0, n_item), e.g. -1, pad);
+      a tuple (cand_off, cand_items)                the ragged form: int64 offsets [n + 1] and the int32 / int64 entries;
+      a list of n int sequences                     built into the ragged form (int32 entries when every id fits);
+      a CandidateRows, or a DeviceRows (wrapped as CandidateRows(x, first_col=1)), which also supply the users.
+
+    n: the number of users the lists are for, or None to take it from x.  A tensor already on the device is not copied.
+    Offsets that come from the host are checked there: length n + 1, from 0, non-decreasing, last at most len(cand_items);
+    offsets already on the device are checked for their length only.  Ids are not range-checked: the kernel skips the
+    out-of-range ones."""
+    device = torch.device(device)
+    if isinstance(x, Candidates):
+        got = x
+    elif hasattr(x, "wait_ready") and hasattr(x, "rows") or isinstance(x, CandidateRows):
+        r = x if isinstance(x, CandidateRows) else CandidateRows(x, 1)
+        rows = r.rows.to(device)
+        rows = rows if rows.is_contiguous() else rows.contiguous()
+        stride, first, cols = r.geometry
+        got = Candidates(rows.shape[0], rows, None, stride, first, cols, users=rows[:, 0])
+    elif isinstance(x, tuple):
+        if len(x) != 2:
+            raise ValueError("a ragged candidate set is a (cand_off, cand_items) pair, got a tuple of %d" % len(x))
+        off, items = x
+        items = _cand_items(items, device)
+        if items.dim() != 1:
+            raise ValueError("cand_items must be 1-D, got shape %s" % (tuple(items.shape),))
+        on_host = not (torch.is_tensor(off) and off.device.type != "cpu")
+        if on_host:
+            h = np.asarray(off.numpy() if torch.is_tensor(off) else off)
+            if h.dtype.kind not in "iu" or h.ndim != 1 or h.shape[0] < 1:
+                raise ValueError("cand_off must be a 1-D int array [n + 1], got %s %s" % (h.dtype, h.shape))
+            h = h.astype(np.int64)
+            if h[0] != 0 or (np.diff(h) < 0).any() or h[-1] > items.shape[0]:
+                raise ValueError("cand_off must start at 0, never decrease and end at most at len(cand_items) = %d" % items.shape[0])
+            off = torch.from_numpy(h)
+        elif off.dtype != torch.int64 or off.dim() != 1 or off.shape[0] < 1:
+            raise ValueError("cand_off must be int64 [n + 1], got %s %s" % (off.dtype, tuple(off.shape)))
+        off = off.to(device)
+        got = Candidates(off.shape[0] - 1, items, off if off.is_contiguous() else off.contiguous())
+    elif isinstance(x, list):
+        parts = [np.asarray(s).reshape(-1) for s in x]
+        for p in parts:
+            if p.size and p.dtype.kind not in "iu":
+                raise ValueError("candidate ids must be integers, got %s" % p.dtype)
+        off = np.zeros(len(parts) + 1, np.int64)
+        np.cumsum([p.size for p in parts], out=off[1:])
+        flat = np.concatenate([p.astype(np.int64) for p in parts]) if parts else np.zeros(0, np.int64)
+        if flat.size == 0 or (flat.min() >= -2 ** 31 and flat.max() < 2 ** 31):
+            flat = flat.astype(np.int32)
+        got = Candidates(len(parts), torch.from_numpy(flat).to(device), torch.from_numpy(off).to(device))
+    else:
+        items = _cand_items(x, device)
+        if items.dim() != 2:
+            raise ValueError("dense candidates are a 2-D array [n, C], got shape %s" % (tuple(items.shape),))
+        got = Candidates(items.shape[0], items, None, items.shape[1], 0, items.shape[1])
+    if n is not None and got.n != int(n):
+        raise ValueError("the candidates hold %d lists, the call has %d users" % (got.n, int(n)))
+    return got
 
 
 _SELF_SEEN = {}
