@@ -668,7 +668,7 @@ int sml_prof_get(sml_ctx* ctx, int cls, int64_t* count, double* total_ms);
  * the reference's loop, NOT its numpy random stream: the driver uses it only when asked
  * (--device_batches); the stream-exact host path (sml_host_resolve_negatives_csr) is the default.
  * Counter-based generator keyed by (seed, e): reproducible for a given seed.  *failed (device int32) counts
- * elements left at -1 after 4096 rejected draws. */
+ * elements whose 4096 draws were all rejected; such an element still gets a valid item, its last candidate. */
 int sml_sample_negatives(sml_ctx* ctx, const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop,
                          const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, uint64_t seed,
                          int64_t* negs, int32_t* failed, void* stream);
@@ -771,6 +771,46 @@ int sml_neg_sets(sml_ctx* ctx, const int64_t* rows, int64_t n, int n_cols, int64
                  const int64_t* h_off, int64_t n_user, const int32_t* h_items, const int32_t* h_since, int neg_num, uint64_t seed,
                  int max_workgroups, int64_t* out, int32_t* failed, void* stream);
 
+/* ---- training negatives ---------------------------------------------------------------- */
+/* One training negative per element, drawn uniformly or by popularity and, with a pool, the hardest of M: the sampler of
+ * the device batch supply beyond sml_sample_negatives.  The kernel (sml_sample_negatives_ex), the host walk
+ * (sml_host_sample_negatives_ex) and the tests' restatement all implement this definition.
+ *
+ * Inputs.  For element e of [0, n) with user u = users[e]: item_all[0..pop); the CSR user_ptr [n_users + 1] / user_items
+ *   (ascending per user); an optional cdf; pool = M, 1 <= M <= 64; seed; for M > 1, fp32 tables w_user, w_item of width
+ *   d = 32 or 64 (fp16 tables are out of scope).
+ * Draws.  s0 = neg_stream(seed, e) = seed ^ (e * 0xd1342543de82ef95 + 0x632be59bd9b4e019); output number c = 0, 1, 2, ... is
+ *   z_c = splitmix64_mix(s0 + (c + 1) * 0x9e3779b97f4a7c15) -- the c-th splitmix64() call from state s0, the stream
+ *   sml_sample_negatives consumes, addressed by c.
+ * Candidate c.  cdf == NULL: cand_c = item_all[umulhi64(z_c, pop)], sml_sample_negatives' expression.  cdf given: cdf is
+ *   float64 [pop], nondecreasing, cdf[pop - 1] == 1.0; u_c = (z_c >> 11) * 2^-53; idx_c = the first index with
+ *   cdf[idx] > u_c (bisect right); cand_c = item_all[idx_c].  Entries of zero mass are never drawn.
+ * Admissible.  cand_c is admissible when it is not in u's CSR range, tested by bisection.  A user outside [0, n_users) has
+ *   an empty range.
+ * Pool.  The first M admissible candidates in order of c, restricted to c < 4096.  The pool may hold the same item twice.
+ * Choice.  M == 1: the first admissible candidate; no table is read, the table pointers may be NULL.  M > 1: the pool
+ *   member with the greatest S = the fp32 fmaf chain of the retrieval section over (w_user[u], w_item[cand]): acc = 0, then
+ *   for s = 0 .. d/2 - 1: acc = fmaf(x[s], u[s], acc); acc = fmaf(x[s + d/2], u[s + d/2], acc).  A NaN score loses to every
+ *   non-NaN score; among equal scores, or among all-NaN scores, the smaller c wins.  Fewer than M admissible candidates
+ *   below the cap: the choice is among those found; this is not a failure.  No admissible candidate below the cap:
+ *   *failed += 1 and the result is cand_4095, a valid item, which is what sml_sample_negatives returns.
+ * Outputs.  negs int64 [n]; score float32 [n] (optional, may be NULL), S(u, negs[e]), written for M > 1 only; failed
+ *   int32 [1], zeroed by the call.
+ * Identity.  The bytes do not depend on launch geometry: elements are walked grid-stride, max_workgroups = 0 leaves the
+ *   grid to the call, any grid gives the same bytes.  With cdf == NULL and M == 1, negs and failed equal
+ *   sml_sample_negatives' output for the same arguments, byte for byte (with max_workgroups = 0 that case launches
+ *   sml_sample_negatives' own kernel: the new one-lane kernel measured 1.3 - 3.8 % slower).
+ * Properties.  The pool for M is a prefix of the pool for M' > M, so the chosen score never decreases as M grows; for
+ *   M = 1 it is the score of sml_sample_negatives' negative.
+ * Refused (SML_EINVAL): pool outside 1..64; pool > 1 with a NULL table, with d not 32 or 64, or with a table that is not
+ *   16-byte aligned; a NULL users, item_all, user_ptr, user_items, negs or failed; pop <= 0; n, n_users or max_workgroups
+ *   < 0.  Indices are trusted on the device (HipEngine.sample_negatives_ex range-checks users and item_all against the
+ *   tables).  No allocation, no copy to the host, no synchronise.  All pointers are device memory.  Asynchronous. */
+int sml_sample_negatives_ex(sml_ctx* ctx, const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop,
+                            const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, const double* cdf, int pool,
+                            const float* w_user, const float* w_item, int d, uint64_t seed, int max_workgroups, int64_t* negs,
+                            float* score, int32_t* failed, void* stream);
+
 /* ---- host helper: batch supply ------------------------------------------------------- */
 /* Sequential rejection sampling of offlineDataset_withsample.__getitem__ (reference
  * data/dataset.py:63-71) over a pre-drawn candidate stream, on the HOST (no GPU involved):
@@ -802,6 +842,13 @@ int sml_host_resolve_negatives_csr(const int64_t* users, int64_t n, const int64_
 int sml_host_neg_sets(const int64_t* rows, int64_t n, int n_cols, int64_t g0, const int32_t* n_cat, const int32_t* order,
                       const int64_t* h_off, int64_t n_user, const int32_t* h_items, const int32_t* h_since, int neg_num, uint64_t seed,
                       int64_t* out, int32_t* failed);
+
+/* sml_sample_negatives_ex (training negatives) over HOST memory: a single-threaded walk of the same definition, one
+ * candidate at a time, drawing through the same functions as the kernels -- the same bytes in negs and score and the same
+ * count in *failed (host int32).  The route of a machine without a GPU. */
+int sml_host_sample_negatives_ex(const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop, const int64_t* user_ptr,
+                                 int64_t n_users, const int64_t* user_items, const double* cdf, int pool, const float* w_user,
+                                 const float* w_item, int d, uint64_t seed, int64_t* negs, float* score, int32_t* failed);
 
 /* ---- self test ------------------------------------------------------------------ */
 /* Checks the MFMA operand/accumulator lane maps this library assumes against a

@@ -204,6 +204,11 @@ SIGNATURES = {
                                     c_void, c_void, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, c_void, c_void, c_void]),
     "sml_host_neg_sets": (ctypes.c_int, [c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void, ctypes.c_int64,
                                          c_void, c_void, ctypes.c_int, ctypes.c_uint64, c_void, c_void]),
+    "sml_sample_negatives_ex": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void,
+                                               ctypes.c_int, c_void, c_void, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, c_void, c_void,
+                                               c_void, c_void]),
+    "sml_host_sample_negatives_ex": (ctypes.c_int, [c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void,
+                                                    ctypes.c_int, c_void, c_void, ctypes.c_int, ctypes.c_uint64, c_void, c_void, c_void]),
     "sml_selftest": (ctypes.c_int, [ctypes.c_int]),
 }
 

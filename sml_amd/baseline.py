@@ -20,6 +20,12 @@ lines so its recorded runs (fixtures G10 and G16) replay against them:
 - `SPMF.run_one_stage2` (model/baseline.py:306-386), the fine-tune / full-retrain inner loop (G10).
 - `base_train_not_train`, `run` with its summary lines, and `main()` (model/baseline.py:149-160, 505-671): the
   `--method full|fine|spmf` program, plus `--device_batches` and `--pre_model ''` (no checkpoint: fresh tables).
+- `--device_batches 1` with `full` / `fine`: every epoch is offlineDataset_withsample.epoch_triples_device, keyed by
+  (stage, epoch) with the seed expression of SPMF's device mode; no numpy or torch draw is made for the batches.
+- `--neg_pool M`, `--neg_pop_alpha A` (extensions, device batches only; anything else raises ValueError): the negatives
+  of an epoch come from sml_amd.sampling.NegativeSampler(M, A) -- popularity-weighted candidates, the highest-scoring
+  of the first M admissible ones -- through HipEngine.sample_negatives_ex.  The pool is scored by the tables as they
+  are when the epoch starts.  With the defaults every printed line and trained byte is what it is without the flags.
 - `--full_eval 1` (an extension): after the final test line of a stage, `SPMF.full_test` ranks every test user's held-out
   set against the whole catalogue minus the training history (a retrieval.DeviceSeen grown by one period per stage) and
   one `full-catalogue test---` line is printed.  No RNG draw: the training trajectory is the one without the flag.
@@ -43,6 +49,7 @@ from . import datasets as D
 from .datasets import offlineDataset_withsample
 from .engine import get_engine
 from .mf import MFbasemode
+from .sampling import NegativeSampler
 
 
 class Reservious(object):
@@ -145,6 +152,10 @@ class SPMF(object):
         self.item_num = int(item_num)
         self.user_num = int(user_num)
         self.device_batches = int(getattr(args, "device_batches", 0) or 0)
+        self.sampler = NegativeSampler(getattr(args, "neg_pool", 1), getattr(args, "neg_pop_alpha", 0.0))
+        if not self.sampler.is_default and not self.device_batches:
+            raise ValueError("--neg_pool / --neg_pop_alpha select a sampler of the device batch supply: they need --device_batches 1 "
+                             "(the host route draws the reference's numpy stream)")
         self.run_stage = 0
         self._order = None                          # device rank order of the stage's rows (device_batches)
         self.engine = engine if engine is not None else get_engine(self.device, laten_dim, max(int(args.batch_size), 4096))
@@ -155,10 +166,26 @@ class SPMF(object):
     def get_next_data(self, stage_id, types="only_new"):
         return self.dataset.get_next(stage_id, types=types)
 
-    def _epoch(self, train):
+    def _sampler_or_none(self):
+        return None if self.sampler.is_default else self.sampler
+
+    def _epoch(self, train, stage_id=0, epoch=0):
         """One shuffled pass: batches drawn with the reference's random-number consumption, trained in ONE engine
-        call; returns the mean batch loss accumulated in fp32 as `loss_all += loss.data` does."""
-        tri = train.epoch_triples(D.loader_order(len(train), shuffle=True))
+        call; returns the mean batch loss accumulated in fp32 as `loss_all += loss.data` does.
+
+        `--device_batches 1`: the pass is built on the device instead (offlineDataset_withsample.epoch_triples_device, keyed
+        by (stage_id, epoch) as SPMF's device mode keys its epochs): the same distribution, not the same stream, and no
+        numpy or torch draw is made.  The negatives come from this run's NegativeSampler (--neg_pool, --neg_pop_alpha).
+        Its pool is scored by the tables as they are at the epoch's start -- the previous epoch's mf_flush has made them
+        current -- not by the tables as the epoch's own batches move them."""
+        if self.device_batches:
+            seed = (2002 * 1000003 + stage_id) * 1000003 + epoch
+            tri = train.epoch_triples_device(self.engine, seed, sampler=self._sampler_or_none(), model=self.MFbase)
+            failed = getattr(train, "_last_failed", None)
+            if failed is not None and int(failed[0]):
+                raise RuntimeError("negative sampling does not terminate: a user owns (almost) every item")
+        else:
+            tri = train.epoch_triples(D.loader_order(len(train), shuffle=True))
         self.MFbase.train()
         losses = self.engine.bare_adam_epoch(self.MFbase, tri, self.batch_size, self.lr, self.lambda_u, self.lambda_i, bce=True)
         self.engine.mf_flush(self.MFbase)          # dense-Adam state of every row is current again
@@ -183,7 +210,7 @@ class SPMF(object):
         stale = 0
         for epoch in range(self.epochs):
             t0 = time.time()
-            loss = self._epoch(train)
+            loss = self._epoch(train, stage_id, epoch)
             print("epoch: {} ,time:{:.1f}, loss:{:.4f}".format(epoch, time.time() - t0, loss))
             stale += 1
             if epoch % 5:
@@ -308,11 +335,24 @@ class SPMF(object):
                 t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
                 ptr, items = self._csr
                 self._dev_supply = (t(train_data), t(self._items), t(ptr), t(items))
+                self._dev_extra = {}                    # the stage's popularity cdf, built on first use
             rows, item_all, ptr, items = self._dev_supply
             seed = (2002 * 1000003 + stage_id) * 1000003 + epoch
             tri, failed = self.engine.weighted_epoch(rows, self._order, item_all, ptr, items, itr * B, seed)
             if int(failed[0]):
                 raise RuntimeError("negative sampling does not terminate: a user owns (almost) every item")
+            if not self.sampler.is_default:
+                # another sampler: column 2 is redrawn for the users of column 0 (the pool scored by the epoch-start tables)
+                if "cdf" not in self._dev_extra:
+                    from . import sampling
+                    cdf = self.sampler.cdf(self._items, train_data[:, 1])
+                    self._dev_extra["cdf"] = None if cdf is None else sampling.device_cdf(cdf, self.engine.device)
+                w_user, w_item = self.sampler.tables(self.MFbase)
+                negs, failed = self.engine.sample_negatives_ex(tri[:, 0].contiguous(), item_all, ptr, items, seed + 1, pool=self.sampler.pool,
+                                                               cdf=self._dev_extra["cdf"], w_user=w_user, w_item=w_item)
+                if int(failed[0]):
+                    raise RuntimeError("negative sampling does not terminate: a user owns (almost) every item")
+                tri[:, 2] = negs
         else:
             tri = np.empty((itr * B, 3), dtype=np.int64)
             for b in range(itr):
@@ -443,7 +483,11 @@ def get_parse():
                         help="pretrained MFbase state dict; '' starts from fresh tables")
     parser.add_argument('--start_idx', type=int, default=30, help='retraining from which period: yelp 30, news(adressa) 48')
     # extension (not a reference flag): SPMF batches drawn on the device -- the same distribution, not the same numpy stream
-    parser.add_argument('--device_batches', type=int, default=0, help='1: draw the SPMF epochs on the device (not stream-exact)')
+    parser.add_argument('--device_batches', type=int, default=0, help='1: draw the epochs of every method on the device (not stream-exact)')
+    parser.add_argument('--neg_pool', type=int, default=1,
+                        help='with --device_batches 1: train on the highest-scoring of the first M admissible negatives (1..64)')
+    parser.add_argument('--neg_pop_alpha', type=float, default=0.0,
+                        help='with --device_batches 1: draw negatives with p(i) ~ count(i)^alpha over the training rows (0: uniform)')
     parser.add_argument('--full_eval', type=int, default=0,
                         help='1: after each stage also print the all-ranking metrics over the whole catalogue minus the history')
     return parser

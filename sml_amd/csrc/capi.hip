@@ -2451,6 +2451,54 @@ int sml_host_neg_sets(const int64_t* rows, int64_t n, int n_cols, int64_t g0, co
     return SML_OK;
 }
 
+// ---- training negatives (neg_sampler.hip) ----
+static const char* neg_sampler_refusal(const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop, const int64_t* user_ptr,
+                                       int64_t n_users, const int64_t* user_items, int pool, const float* w_user, const float* w_item, int d,
+                                       int max_workgroups, const int64_t* negs, const int32_t* failed) {
+    if (n < 0 || pop <= 0 || n_users < 0 || max_workgroups < 0) return "bad argument (n >= 0, pop > 0, n_users >= 0, max_workgroups >= 0)";
+    if (pool < 1 || pool > 64) return "bad argument (1 <= pool <= 64)";
+    if (!users || !item_all || !user_ptr || !user_items || !negs || !failed) return "null argument";
+    if (pool > 1) {
+        if (!w_user || !w_item) return "null argument (pool > 1 scores the candidates: w_user and w_item are needed)";
+        if (d != 32 && d != 64) return "bad argument (pool > 1: d must be 32 or 64, fp32 tables)";
+        if ((((uintptr_t)w_user) | ((uintptr_t)w_item)) & 15) return "bad argument (the tables must be 16-byte aligned)";
+    }
+    return nullptr;
+}
+
+int sml_sample_negatives_ex(sml_ctx* ctx, const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop, const int64_t* user_ptr,
+                            int64_t n_users, const int64_t* user_items, const double* cdf, int pool, const float* w_user,
+                            const float* w_item, int d, uint64_t seed, int max_workgroups, int64_t* negs, float* score, int32_t* failed,
+                            void* stream) {
+    if (!ctx) return fail(SML_EINVAL, "sml_sample_negatives_ex", "null context");
+    if (const char* why = neg_sampler_refusal(users, n, item_all, pop, user_ptr, n_users, user_items, pool, w_user, w_item, d, max_workgroups,
+                                              negs, failed))
+        return fail(SML_EINVAL, "sml_sample_negatives_ex", why);
+    DevGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(failed, 0, sizeof(int32_t), st));
+    if (n == 0) return SML_OK;
+    if (pool == 1 && !cdf && max_workgroups == 0) {
+        // the uniform sampler with the grid left to the call: sml_sample_negatives' own kernel, the same bytes -- k_neg_one measured
+        // 1.3 % (n = 100,000) and 3.8 % (n = 3,000,000) slower, outside the old kernel's run-to-run spread (profiles/r18_neg_sampler_probe.json)
+        PROFILED(PC_MISC, HIPCHK(sml_launch_sample_negatives(users, n, item_all, pop, user_ptr, n_users, user_items, seed, negs, failed, st)));
+        return SML_OK;
+    }
+    PROFILED(PC_MISC, HIPCHK(sml_launch_neg_sampler(users, n, item_all, pop, user_ptr, n_users, user_items, cdf, pool, w_user, w_item, d, seed,
+                                                    max_workgroups, negs, pool > 1 ? score : nullptr, failed, st)));
+    return SML_OK;
+}
+
+int sml_host_sample_negatives_ex(const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop, const int64_t* user_ptr,
+                                 int64_t n_users, const int64_t* user_items, const double* cdf, int pool, const float* w_user,
+                                 const float* w_item, int d, uint64_t seed, int64_t* negs, float* score, int32_t* failed) {
+    if (const char* why = neg_sampler_refusal(users, n, item_all, pop, user_ptr, n_users, user_items, pool, w_user, w_item, d, 0, negs, failed))
+        return fail(SML_EINVAL, "sml_host_sample_negatives_ex", why);
+    *failed = (int32_t)sml_neg_sampler_host_walk(users, n, item_all, pop, user_ptr, n_users, user_items, cdf, pool, w_user, w_item, d, seed,
+                                                 negs, score);
+    return SML_OK;
+}
+
 int sml_host_resolve_negatives_csr(const int64_t* users, int64_t n, const int64_t* cand, int64_t m,
                                    const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t* negs,
                                    int64_t* consumed, int64_t* resolved) {

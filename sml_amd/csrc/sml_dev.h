@@ -74,6 +74,32 @@ __device__ __forceinline__ int64_t draw_negative(uint64_t& st, int64_t u, const 
     atomicAdd(failed, 1);
     return cand;
 }
+// Training negatives with a pool (neg_sampler.hip, include/sml_hip.h "training negatives"): the stream draw_negative walks,
+// addressed by the draw's number c = 0, 1, 2, ... -- neg_draw(s0, c) is the (c + 1)-th splitmix64() from state s0 -- and the
+// two tests every candidate takes.  The kernels and sml_host_sample_negatives_ex all draw through these.
+#define SML_NEG_DRAW_CAP 4096           // candidates an element may look at (draw_negative's 4096 tries)
+__host__ __device__ __forceinline__ uint64_t neg_draw(uint64_t s0, uint64_t c) { return splitmix64_mix(s0 + (c + 1) * SML_SPLITMIX_GAMMA); }
+// position in item_all of the candidate drawn as z: uniform, floor(z * pop / 2^64); or by the float64 cdf [pop] (nondecreasing,
+// cdf[pop - 1] == 1.0), the first position whose cdf exceeds u = (z >> 11) * 2^-53 -- a position of zero mass is never that
+__host__ __device__ __forceinline__ int64_t neg_candidate_pos(uint64_t z, int64_t pop, const double* __restrict__ cdf) {
+    if (cdf == nullptr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return (int64_t)__umul64hi(z, (uint64_t)pop);
+#else
+        return (int64_t)(((unsigned __int128)z * (uint64_t)pop) >> 64);
+#endif
+    }
+    const double u = (double)(z >> 11) * 0x1.0p-53;
+    int64_t lo = 0, hi = pop - 1;                                      // (u < 1 == cdf[pop - 1]: the answer is at most pop - 1)
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (cdf[mid] > u) hi = mid; else lo = mid + 1; }
+    return lo;
+}
+// is cand one of the ascending user_items[b, t)?
+__host__ __device__ __forceinline__ bool neg_is_own(const int64_t* __restrict__ user_items, int64_t b, int64_t t, int64_t cand) {
+    int64_t lo = b, hi = t;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (user_items[mid] < cand) lo = mid + 1; else hi = mid; }
+    return lo < t && user_items[lo] == cand;
+}
 
 #define SML_HID 512   // fc1 width                    (reference model/conv_transfer.py:33)
 #define SML_C1 10     // conv1 output channels        (model/conv_transfer.py:26-27)

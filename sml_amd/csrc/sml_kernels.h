@@ -475,3 +475,11 @@ hipError_t sml_launch_neg_sets(const int64_t* rows, int64_t n, int n_cols, int64
 int64_t sml_neg_sets_host_walk(const int64_t* rows, int64_t n, int n_cols, int64_t g0, const int32_t* n_cat, const int32_t* order,
                                const int64_t* h_off, const int32_t* h_items, const int32_t* h_since, int neg_num, uint64_t seed,
                                int64_t* out);
+// neg_sampler.hip: training negatives (1 <= pool <= 64; pool > 1: fp32 tables of d = 32 / 64; cdf NULL = uniform; no allocation,
+// copy or synchronise) and the same definition as a single-threaded walk over host memory (returns the number of failures)
+hipError_t sml_launch_neg_sampler(const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop, const int64_t* user_ptr,
+                                  int64_t n_users, const int64_t* user_items, const double* cdf, int pool, const float* wu, const float* wi,
+                                  int d, uint64_t seed, int max_workgroups, int64_t* negs, float* score, int* failed, hipStream_t st);
+int64_t sml_neg_sampler_host_walk(const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop, const int64_t* user_ptr,
+                                  int64_t n_users, const int64_t* user_items, const double* cdf, int pool, const float* wu, const float* wi,
+                                  int d, uint64_t seed, int64_t* negs, float* score);

@@ -226,11 +226,16 @@ class offlineDataset_withsample(Dataset):
         return out
 
 
-    def epoch_triples_device(self, engine, seed):
+    def epoch_triples_device(self, engine, seed, sampler=None, model=None):
         """One shuffled pass with fresh negatives, built ON THE DEVICE (fast mode: the same distribution as
         epoch_triples, not the reference's random streams): the counter-based permutation of sml_device_epoch over the
         resident (user, item) pairs, then engine.sample_negatives.  Returns an int64 [n,3] device tensor; nothing crosses
-        PCIe per epoch, and every rank of a job derives the same epoch from the same seed."""
+        PCIe per epoch, and every rank of a job derives the same epoch from the same seed.
+
+        sampler: a sml_amd.sampling.NegativeSampler; None is the uniform sampler above, the same code path and bytes.
+        Otherwise the same shuffle, then engine.sample_negatives_ex with seed + 1: the popularity cdf (alpha > 0) comes from
+        this set's own item column, built once and kept on the device; with pool > 1 the candidates are scored by the
+        tables of `model` (an MFbasemode, required then) as they are when the call is made."""
         import torch
         dev = engine.device
         cache = self.__dict__.setdefault("_dev_cache", {})
@@ -244,7 +249,17 @@ class offlineDataset_withsample(Dataset):
         # the shuffle: sml_device_epoch's counter-based permutation (columns 0, 1 of the triples); then the negatives
         tri = engine.device_epoch(c["ui"], len(self), seed)
         users = tri[:, 0].contiguous()
-        negs, failed = engine.sample_negatives(users, c["item_all"], c["uptr"], c["uitems"], int(seed) + 1)
+        if sampler is None:
+            negs, failed = engine.sample_negatives(users, c["item_all"], c["uptr"], c["uitems"], int(seed) + 1)
+        else:
+            from . import sampling
+            key = ("cdf", sampler.alpha)
+            if key not in c:
+                cdf = sampler.cdf(self.item_all, self.item)
+                c[key] = None if cdf is None else sampling.device_cdf(cdf, dev)
+            w_user, w_item = sampler.tables(model)
+            negs, failed = engine.sample_negatives_ex(users, c["item_all"], c["uptr"], c["uitems"], int(seed) + 1, pool=sampler.pool,
+                                                      cdf=c[key], w_user=w_user, w_item=w_item)
         self._last_failed = failed            # device counter; checked lazily by the caller if it cares
         tri[:, 2] = negs
         return tri

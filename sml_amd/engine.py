@@ -533,6 +533,48 @@ class HipEngine(object):
                                             _ptr(negs), _ptr(failed), self._stream()), "sml_sample_negatives")
         return negs, failed
 
+    def sample_negatives_ex(self, users, item_all, user_ptr, user_items, seed, pool=1, cdf=None, w_user=None, w_item=None,
+                            want_score=False, max_workgroups=0):
+        """A training negative per element of `users` (sml_sample_negatives_ex, "training negatives" in include/sml_hip.h):
+        candidates uniform over item_all -- or, with cdf (float64 [pop], nondecreasing, last entry exactly 1.0; a host
+        array, validated here before it is uploaded, or what sml_amd.sampling.device_cdf returned), by that distribution --
+        never one of the user's own items (CSR user_ptr / user_items, device int64); with pool = M > 1 the one of the first
+        M admissible candidates that the fp32 tables w_user / w_item [rows, d], d = 32 / 64, score highest.  pool=1,
+        cdf=None gives sample_negatives' bytes.  Returns (negs, failed[, score]); score (float32 [n], pool > 1 only, else
+        None) with want_score.  With pool > 1 the users and item_all are range-checked against the tables, one read-back."""
+        from . import sampling
+        users = self._dev(users, torch.int64)
+        item_all, user_ptr, user_items = (self._dev(t, torch.int64) for t in (item_all, user_ptr, user_items))
+        n, pop, pool = users.shape[0], item_all.shape[0], int(pool)
+        if pool < 1 or pool > 64:
+            raise ValueError("sample_negatives_ex: pool must be in 1..64, got %d" % pool)
+        if pop <= 0:
+            raise ValueError("sample_negatives_ex: item_all is empty")
+        if cdf is not None and not isinstance(cdf, sampling.DeviceCdf):
+            cdf = sampling.device_cdf(cdf, self.device, pop)           # validated on the host, then uploaded
+        if cdf is not None and (cdf.tensor.shape[0] != pop or cdf.tensor.device != self.device):
+            raise ValueError("sample_negatives_ex: cdf must have one entry per item of item_all (%d), on %s" % (pop, self.device))
+        wu = wi = score = None
+        if pool > 1:
+            if w_user is None or w_item is None:
+                raise ValueError("sample_negatives_ex: pool > 1 scores the candidates: w_user and w_item are needed")
+            if self.d not in (32, 64):
+                raise ValueError("sample_negatives_ex: pool > 1 needs embedding width 32 or 64, got %d" % self.d)
+            wu, wi = self._table(w_user), self._table(w_item)
+            if n:
+                lim = torch.stack([users.min(), users.max(), item_all.min(), item_all.max()]).tolist()      # one read-back
+                if lim[0] < 0 or lim[1] >= wu.shape[0] or lim[2] < 0 or lim[3] >= wi.shape[0]:
+                    raise ValueError("sample_negatives_ex: a user or an item of item_all is outside the tables")
+            if want_score:
+                score = torch.empty(n, device=self.device, dtype=torch.float32)
+        negs = torch.empty(n, device=self.device, dtype=torch.int64)
+        failed = torch.empty(1, device=self.device, dtype=torch.int32)
+        check(self.lib.sml_sample_negatives_ex(self._ctx, _ptr(users), n, _ptr(item_all), pop, _ptr(user_ptr), user_ptr.shape[0] - 1,
+                                               _ptr(user_items), _ptr(cdf.tensor if cdf is not None else None), pool, _ptr(wu), _ptr(wi),
+                                               self.d, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(max_workgroups), _ptr(negs),
+                                               _ptr(score), _ptr(failed), self._stream()), "sml_sample_negatives_ex")
+        return (negs, failed, score) if want_score else (negs, failed)
+
     def device_epoch(self, ui, n, seed, mat=None, row_stride=1, col=0):
         """int64 [n,3] device triples of one shuffled pass (sml_device_epoch): columns 0, 1 = ui[perm(e)] (ui: device int64
         [n,2]); column 2 = mat[perm(e) * row_stride + col] when a device integer matrix / column vector is given, else
