@@ -811,6 +811,58 @@ int sml_sample_negatives_ex(sml_ctx* ctx, const int64_t* users, int64_t n, const
                             const float* w_user, const float* w_item, int d, uint64_t seed, int max_workgroups, int64_t* negs,
                             float* score, int32_t* failed, void* stream);
 
+/* ---- RE-RANKING ------------------------------------------------------------------------ */
+/* Greedy MMR (maximal marginal relevance) re-ranking: from each list's pool of (item, relevance) entries pick up to k, one at
+ * a time, trading relevance against the similarity to what is already picked, and report how alike the picks are.  The
+ * kernel (sml_rerank_mmr), the host walk (sml_host_rerank_mmr) and the tests' restatement all implement this definition.
+ *
+ * Inputs per list x of [0, n).  A pool of at most 128 entries: pool_items[x * pool_stride + e] (int32) and
+ *   pool_rel[x * pool_stride + e] (float) for e in [0, pool_cols); 1 <= pool_cols <= 128, pool_stride >= pool_cols,
+ *   1 <= k <= 128.
+ * Tables.  The item table w_item [n_item, d], elem_bytes 4 (fp32, d = 32 / 64) or 2 (fp16, d = 32 / 64 / 128): the pairs
+ *   sml_retrieval_supports answers for; fp16 entries are widened exactly.
+ * Norms.  nrm float [>= n_item] or NULL: plane 0 of the table sml_item_adjust_cosine writes is exactly this.
+ * Trade-off.  lam in [0, 1]; oml = 1.0f - lam, formed once in fp32; normalize is 0 or 1.
+ * Eligible.  Entry e is ELIGIBLE when 0 <= id < n_item (any other id is padding and no address is formed from it: the
+ *   (-1, -inf) padding of the top-K calls is skipped), rel is not NaN, and no e' < e has the same id and a non-NaN rel: the
+ *   first occurrence wins.
+ * Relevance r(e).  normalize == 0: rel as given.  normalize == 1: min-max scaled over the list's eligible entries:
+ *   lo = min rel, hi = max rel (-0 orders below +0), span = hi - lo, r = span > 0 ? (rel - lo) / span : +0 -- an fp32
+ *   subtraction and a correctly rounded fp32 division.
+ * Similarity of candidate c against a picked item s.  S = the retrieval score chain with x_s on the user side and x_c on the
+ *   item side: acc = 0, then for q = 0 .. d/2 - 1: acc = fmaf(x_c[q], x_s[q], acc); acc = fmaf(x_c[q + d/2], x_s[q + d/2],
+ *   acc).  nrm == NULL: sim = S.  Otherwise sim = (S * nrm[c]) * nrm[s]: two fp32 multiplies in that order, the candidate's
+ *   norm first.
+ * State.  Per entry pen = -inf, sum = +0; per list total = +0.
+ * Selection, for t = 0, 1, ... while t < k and an eligible entry is unpicked:
+ *   q(e) = +0 when t == 0, otherwise q(e) = -(oml * pen(e)): one fp32 multiply, then an exact negation;
+ *   v(e) = fmaf(lam, r(e), q(e));
+ *   the pick is the unpicked eligible entry that comes first in the total order (NaN last, then v descending, then pool
+ *   position ascending);
+ *   items[x, t] = id, pos[x, t] = e, value[x, t] = v;  total = total + sum(pick), an fp32 add, in pick order;
+ *   for every other unpicked eligible entry, with sim taken against the pick: pen = sim > pen ? sim : pen (a NaN sim never
+ *   replaces pen); sum = sum + sim, an fp32 add.
+ * Outputs.  items, pos int32 [n, k], value float [n, k]; n_sel[x] (int32 [n]) = the number of picks = min(k, eligible
+ *   entries); sim_sum[x] (float [n]) = total, which the caller divides by m (m - 1) / 2 to get the intra-list similarity of
+ *   the m picks.  Unused slots hold (-1, -1, -inf).  Every output is written.
+ * Rounding rule.  Each named multiply, add and subtract is a single rounding: sum + sim does not fuse with sim's last
+ *   multiply and oml * pen does not fuse into anything; the only fused operations are the fmaf calls named above.  This
+ *   holds on the device and in the host walk alike.
+ * Consequences.  With lam == 1 and normalize == 0 the picks are the pool in order of (rel descending, position ascending)
+ *   and value holds rel's bits (oml is 0, so q is a zero as long as pen is finite; a rel of -0 may read +0): on a pool that a
+ *   top-K call returned, items is the pool's first k columns byte for byte.
+ *   With lam == 0 the first pick is the pool position of the first eligible entry.  The bytes are the same for every launch
+ *   geometry: max_workgroups = 0 leaves the grid to the call, a positive value caps it (lists are walked grid-stride, one
+ *   wavefront per list).  At d = 32 / 64 a call on fp16 tables equals the call on exact fp32 copies bit for bit.
+ * Refused (sml_last_error): a (d, elem_bytes) pair without kernels; pool_cols, pool_stride or k out of range; lam outside
+ *   [0, 1] or NaN; normalize not 0 / 1; max_workgroups < 0; a table that is not 16-byte aligned; an output that overlaps an
+ *   input or another output as far as the pointers and the sizes show it.  n == 0 is a valid call that launches nothing.
+ *   No allocation, no scratch, no copy to the host, no synchronise.  All pointers are device memory.  Asynchronous. */
+int sml_rerank_mmr(sml_ctx* ctx, const void* w_item, int elem_bytes, int64_t n_item, const int32_t* pool_items,
+                   const float* pool_rel, int64_t n, int pool_cols, int64_t pool_stride, const float* nrm, float lam,
+                   int normalize, int k, int max_workgroups, int32_t* items, int32_t* pos, float* value, int32_t* n_sel,
+                   float* sim_sum, void* stream);
+
 /* ---- host helper: batch supply ------------------------------------------------------- */
 /* Sequential rejection sampling of offlineDataset_withsample.__getitem__ (reference
  * data/dataset.py:63-71) over a pre-drawn candidate stream, on the HOST (no GPU involved):
@@ -849,6 +901,13 @@ int sml_host_neg_sets(const int64_t* rows, int64_t n, int n_cols, int64_t g0, co
 int sml_host_sample_negatives_ex(const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop, const int64_t* user_ptr,
                                  int64_t n_users, const int64_t* user_items, const double* cdf, int pool, const float* w_user,
                                  const float* w_item, int d, uint64_t seed, int64_t* negs, float* score, int32_t* failed);
+
+/* sml_rerank_mmr (re-ranking) over HOST memory: the single-threaded walk of the same definition, one entry at a time, built
+ * from the same functions as the kernel -- the same bytes in every output, fp16 tables included (d is given since there is
+ * no context).  The refusals are the kernel entry's.  The route of a machine without a GPU. */
+int sml_host_rerank_mmr(const void* w_item, int elem_bytes, int d, int64_t n_item, const int32_t* pool_items,
+                        const float* pool_rel, int64_t n, int pool_cols, int64_t pool_stride, const float* nrm, float lam,
+                        int normalize, int k, int32_t* items, int32_t* pos, float* value, int32_t* n_sel, float* sim_sum);
 
 /* ---- self test ------------------------------------------------------------------ */
 /* Checks the MFMA operand/accumulator lane maps this library assumes against a

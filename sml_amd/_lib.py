@@ -209,6 +209,12 @@ SIGNATURES = {
                                                c_void, c_void]),
     "sml_host_sample_negatives_ex": (ctypes.c_int, [c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void,
                                                     ctypes.c_int, c_void, c_void, ctypes.c_int, ctypes.c_uint64, c_void, c_void, c_void]),
+    "sml_rerank_mmr": (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                      c_void, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void, c_void, c_void,
+                                      c_void]),
+    "sml_host_rerank_mmr": (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_void, c_void, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.c_int64, c_void, ctypes.c_float, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void, c_void,
+                                           c_void]),
     "sml_selftest": (ctypes.c_int, [ctypes.c_int]),
 }
 

@@ -2499,6 +2499,63 @@ int sml_host_sample_negatives_ex(const int64_t* users, int64_t n, const int64_t*
     return SML_OK;
 }
 
+// ---- re-ranking (rerank.hip) ----
+// what both entries refuse, as the header lists it; nullptr = the call is in order (n == 0 included: nothing is read)
+static const char* rerank_refusal(const void* w_item, int elem_bytes, int d, int64_t n_item, const int32_t* pool_items, const float* pool_rel,
+                                  int64_t n, int pool_cols, int64_t pool_stride, const float* nrm, float lam, int normalize, int k,
+                                  int max_workgroups, const int32_t* items, const int32_t* pos, const float* value, const int32_t* n_sel,
+                                  const float* sim_sum) {
+    if (!elem_ok(elem_bytes) || !sml_retrieval_supports(d, elem_bytes))
+        return "bad argument (d must be 32/64, or 128 for fp16 tables; elem_bytes 4 or 2)";
+    if (n_item <= 0 || n_item >= ((int64_t)1 << 31) || n < 0 || n >= ((int64_t)1 << 31)) return "bad argument (0 < n_item < 2^31, 0 <= n < 2^31)";
+    if (pool_cols < 1 || pool_cols > 128 || pool_stride < pool_cols) return "bad argument (1 <= pool_cols <= 128, pool_stride >= pool_cols)";
+    if (k < 1 || k > 128) return "bad argument (1 <= k <= 128)";
+    if (!(lam >= 0.0f && lam <= 1.0f)) return "bad argument (lam must lie in [0, 1])";
+    if (normalize != 0 && normalize != 1) return "bad argument (normalize must be 0 or 1)";
+    if (max_workgroups < 0) return "bad argument (max_workgroups >= 0)";
+    if (n == 0) return nullptr;
+    if (!w_item || !pool_items || !pool_rel || !items || !pos || !value || !n_sel || !sim_sum) return "null argument";
+    if ((uintptr_t)w_item & 15) return "the table must be 16-byte aligned";
+    const int64_t pool_bytes = 4 * ((n - 1) * pool_stride + pool_cols), out_bytes = 4 * n * (int64_t)k;
+    const struct { const void* p; int64_t bytes; } in[] = {
+        {w_item, n_item * d * elem_bytes}, {pool_items, pool_bytes}, {pool_rel, pool_bytes}, {nrm, 4 * n_item}};
+    const struct { const void* p; int64_t bytes; } out[] = {{items, out_bytes}, {pos, out_bytes}, {value, out_bytes}, {n_sel, 4 * n}, {sim_sum, 4 * n}};
+    for (const auto& o : out)
+        for (const auto& i : in)
+            if (iset_overlap(o.p, o.bytes, i.p, i.bytes)) return "an output overlaps an input";
+    for (int a = 0; a < 5; ++a)
+        for (int b = a + 1; b < 5; ++b)
+            if (iset_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) return "the outputs overlap each other";
+    return nullptr;
+}
+
+int sml_rerank_mmr(sml_ctx* ctx, const void* w_item, int elem_bytes, int64_t n_item, const int32_t* pool_items, const float* pool_rel,
+                   int64_t n, int pool_cols, int64_t pool_stride, const float* nrm, float lam, int normalize, int k, int max_workgroups,
+                   int32_t* items, int32_t* pos, float* value, int32_t* n_sel, float* sim_sum, void* stream) {
+    if (!ctx) return fail(SML_EINVAL, "sml_rerank_mmr", "null context");
+    if (const char* why = rerank_refusal(w_item, elem_bytes, ctx->d, n_item, pool_items, pool_rel, n, pool_cols, pool_stride, nrm, lam, normalize,
+                                         k, max_workgroups, items, pos, value, n_sel, sim_sum))
+        return fail(SML_EINVAL, "sml_rerank_mmr", why);
+    if (n == 0) return SML_OK;
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_rerank_mmr(ctx->d, elem_bytes, w_item, n_item, pool_items, pool_rel, n, pool_cols, pool_stride, nrm, lam,
+                                                   normalize, k, max_workgroups, items, pos, value, n_sel, sim_sum, st)));
+    return SML_OK;
+}
+
+int sml_host_rerank_mmr(const void* w_item, int elem_bytes, int d, int64_t n_item, const int32_t* pool_items, const float* pool_rel, int64_t n,
+                        int pool_cols, int64_t pool_stride, const float* nrm, float lam, int normalize, int k, int32_t* items, int32_t* pos,
+                        float* value, int32_t* n_sel, float* sim_sum) {
+    if (const char* why = rerank_refusal(w_item, elem_bytes, d, n_item, pool_items, pool_rel, n, pool_cols, pool_stride, nrm, lam, normalize, k, 0,
+                                         items, pos, value, n_sel, sim_sum))
+        return fail(SML_EINVAL, "sml_host_rerank_mmr", why);
+    if (n == 0) return SML_OK;
+    if (!sml_rerank_host_walk(d, elem_bytes, w_item, n_item, pool_items, pool_rel, n, pool_cols, pool_stride, nrm, lam, normalize, k, items, pos,
+                              value, n_sel, sim_sum))
+        return fail(SML_EINVAL, "sml_host_rerank_mmr", "no walk for this (d, elem_bytes) pair");
+    return SML_OK;
+}
+
 int sml_host_resolve_negatives_csr(const int64_t* users, int64_t n, const int64_t* cand, int64_t m,
                                    const int64_t* user_ptr, int64_t n_users, const int64_t* user_items, int64_t* negs,
                                    int64_t* consumed, int64_t* resolved) {

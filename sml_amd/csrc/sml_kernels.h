@@ -483,3 +483,13 @@ hipError_t sml_launch_neg_sampler(const int64_t* users, int64_t n, const int64_t
 int64_t sml_neg_sampler_host_walk(const int64_t* users, int64_t n, const int64_t* item_all, int64_t pop, const int64_t* user_ptr,
                                   int64_t n_users, const int64_t* user_items, const double* cdf, int pool, const float* wu, const float* wi,
                                   int d, uint64_t seed, int64_t* negs, float* score);
+// rerank.hip: greedy MMR re-ranking of per-list pools (1 <= pool_cols, k <= 128; the (d, elem_bytes) pairs of
+// sml_retrieval_supports, any other is hipErrorInvalidValue / false; nrm NULL = the bare dot; no allocation, copy or
+// synchronise) and the same definition as a single-threaded walk over host memory
+hipError_t sml_launch_rerank_mmr(int d, int elem_bytes, const void* wi, int64_t n_item, const int32_t* pool_items, const float* pool_rel,
+                                 int64_t n, int pool_cols, int64_t pool_stride, const float* nrm, float lam, int normalize, int k,
+                                 int max_workgroups, int32_t* items, int32_t* pos, float* value, int32_t* n_sel, float* sim_sum,
+                                 hipStream_t st);
+bool sml_rerank_host_walk(int d, int elem_bytes, const void* wi, int64_t n_item, const int32_t* pool_items, const float* pool_rel, int64_t n,
+                          int pool_cols, int64_t pool_stride, const float* nrm, float lam, int normalize, int k, int32_t* items,
+                          int32_t* pos, float* value, int32_t* n_sel, float* sim_sum);

@@ -1003,6 +1003,50 @@ class HipEngine(object):
                                            _ptr(n_elig), self._stream()), "sml_topk_candidates")
         return items.long(), scores, n_elig
 
+    def rerank_mmr(self, item_tab, pool_items, pool_scores, k, lam, metric="cosine", normalize=True, max_workgroups=0, nrm=None):
+        """Greedy MMR re-ranking of per-list pools (include/sml_hip.h, RE-RANKING; sml_rerank_mmr: one wavefront per list, no
+        scratch).  pool_items int [n, C <= 128] (int64 as recommend returns them is narrowed on the device; entries outside
+        the catalogue are padding) and pool_scores float32 [n, C]: each list's candidates and their relevance.  Each of up
+        to k picks maximises lam * r - (1 - lam) * max sim(candidate, picks so far); r is the relevance, min-max scaled per
+        list with normalize.  metric="cosine" builds the item norms from item_tab now (item_adjust_cosine) unless nrm= gives
+        a ready table (float32 [>= n_item], or the [2, n_pad] table item_adjust_cosine returns); metric="dot" is the bare
+        dot product.  Returns (items int64 [n, k], pos int32 [n, k] -- the pick's column in the pool --, value float32
+        [n, k], n_sel int32 [n], sim_sum float32 [n] -- the sum of the picks' pairwise similarities); unused slots are
+        (-1, -1, -inf).  max_workgroups > 0 caps the grid (the bytes do not depend on it)."""
+        from .retrieval import rerank_args
+        k, lam = rerank_args(k, lam, metric)
+        _, wi, _ = self._retrieval_tables(item_tab, item_tab)
+        pool_items = self._dev(pool_items, torch.int64 if not torch.is_tensor(pool_items) else pool_items.dtype)
+        if pool_items.dtype not in (torch.int32, torch.int64) or pool_items.dim() != 2:
+            raise ValueError("pool_items is an int32 / int64 matrix [n, C], got %s %s" % (pool_items.dtype, tuple(pool_items.shape)))
+        pool_scores = self._dev(pool_scores, torch.float32)
+        if pool_scores.shape != pool_items.shape:
+            raise ValueError("pool_scores %s does not match pool_items %s" % (tuple(pool_scores.shape), tuple(pool_items.shape)))
+        n, cols = pool_items.shape
+        rerank_args(k, lam, metric, cols)
+        if pool_items.dtype == torch.int64:              # ids beyond int32 are padding either way: they narrow to -1
+            pool_items = torch.where((pool_items >= 0) & (pool_items < wi.shape[0]), pool_items, pool_items.new_full((), -1)).int()
+        if metric == "dot":
+            nrm = None
+        elif nrm is None:
+            nrm = self.item_adjust_cosine(wi)
+        else:
+            if not torch.is_tensor(nrm):
+                nrm = self._dev(np.asarray(nrm), torch.float32)
+            shape_ok = (nrm.dim() == 1 and nrm.shape[0] >= wi.shape[0]) or (nrm.dim() == 2 and nrm.shape[1] >= wi.shape[0])
+            if nrm.dtype != torch.float32 or nrm.device != self.device or not nrm.is_contiguous() or not shape_ok:
+                raise ValueError("nrm is a contiguous float32 table of at least %d entries on %s (plane 0 of item_adjust_cosine's table)"
+                                 % (wi.shape[0], self.device))
+        items = torch.empty(n, k, device=self.device, dtype=torch.int32)
+        pos = torch.empty(n, k, device=self.device, dtype=torch.int32)
+        value = torch.empty(n, k, device=self.device, dtype=torch.float32)
+        n_sel = torch.empty(n, device=self.device, dtype=torch.int32)
+        sim_sum = torch.empty(n, device=self.device, dtype=torch.float32)
+        check(self.lib.sml_rerank_mmr(self._ctx, _ptr(wi), wi.element_size(), wi.shape[0], _ptr(pool_items), _ptr(pool_scores), n, cols, cols,
+                                      _ptr(nrm), lam, int(bool(normalize)), k, int(max_workgroups), _ptr(items), _ptr(pos), _ptr(value),
+                                      _ptr(n_sel), _ptr(sim_sum), self._stream()), "sml_rerank_mmr")
+        return items.long(), pos, value, n_sel, sim_sum
+
     USER_RANK_SCRATCH_BYTES = 256 << 20  # held-out items of one sml_user_rank call are capped so its scratch fits this
 
     def user_ranks(self, user_tab, item_tab, users, pos_off, pos_items, seen=None, ks=(20,), allow=None, adjust=None):

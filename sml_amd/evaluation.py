@@ -144,3 +144,25 @@ def test_model_users(model, test_pairs, seen=None, topK=(20, 10, 5), old_user=No
     extra = dict(([("items", items)] if items is not None else []) + ([("score", score)] if score is not None else []))
     out = model.test_users(sets, topK=topK, exclude=seen, **extra)
     return user_metrics(out, old_user, old_item)
+
+
+def intra_list_similarity(model, lists, metric="cosine"):
+    """float32 [n]: the mean pairwise similarity of each list's items -- the number that shows what
+    MFbasemode.recommend(diversify=) did.  lists: item ids [n, m <= 128], padded with -1 (ids outside the catalogue and
+    repeats of an id count as padding); metric "cosine" or "dot" of the item rows.  One HipEngine.rerank_mmr call with
+    lam = 1, normalize=False and rel = -position: the order is kept, so the sum of the pairs' similarities runs in list
+    order, and it is divided by m (m - 1) / 2 over the m live items (0 for m < 2)."""
+    from .mf import _engine_for
+    from .retrieval import rerank_args
+    eng = _engine_for(model)
+    dev = model.item_laten.weight.device
+    lists = torch.as_tensor(lists).to(dev)
+    if lists.dim() != 2:
+        raise ValueError("lists is a matrix [n, m] of item ids padded with -1, got shape %s" % (tuple(lists.shape),))
+    n, m = lists.shape
+    rerank_args(m, 1.0, metric, m)
+    rel = -torch.arange(m, device=dev, dtype=torch.float32).expand(n, m).contiguous()
+    _, _, _, n_sel, sim_sum = eng.rerank_mmr(model.item_laten.weight.data, lists, rel, m, 1.0, metric=metric, normalize=False)
+    cnt = n_sel.float()
+    pairs = cnt * (cnt - 1.0) / 2.0
+    return torch.where(pairs > 0, sim_sum / pairs.clamp(min=1.0), torch.zeros_like(sim_sum))

@@ -70,7 +70,8 @@ class MFbasemode(nn.Module):
         hit_rows = (ranks < topK).nonzero()[:, 0]
         return hit_rows, ranks, hits * 1.0, (torch.tensor(ndcg) if hits > 0 else 0)
 
-    def recommend(self, users, topK=20, exclude=None, items=None, score=None, candidates=None):
+    def recommend(self, users, topK=20, exclude=None, items=None, score=None, candidates=None, diversify=None, pool=None,
+                  metric="cosine"):
         """(items int64 [n, topK], scores float32 [n, topK]): each user's topK items over the whole catalogue by the score
         test() uses (no bias terms), score descending then item id ascending, leaving out `exclude` (a
         sml_amd.retrieval.SeenItems or a (seen_off, seen_items) CSR); missing slots are (-1, -inf).  items: restrict the
@@ -80,8 +81,20 @@ class MFbasemode(nn.Module):
         dot product.  The returned scores are A.  candidates: the same call restricted PER USER -- each user's own list of
         item ids (anything sml_amd.retrieval.as_candidates takes: a matrix [n, C] padded with -1, a (cand_off, cand_items)
         pair, a list of sequences, a CandidateRows); the lists hold the distinct eligible candidates only, and no catalogue
-        walk is made (HipEngine.topk_candidates).  users may be None when candidates is a CandidateRows."""
+        walk is made (HipEngine.topk_candidates).  users may be None when candidates is a CandidateRows.
+        diversify: None -- nothing changes -- or lam in [0, 1]: "the same list, but not topK of the same thing".  The call
+        then takes each user's top `pool` items (default min(128, 5 * topK); exclude, items, score and candidates apply as
+        above) and re-ranks them greedily by lam * r - (1 - lam) * max similarity to the items already picked (r: the score,
+        min-max scaled per list; similarity by `metric`, "cosine" or "dot" of the item rows; HipEngine.rerank_mmr).  The
+        returned scores are the model's scores of the picked items, gathered from the pool.  diversify=1 returns the plain
+        list; sml_amd.evaluation.intra_list_similarity says how alike a list's items are."""
         from .retrieval import as_csr, as_filter, as_score
+        if diversify is not None:
+            from .retrieval import diversify_args
+            pool = diversify_args(topK, diversify, pool, metric)
+            it, sc = self.recommend(users, pool, exclude=exclude, items=items, score=score, candidates=candidates)
+            picked, at, _, _, _ = _engine_for(self).rerank_mmr(self.item_laten.weight.data, it, sc, topK, diversify, metric=metric)
+            return picked, torch.where(at >= 0, sc.gather(1, at.clamp(min=0).long()), sc.new_full((), float("-inf")))
         eng = _engine_for(self)
         w = self.user_laten.weight
         if candidates is not None:

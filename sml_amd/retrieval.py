@@ -544,3 +544,34 @@ def self_seen(n_item, device):
         hit = _SELF_SEEN[key] = (int(n_item), (torch.arange(n_item + 1, device=device, dtype=torch.int64),
                                               torch.arange(n_item, device=device, dtype=torch.int32)))
     return hit[1]
+
+
+RERANK_MAX = 128     # pool entries and picks per list of sml_rerank_mmr
+
+
+def rerank_args(k, lam, metric="cosine", pool_cols=None):
+    """(k, lam) as HipEngine.rerank_mmr passes them on, checked without a device: 1 <= k <= 128, lam a number in [0, 1],
+    metric "cosine" or "dot", and, when given, 1 <= pool_cols <= 128."""
+    k = int(k)
+    if not 1 <= k <= RERANK_MAX:
+        raise ValueError("k must lie in 1..%d, got %d" % (RERANK_MAX, k))
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:                     # (NaN fails both comparisons)
+        raise ValueError("lam must lie in [0, 1], got %r" % (lam,))
+    if metric not in ("cosine", "dot"):
+        raise ValueError('metric is "cosine" or "dot", got %r' % (metric,))
+    if pool_cols is not None and not 1 <= int(pool_cols) <= RERANK_MAX:
+        raise ValueError("a pool holds 1..%d entries per list, got %d" % (RERANK_MAX, int(pool_cols)))
+    return k, lam
+
+
+def diversify_args(topK, diversify, pool, metric):
+    """The pool size of MFbasemode.recommend(diversify=): `pool` or min(128, 5 * topK), checked without a device."""
+    topK = int(topK)
+    pool = min(RERANK_MAX, 5 * topK) if pool is None else int(pool)
+    if pool > RERANK_MAX:
+        raise ValueError("pool must not exceed %d, got %d" % (RERANK_MAX, pool))
+    if topK > pool:
+        raise ValueError("topK = %d exceeds the pool of %d" % (topK, pool))
+    rerank_args(topK, diversify, metric, pool)
+    return pool
