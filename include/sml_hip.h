@@ -635,6 +635,51 @@ int sml_topk_candidates(sml_ctx* ctx, const void* w_user, const void* w_item, in
                         int k, const int64_t* seen_off, const int32_t* seen_items,
                         const uint32_t* allow, const float* adj, int max_workgroups,
                         int32_t* items, float* scores, int32_t* n_elig, void* stream);
+/* ---- DEEP LISTS: candidate generation at depth -- lists of up to 1,024 items per user over the whole catalogue, for a
+ * downstream re-ranker, a recall@K curve or a pool.  sml_topk_items keeps a sorted list per (user, slice) and its cost grows
+ * with k; sml_topk_deep selects by radix: a fixed number of catalogue walks (four counting passes over the order-preserving
+ * bits of the score, one or two collecting passes) and one sort per user, whatever k is and whatever the data are.
+ * Arguments: the tables, elem_bytes (4: d = 32 / 64; 2: d = 32 / 64 / 128; any other pair is refused), Seen and allow are
+ * those of sml_topk_items_adjusted, and so is adj, except that here adj == NULL is accepted and means the bare score S (no fmaf
+ * is applied: the chain's bits are returned, as sml_topk_candidates reads it).  allow == NULL: no filter.
+ * 1 <= k <= SML_TOPK_DEEP_MAX.  users int64 [n]; a user may repeat.
+ * Outputs: items / scores (int32 / float [n, k]) are exactly the top-K family's definition: the ELIGIBLE items -- below n_item,
+ * not in Seen(u), allowed, and A not NaN -- in the order A descending, then item id ascending; slots past the eligible count
+ * hold (-1, -inf).  n_elig[x] (int32 [n]; may be NULL) = the number of eligible items of users[x].  Every output is written.
+ * Defining identities:
+ *   - for k <= 128, items and scores equal those of sml_topk_items[_filtered|_adjusted][_f16] on the same arguments byte for
+ *     byte;
+ *   - for any k' < k, row x of the k'-call is the first k' slots of row x of the k-call;
+ *   - a filtered call returns what the unfiltered call returns with the complement of the filter added to every user's Seen
+ *     range (Seen' = Seen U complement); at d = 32 / 64 a call on fp16 tables equals the call on fp32 copies of them bit for
+ *     bit; with the same Seen, filter and adj, the positive of a row (u, p) sits at position
+ *     rank + #{eligible i != p : A(u,i) == A(u,p), i < p} of u's list (rank: sml_full_rank's) whenever that is < k.
+ * Ties: the order compares floats, so -0 and +0 tie and the id decides (with adj, fmaf(+0, -1, -0) is -0); the integer key
+ * the selection derives from a score sends both zeros to one key, and the returned score keeps its own sign bit.  NaN never
+ * enters a list.  -inf is eligible and orders last.
+ * Geometry: slices = 0 leaves the grid to the call, a value in [1, 256] forces the number of item slices; the bytes are the
+ * same for every value, empty slices included.
+ * scratch: sml_topk_deep_scratch_bytes(ctx, n, k, n_item, slices) bytes of device memory, 256-byte aligned, for the same n,
+ * n_item and slices (< 0: bad argument); about 1 KB per user.  It is written by the call and holds nothing afterwards.
+ * n == 0 is a valid call that launches nothing.  No allocation, no copy to the host and no synchronise happen inside; counts
+ * are added with integer atomics (exact, order-free) and there are no floating-point atomics.
+ * Refused (sml_last_error): k outside [1, 1024] or slices outside [0, 256]; exactly one of seen_off / seen_items NULL; a
+ * (d, elem_bytes) pair the kernels do not exist for; a misaligned table, adj or scratch; an output that overlaps an input or
+ * another output as far as the pointers and the sizes known to the call show it.  Indices (users) are trusted.
+ * Not measured beyond the shapes profiles/ records; sml_topk_candidates and sml_rerank_mmr keep their limit of 128.
+ * sml_host_topk_items: the same definition as a single-threaded walk over HOST memory, for any k in [1, 1024] -- every item's
+ * score by the same chain (the host and the device share its text), no GPU needed; d is the caller's (no context).  It
+ * refuses what sml_topk_deep refuses, except that nothing has to be aligned. */
+#define SML_TOPK_DEEP_MAX 1024
+int64_t sml_topk_deep_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item, int slices);
+int sml_topk_deep(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item,
+                  const int64_t* users, int64_t n, int k,
+                  const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                  int slices, void* scratch, int32_t* items, float* scores, int32_t* n_elig, void* stream);
+int sml_host_topk_items(const void* w_user, const void* w_item, int elem_bytes, int d, int64_t n_item,
+                        const int64_t* users, int64_t n, int k,
+                        const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                        int32_t* items, float* scores, int32_t* n_elig);
 /* Per-user metrics from pos (as sml_user_rank writes it; any value < 0 is never a hit) over the ranges of pos_off,
  * n < 2^31.  ks: HOST int32 [n_k], 1 <= n_k <= 8, every K >= 1.  For user x with m = |T(x)| and each K (outputs [n, n_k], row-major):
  *   hits = #{p : 0 <= pos(p) < K};  dcg = sum over hits of 1/log2(pos + 2), fp32, summed in ascending pos;

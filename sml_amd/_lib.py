@@ -142,6 +142,11 @@ SIGNATURES = {
     "sml_topk_candidates": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, c_void, ctypes.c_int,
                                            c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_void, c_void, c_void, c_void,
                                            ctypes.c_int, c_void, c_void, c_void, c_void]),
+    "sml_topk_deep_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    "sml_topk_deep": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
+                                     c_void, c_void, ctypes.c_int, c_void, c_void, c_void, c_void, c_void]),
+    "sml_host_topk_items": (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int,
+                                           c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "sml_user_metrics": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,
                                         c_void]),
     "sml_stream_create_cu_range": (ctypes.c_int, [ctypes.POINTER(c_void), ctypes.c_int, ctypes.c_int, ctypes.c_int]),

@@ -1998,6 +1998,75 @@ int sml_topk_candidates(sml_ctx* ctx, const void* w_user, const void* w_item, in
     return SML_OK;
 }
 
+// deep lists: what sml_topk_deep and sml_host_topk_items refuse alike (NULL: nothing).  The tables' heights are unknown: they
+// count from their first row only
+static const char* deep_refusal(int d, int elem_bytes, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,
+                                int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj, int slices,
+                                const void* scratch, int64_t scratch_bytes, const int32_t* items, const float* scores, const int32_t* n_elig) {
+    if (!elem_ok(elem_bytes)) return "bad argument (elem_bytes must be 4 or 2)";
+    if (k < 1 || k > SML_TOPK_DEEP_MAX) return "bad argument (1 <= k <= 1024)";
+    if (slices < 0 || slices > 256) return "bad argument (0 <= slices <= 256)";
+    if (!sml_retrieval_supports(d, elem_bytes)) return "bad argument (d must be 32/64, or 128 for fp16 tables)";
+    if (n_item <= 0 || n_item >= ((int64_t)1 << 31) || n < 0 || n >= ((int64_t)1 << 31)) return "bad argument (0 < n_item < 2^31, 0 <= n < 2^31)";
+    if ((!seen_off) != (!seen_items)) return "bad argument (seen_off and seen_items both or neither)";
+    if (n == 0) return nullptr;
+    if (!w_user || !w_item || !users || !items || !scores) return "null argument";
+    const int64_t out_bytes = 4 * n * (int64_t)k;
+    const int64_t n_pad = sml_item_adjust_pad(n_item);
+    const struct { const void* p; int64_t bytes; } in[] = {
+        {users, 8 * n}, {w_user, (int64_t)d * elem_bytes}, {w_item, n_item * d * elem_bytes}, {seen_off, 8}, {seen_items, 4},
+        {allow, n_pad / 8}, {adj, 8 * n_pad}};
+    const struct { const void* p; int64_t bytes; } out[] = {{items, out_bytes}, {scores, out_bytes}, {n_elig, 4 * n}, {scratch, scratch_bytes}};
+    for (const auto& o : out)
+        for (const auto& i : in)
+            if (iset_overlap(o.p, o.bytes, i.p, i.bytes)) return "an output overlaps an input";
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            if (iset_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) return "the outputs overlap each other";
+    return nullptr;
+}
+
+int64_t sml_topk_deep_scratch_bytes(sml_ctx* ctx, int64_t n, int k, int64_t n_item, int slices) {
+    if (!ctx || n < 0 || n >= ((int64_t)1 << 31) || k < 1 || k > SML_TOPK_DEEP_MAX || n_item <= 0 || n_item >= ((int64_t)1 << 31) || slices < 0 ||
+        slices > 256)
+        return fail(SML_EINVAL, "sml_topk_deep_scratch_bytes", "bad argument (1 <= k <= 1024, 0 <= slices <= 256, 0 < n_item < 2^31, 0 <= n < 2^31)");
+    return n == 0 ? 0 : sml_topk_deep_scratch_size(n, n_item, slices);
+}
+
+int sml_topk_deep(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* users, int64_t n, int k,
+                  const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj, int slices, void* scratch,
+                  int32_t* items, float* scores, int32_t* n_elig, void* stream) {
+    const char* what = "sml_topk_deep";
+    if (!ctx) return fail(SML_EINVAL, what, "null argument");
+    if (adj && ((uintptr_t)adj & 15)) return fail(SML_EINVAL, what, "adj must be 16-byte aligned");
+    const int64_t scratch_bytes = n > 0 && n < ((int64_t)1 << 31) && n_item > 0 && n_item < ((int64_t)1 << 31) && slices >= 0 && slices <= 256
+                                      ? sml_topk_deep_scratch_size(n, n_item, slices) : 0;
+    if (const char* why = deep_refusal(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, adj, slices, scratch,
+                                       scratch_bytes, items, scores, n_elig))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    if (!scratch) return fail(SML_EINVAL, what, "null argument");
+    if (((uintptr_t)w_user | (uintptr_t)w_item) & 15) return fail(SML_EINVAL, what, "the tables must be 16-byte aligned");
+    if ((uintptr_t)scratch & 255) return fail(SML_EINVAL, what, "scratch must be 256-byte aligned");
+    const SmlCatalogue c = {ctx->d, elem_bytes, w_user, w_item, n_item, seen_off, seen_items, allow, adj};
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_topk_deep(c, users, n, k, slices, scratch, items, scores, n_elig, st)));
+    return SML_OK;
+}
+
+int sml_host_topk_items(const void* w_user, const void* w_item, int elem_bytes, int d, int64_t n_item, const int64_t* users, int64_t n, int k,
+                        const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj, int32_t* items,
+                        float* scores, int32_t* n_elig) {
+    const char* what = "sml_host_topk_items";
+    if (const char* why = deep_refusal(d, elem_bytes, w_user, w_item, n_item, users, n, k, seen_off, seen_items, allow, adj, 0, nullptr, 0, items,
+                                       scores, n_elig))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    const SmlCatalogue c = {d, elem_bytes, w_user, w_item, n_item, seen_off, seen_items, allow, adj};
+    if (!sml_topk_host_walk(c, users, n, k, items, scores, n_elig)) return fail(SML_EINVAL, what, "no walk for this (d, elem_bytes) pair");
+    return SML_OK;
+}
+
 int64_t sml_item_adjust_len(int64_t n_item) {
     if (n_item <= 0 || n_item >= ((int64_t)1 << 31)) return fail(SML_EINVAL, "sml_item_adjust_len", "bad argument (0 < n_item < 2^31)");
     return sml_item_adjust_pad(n_item);

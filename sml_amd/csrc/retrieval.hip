@@ -77,6 +77,11 @@
 // ids instead of walking the catalogue -- one wavefront per list, a lane per candidate, the row gathered whole and scored by
 // score_chain on the VALU, the K best in the wave's LDS.  It shares score_chain, better, adjusted, offset_plane and
 // lower_bound with the kernels above and changes none of them.
+//
+// Deep lists (sml_topk_deep, 1 <= k <= 1,024): k_deep_count / k_deep_pick / k_deep_collect / k_deep_sort behind it select each
+// user's k best by radix over an integer key of the score -- walk_slice callables that keep nothing sorted, so the cost is a
+// fixed number of walks whatever k is -- and deep_host_walk is the same definition on the host (sml_host_topk_items).  For
+// that walk score_chain, better and adjusted are __host__ __device__: the host and the kernels share the chain's text.
 #include <climits>
 #include <cmath>
 #include <type_traits>
@@ -93,7 +98,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // S(u, i) in the k order of tile_scores(): the device-side definition every retrieval kernel agrees with, bit for bit
 // (T = _Float16: x[s] and u[s] convert to float, exactly, as fmaf's arguments)
 template <int D, class T>
-__device__ __forceinline__ float score_chain(const T* __restrict__ u, const T* __restrict__ x) {
+__host__ __device__ __forceinline__ float score_chain(const T* __restrict__ u, const T* __restrict__ x) {
     float acc = 0.0f;
 #pragma unroll
     for (int s = 0; s < D / 2; ++s) {
@@ -157,7 +162,7 @@ __device__ __forceinline__ unsigned lane_rows(unsigned word, int h) {
 }
 
 // total order of the top-K lists: score descending, then item id ascending (NaN is never better than anything)
-__device__ __forceinline__ bool better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
+__host__ __device__ __forceinline__ bool better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
 
 // first index of [lo, hi) at which pred is false, hi if there is none (pred holds on a prefix of the range)
 template <class I, class P>
@@ -258,7 +263,7 @@ __device__ __forceinline__ const float* offset_plane(const float* adj, int64_t n
 // A(u, p) from s = S(u, p): the expression of TileTerms::apply, for the thresholds (A = false: s itself).  scale / offset:
 // the two planes of adj
 template <bool A>
-__device__ __forceinline__ float adjusted(float s, const float* __restrict__ scale, const float* __restrict__ offset, int64_t p) {
+__host__ __device__ __forceinline__ float adjusted(float s, const float* __restrict__ scale, const float* __restrict__ offset, int64_t p) {
     if constexpr (!A) return s;
     else return __builtin_fmaf(s, scale[p], offset[p]);
 }
@@ -1018,6 +1023,343 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_topk_cand(const T* __restri
     }
 }
 
+// ---- deep lists (sml_topk_deep): top-K up to 1,024 by radix select -----------------------------------------------------------
+//
+// The cost of a list must not grow with k, so nothing is kept sorted during the walks.  Per user: the key of the k-th best
+// eligible score is found by an MSB-first radix select over an order-preserving integer key of the score (four passes of 8
+// bits, each one catalogue walk that counts into 256 bins), one more walk collects everything above that key (and the ties
+// with it that belong to the list), and a bitonic sort per user puts the at most k collected pairs in the top-K order.  The
+// number of launches and walks is fixed by the arguments, never by the data.
+//
+//   k_deep_count    a walk_slice callable: an eligible score whose key agrees with the user's prefix so far adds 1 to bin
+//                   (key >> shift) & 255 of the wave's LDS histogram [256][32] (column = user lane: the 32 lanes of a half hit
+//                   32 banks; the two halves hold other items of the same users and meet only on equal digits, which the LDS
+//                   atomic serialises).  The wave then adds its non-zero bins to the global histogram of its 32 users, layout
+//                   [user group][256][32] so that a wave's adds and the pick's reads are contiguous -- integer atomicAdd.
+//   k_deep_pick     one thread per user: bins from the top, the digit that holds the k-th best extends the prefix, need -=
+//                   the population above it; every bin read is written back 0 for the next pass.  Pass 0's total is n_elig; a
+//                   user with fewer than k eligible items takes them all (need 0, key 0: no eligible key is 0).  After the
+//                   last pass the prefix is K*, the key of the k-th entry, need = k - #{key > K*} and ties = #{key == K*}.
+//   k_deep_collect  phase 0: entries with key > K*, and those with key == K* when ties == need, go to slots of the user's row
+//                   of items / scores handed out by an integer atomic counter (any order: the sort fixes it); the ties a wave
+//                   met in its slice are written per (user, slice).  Phase 1 serves the users with ties > need, who take the
+//                   `need` smallest ids among the ties: slices are ascending id ranges, so a tie's place is the ties of the
+//                   earlier slices plus those earlier in the walk plus a popcount over the tile's tie word (both lane halves'
+//                   rows, ascending); a tie whose place is below need goes to slot k - need + place.  A wave without such
+//                   a user returns before it loads anything.
+//   k_deep_sort     one workgroup per user: the collected pairs, padded to a power of two with (-inf, INT_MAX), sorted in
+//                   LDS under `better` and written over the row with the (-1, -inf) padding.  Ids are distinct, so the order
+//                   is total and the bytes do not depend on the slots the atomics gave.
+
+constexpr int kDeepWaves = 2;              // 32 KB of histogram per wave: 64 KB of dynamic LDS per workgroup
+constexpr int kDeepBins = 256;
+constexpr int kDeepPasses = 4;
+
+// the usual order-preserving integer of an fp32 with the two zeros merged (the order compares floats: -0 == +0, the id decides).
+// No non-NaN score has key 0
+__host__ __device__ __forceinline__ uint32_t deep_key(float a) {
+    const uint32_t b = a == 0.0f ? 0u : __builtin_bit_cast(uint32_t, a);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// bit q: acc[q] belongs to an eligible item (elig) and is not NaN
+__device__ __forceinline__ unsigned deep_live(const f32x16& acc, unsigned elig) {
+    unsigned ok = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) ok |= (unsigned)(acc[q] == acc[q]) << q;
+    return ok & elig;
+}
+
+// per-user state of a call, int32 [kDeepState][n_pad] behind the histogram
+enum { DS_CNT = 0, DS_PREFIX, DS_NEED, DS_TOTAL, DS_TIES, kDeepState };
+
+template <int D, class T, bool F, bool A>
+__device__ __forceinline__ void deep_count_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                                const int64_t* __restrict__ users, int64_t n,
+                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                int slice_tiles, int shift, const int32_t* __restrict__ prefix,
+                                                int32_t* __restrict__ hist) {
+    extern __shared__ float lds[];
+    const LanePos lp = lane_pos(slices, kDeepWaves, n);
+    const int lane = threadIdx.x & 63;
+    unsigned* lh = reinterpret_cast<unsigned*>(lds) + (size_t)lp.wave * kDeepBins * RT;
+    for (int e = lane; e < kDeepBins * RT; e += 64) lh[e] = 0u;
+    __builtin_amdgcn_wave_barrier();
+    const int64_t u = users[lp.rc];
+    // pass 0 (shift 24) has no prefix yet: every key agrees
+    const unsigned pfx = shift < 24 ? (unsigned)prefix[lp.rc] : 0u;
+    const unsigned high = shift < 24 ? ~0u << (shift + 8) : 0u;
+    walk_slice<D, T, F, A>(wu, wi, n_item, u, seen_off, seen_items, allow, adj, lp, slice_tiles, [&](const f32x16& acc, int64_t, unsigned elig) {
+        const unsigned ok = lp.valid ? deep_live(acc, elig) : 0u;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const unsigned key = deep_key(acc[q]);
+            if (((ok >> q) & 1u) && ((key ^ pfx) & high) == 0u) atomicAdd(&lh[((key >> shift) & 255u) * RT + lp.j], 1u);
+        }
+    });
+    __builtin_amdgcn_wave_barrier();
+    // the wave's 32 users are one aligned group of the global histogram: [group][256][32], the LDS image's own layout
+    const int64_t group = (lp.row - lp.j) / RT;
+    if (group * RT < n) {
+        int32_t* gh = hist + group * (kDeepBins * RT);
+        for (int e = lane; e < kDeepBins * RT; e += 64) {
+            const unsigned v = lh[e];
+            if (v) atomicAdd(gh + e, (int32_t)v);
+        }
+    }
+}
+
+template <int D, class T, bool F, bool A>
+__global__ __launch_bounds__(64 * kDeepWaves) void k_deep_count(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                                                const int64_t* __restrict__ users, int64_t n,
+                                                                const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                                const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                                int slice_tiles, int shift, const int32_t* __restrict__ prefix,
+                                                                int32_t* __restrict__ hist) {
+    deep_count_body<D, T, F, A>(wu, wi, n_item, users, n, seen_off, seen_items, allow, adj, slices, slice_tiles, shift, prefix, hist);
+}
+
+// state: [kDeepState][n_pad]
+__global__ __launch_bounds__(256) void k_deep_pick(int32_t* __restrict__ hist, int32_t* __restrict__ state, int64_t n, int64_t n_pad,
+                                                   int k, int shift, int32_t* __restrict__ n_elig) {
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= n) return;
+    int32_t* bins = hist + (x / RT) * (kDeepBins * RT) + (x % RT);
+    const bool first = shift == 24;
+    int need = first ? k : state[DS_NEED * n_pad + x];
+    int cum = 0, chosen = -1, above = 0, pop = 0;
+    for (int dgt = kDeepBins - 1; dgt >= 0; --dgt) {
+        const int c = bins[dgt * RT];
+        bins[dgt * RT] = 0;
+        if (chosen < 0 && need > 0 && cum + c >= need) { chosen = dgt; above = cum; pop = c; }
+        cum += c;
+    }
+    unsigned pfx = first ? 0u : (unsigned)state[DS_PREFIX * n_pad + x];
+    if (first) {
+        state[DS_TOTAL * n_pad + x] = cum;
+        if (n_elig) n_elig[x] = cum;
+    }
+    if (chosen < 0) {                      // fewer than k eligible items (pass 0), or already so: everything is taken
+        pfx = 0u;
+        need = 0;
+        pop = 0;
+    } else {
+        pfx |= (unsigned)chosen << shift;
+        need -= above;
+    }
+    state[DS_PREFIX * n_pad + x] = (int32_t)pfx;
+    state[DS_NEED * n_pad + x] = need;
+    state[DS_TIES * n_pad + x] = pop;      // (the last pass's is the population of K*)
+}
+
+template <int D, class T, bool F, bool A>
+__device__ __forceinline__ void deep_collect_body(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                                  const int64_t* __restrict__ users, int64_t n, int k,
+                                                  const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                  const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                  int slice_tiles, int phase, int32_t* __restrict__ state, int64_t n_pad,
+                                                  int32_t* __restrict__ tie_cnt, int32_t* __restrict__ items, float* __restrict__ scores) {
+    const LanePos lp = lane_pos(slices, kDeepWaves, n);
+    const int h = lp.h;
+    const unsigned kstar = (unsigned)state[DS_PREFIX * n_pad + lp.rc];
+    const int need = state[DS_NEED * n_pad + lp.rc];
+    const int ties = state[DS_TIES * n_pad + lp.rc];
+    const bool by_place = lp.valid && ties != need;        // this user takes the `need` smallest ids among the ties
+    int before = 0;                                        // ties of the earlier slices (phase 1), then of the walk so far
+    if (phase == 1) {
+        bool mine = by_place;
+        if (mine) {
+            for (int s = 0; s < lp.slice && before < need; ++s) before += tie_cnt[lp.row * slices + s];
+            mine = before < need;
+        }
+        if (!__any(mine)) return;
+    }
+    const int64_t u = users[lp.rc];
+    int32_t* const cnt = state + DS_CNT * n_pad + lp.row;
+    const int64_t o = lp.row * k;
+    walk_slice<D, T, F, A>(wu, wi, n_item, u, seen_off, seen_items, allow, adj, lp, slice_tiles, [&](const f32x16& acc, int64_t base, unsigned elig) {
+        const unsigned ok = lp.valid ? deep_live(acc, elig) : 0u;
+        unsigned take = 0, tie = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const unsigned key = deep_key(acc[q]);
+            take |= (unsigned)(key > kstar) << q;
+            tie |= (unsigned)(key == kstar) << q;
+        }
+        take &= ok;
+        tie &= ok;
+        if (phase == 0) {
+            if (!by_place) take |= tie;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                if ((take >> q) & 1u) {
+                    const int slot = atomicAdd(cnt, 1);
+                    if (slot < k) {
+                        items[o + slot] = (int32_t)(base + row_of(q, h));
+                        scores[o + slot] = acc[q];
+                    }
+                }
+            }
+        }
+        if (!__any(by_place && tie != 0)) return;
+        // the tile's tie word over its 32 rows, both lane halves' bits: a tie's place is the number of ties below it
+        unsigned word = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) word |= ((tie >> q) & 1u) << row_of(q, h);
+        word |= (unsigned)__shfl_xor((int)word, 32, 64);
+        if (phase == 1 && by_place) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                if ((tie >> q) & 1u) {
+                    const int r = row_of(q, h);
+                    const int place = before + __popc(word & ((1u << r) - 1u));
+                    if (place < need) {
+                        const int slot = k - need + place;
+                        if (slot >= 0 && slot < k) {
+                            items[o + slot] = (int32_t)(base + r);
+                            scores[o + slot] = acc[q];
+                        }
+                    }
+                }
+            }
+        }
+        if (by_place) before += __popc(word);
+    });
+    // phase 0: an empty slice still writes its count
+    if (phase == 0 && lp.valid && h == 0) tie_cnt[lp.row * slices + lp.slice] = by_place ? before : 0;
+}
+
+template <int D, class T, bool F, bool A>
+__global__ __launch_bounds__(64 * kDeepWaves) void k_deep_collect(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                                                  const int64_t* __restrict__ users, int64_t n, int k,
+                                                                  const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                                  const uint32_t* __restrict__ allow, const float* __restrict__ adj, int slices,
+                                                                  int slice_tiles, int phase, int32_t* __restrict__ state, int64_t n_pad,
+                                                                  int32_t* __restrict__ tie_cnt, int32_t* __restrict__ items,
+                                                                  float* __restrict__ scores) {
+    deep_collect_body<D, T, F, A>(wu, wi, n_item, users, n, k, seen_off, seen_items, allow, adj, slices, slice_tiles, phase, state, n_pad, tie_cnt,
+                                  items, scores);
+}
+
+// one workgroup per user, P = the power of two >= k (<= 1024) pairs in LDS, P / 2 compare-exchanges per step
+__global__ __launch_bounds__(256) void k_deep_sort(const int32_t* __restrict__ state, int64_t n_pad, int k, int P,
+                                                   int32_t* __restrict__ items, float* __restrict__ scores) {
+    __shared__ float l_s[SML_TOPK_DEEP_MAX];
+    __shared__ int32_t l_i[SML_TOPK_DEEP_MAX];
+    const int64_t x = blockIdx.x;
+    const int total = state[DS_TOTAL * n_pad + x];
+    const int m = total < k ? total : k;
+    for (int q = threadIdx.x; q < P; q += blockDim.x) {
+        const bool live = q < m;
+        l_s[q] = live ? scores[x * k + q] : -INFINITY;
+        l_i[q] = live ? items[x * k + q] : INT_MAX;
+    }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < P / 2; t += blockDim.x) {
+                const int a = 2 * t - (t & (stride - 1)), b = a + stride;
+                const float sa = l_s[a], sb = l_s[b];
+                const int ia = l_i[a], ib = l_i[b];
+                // blocks of `size` alternate direction; the last step (size == P) runs best-first throughout
+                const bool swap = (a & size) == 0 ? better(sb, ib, sa, ia) : better(sa, ia, sb, ib);
+                if (swap) { l_s[a] = sb; l_i[a] = ib; l_s[b] = sa; l_i[b] = ia; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int q = threadIdx.x; q < k; q += blockDim.x) {
+        const bool live = q < m;
+        items[x * k + q] = live ? l_i[q] : -1;
+        scores[x * k + q] = live ? l_s[q] : -INFINITY;
+    }
+}
+
+// the grid of a deep call: slices forced (1 .. 256) or left to the planner (0)
+SliceGrid deep_grid(int64_t n, int64_t n_item, int slices) {
+    if (slices <= 0) return plan_grid(n, kDeepWaves, n_item, 2048, 8);
+    const int64_t n_tiles = (n_item + RT - 1) / RT;
+    return {(n + RT * kDeepWaves - 1) / (RT * kDeepWaves), slices, (int)((n_tiles + slices - 1) / slices)};
+}
+
+int64_t deep_pad(int64_t n) { return (n + RT - 1) / RT * RT; }
+
+// The definition as a single-threaded walk over host memory: every item's score by score_chain (and adjusted), the eligible
+// ones kept as the k best so far in a binary heap under `better` (worst on top), then written best first.
+template <int D, class T>
+void deep_host_walk(const T* wu, const T* wi, int64_t n_item, const int64_t* users, int64_t n, int k, const int64_t* seen_off,
+                    const int32_t* seen_items, const uint32_t* allow, const float* adj, int32_t* items, float* scores, int32_t* n_elig) {
+    const float* offset = adj ? adj + (n_item + RT - 1) / RT * RT : nullptr;
+    float hs[SML_TOPK_DEEP_MAX];
+    int32_t hi[SML_TOPK_DEEP_MAX];
+    // worse(a, b): entry a orders after entry b
+    const auto worse = [&](int a, int b) { return better(hs[b], hi[b], hs[a], hi[a]); };
+    for (int64_t x = 0; x < n; ++x) {
+        const int64_t u = users[x];
+        int64_t sp = seen_off ? seen_off[u] : 0;
+        const int64_t se = seen_off ? seen_off[u + 1] : 0;
+        int m = 0, ne = 0;
+        for (int64_t i = 0; i < n_item; ++i) {
+            while (sp < se && seen_items[sp] < i) ++sp;
+            if (sp < se && seen_items[sp] == i) continue;
+            if (allow && !((allow[i >> 5] >> (i & 31)) & 1u)) continue;
+            float s = score_chain<D, T>(wu + u * D, wi + i * D);
+            if (adj) s = adjusted<true>(s, adj, offset, i);
+            if (s != s) continue;
+            ++ne;
+            if (m == k) {
+                if (!better(s, (int)i, hs[0], hi[0])) continue;
+                // replace the worst entry and sift down
+                int p = 0;
+                for (;;) {
+                    int c = 2 * p + 1;
+                    if (c >= m) break;
+                    if (c + 1 < m && worse(c + 1, c)) ++c;
+                    if (!better(s, (int)i, hs[c], hi[c])) break;
+                    hs[p] = hs[c];
+                    hi[p] = hi[c];
+                    p = c;
+                }
+                hs[p] = s;
+                hi[p] = (int32_t)i;
+            } else {
+                int p = m++;
+                while (p > 0) {
+                    const int q = (p - 1) / 2;
+                    if (!better(hs[q], hi[q], s, (int)i)) break;      // the parent is already worse
+                    hs[p] = hs[q];
+                    hi[p] = hi[q];
+                    p = q;
+                }
+                hs[p] = s;
+                hi[p] = (int32_t)i;
+            }
+        }
+        for (int q = m; q < k; ++q) { items[x * k + q] = -1; scores[x * k + q] = -INFINITY; }
+        // pop the worst into the last live slot
+        for (int live = m; live > 0; --live) {
+            items[x * k + live - 1] = hi[0];
+            scores[x * k + live - 1] = hs[0];
+            const float s = hs[live - 1];
+            const int32_t i = hi[live - 1];
+            int p = 0;
+            for (;;) {
+                int c = 2 * p + 1;
+                if (c >= live - 1) break;
+                if (c + 1 < live - 1 && worse(c + 1, c)) ++c;
+                if (!better(s, i, hs[c], hi[c])) break;
+                hs[p] = hs[c];
+                hi[p] = hi[c];
+                p = c;
+            }
+            hs[p] = s;
+            hi[p] = i;
+        }
+        if (n_elig) n_elig[x] = ne;
+    }
+}
+
 }  // namespace
 
 bool sml_retrieval_supports(int d, int elem_bytes) {
@@ -1161,4 +1503,57 @@ hipError_t sml_launch_item_adjust_cosine(int d, int elem_bytes, const void* wi, 
     }))
         return hipErrorInvalidValue;
     return hipGetLastError();
+}
+
+// scratch of sml_topk_deep: the histogram int32 [n_pad / 32][256][32], the per-user state int32 [kDeepState][n_pad] (both zeroed
+// by the call), the ties per (user, slice) int32 [n][slices]
+int64_t sml_topk_deep_scratch_size(int64_t n, int64_t n_item, int slices) {
+    const int64_t n_pad = deep_pad(n);
+    const int64_t bytes = n_pad * (kDeepBins + kDeepState) * 4 + n * deep_grid(n, n_item, slices).slices * 4;
+    return (bytes + 255) / 256 * 256;
+}
+
+hipError_t sml_launch_topk_deep(const SmlCatalogue& c, const int64_t* users, int64_t n, int k, int slices, void* scratch, int32_t* items,
+                                float* scores, int32_t* n_elig, hipStream_t st) {
+    const SliceGrid g = deep_grid(n, c.n_item, slices);
+    const int64_t n_pad = deep_pad(n);
+    int32_t* hist = static_cast<int32_t*>(scratch);
+    int32_t* state = hist + n_pad * kDeepBins;
+    int32_t* tie_cnt = state + n_pad * kDeepState;
+    hipError_t e = hipMemsetAsync(hist, 0, n_pad * (kDeepBins + kDeepState) * sizeof(int32_t), st);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)(g.groups * g.slices)), block(64 * kDeepWaves);
+    const size_t lds = (size_t)kDeepWaves * kDeepBins * RT * 4;
+    const dim3 ugrid((unsigned)((n + 255) / 256)), ublock(256);
+    for (int pass = 0; pass < kDeepPasses; ++pass) {
+        const int shift = 24 - 8 * pass;
+        if (!with_width(c, [&](auto dd, auto ff, auto aa, auto* tu, auto* ti) {
+            k_deep_count<dd(), elem_t<decltype(tu)>, ff(), aa()><<<grid, block, lds, st>>>(
+                tu, ti, c.n_item, users, n, c.seen_off, c.seen_items, c.allow, c.adj, g.slices, g.slice_tiles, shift, state + DS_PREFIX * n_pad, hist);
+        }))
+            return hipErrorInvalidValue;
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_deep_pick<<<ugrid, ublock, 0, st>>>(hist, state, n, n_pad, k, shift, n_elig);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    for (int phase = 0; phase < 2; ++phase) {
+        if (!with_width(c, [&](auto dd, auto ff, auto aa, auto* tu, auto* ti) {
+            k_deep_collect<dd(), elem_t<decltype(tu)>, ff(), aa()><<<grid, block, 0, st>>>(
+                tu, ti, c.n_item, users, n, k, c.seen_off, c.seen_items, c.allow, c.adj, g.slices, g.slice_tiles, phase, state, n_pad, tie_cnt, items,
+                scores);
+        }))
+            return hipErrorInvalidValue;
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    int P = 1;
+    while (P < k) P <<= 1;
+    const int threads = P / 2 < 64 ? 64 : (P / 2 > 256 ? 256 : P / 2);
+    k_deep_sort<<<dim3((unsigned)n), dim3(threads), 0, st>>>(state, n_pad, k, P, items, scores);
+    return hipGetLastError();
+}
+
+bool sml_topk_host_walk(const SmlCatalogue& c, const int64_t* users, int64_t n, int k, int32_t* items, float* scores, int32_t* n_elig) {
+    return with_width(c, [&](auto dd, auto, auto, auto* tu, auto* ti) {
+        deep_host_walk<dd(), elem_t<decltype(tu)>>(tu, ti, c.n_item, users, n, k, c.seen_off, c.seen_items, c.allow, c.adj, items, scores, n_elig);
+    });
 }

@@ -441,6 +441,14 @@ struct SmlCandidates {
 // one wavefront per list, no scratch; max_workgroups > 0 caps the grid (lists are walked grid-stride)
 hipError_t sml_launch_topk_candidates(const SmlCatalogue& c, const int64_t* users, int64_t n, const SmlCandidates& l, int k,
                                       int max_workgroups, int32_t* items, float* scores, int32_t* n_elig, hipStream_t st);
+// deep lists (sml_topk_deep, include/sml_hip.h): 1 <= k <= 1024 by a per-user radix select, a fixed number of catalogue walks
+// whatever k is; slices 0 = the planner's, 1 .. 256 forced.  scratch: sml_topk_deep_scratch_size bytes.  No allocation, copy to
+// the host or synchronise.  sml_topk_host_walk: the same definition as a single-threaded walk over host memory (c holds host
+// pointers); false: no walk for this (d, elem_bytes) pair
+int64_t sml_topk_deep_scratch_size(int64_t n, int64_t n_item, int slices);
+hipError_t sml_launch_topk_deep(const SmlCatalogue& c, const int64_t* users, int64_t n, int k, int slices, void* scratch, int32_t* items,
+                                float* scores, int32_t* n_elig, hipStream_t st);
+bool sml_topk_host_walk(const SmlCatalogue& c, const int64_t* users, int64_t n, int k, int32_t* items, float* scores, int32_t* n_elig);
 int64_t sml_user_rank_scratch_size(int64_t n_pos);
 hipError_t sml_launch_user_rank(const SmlCatalogue& c, const int64_t* users, int64_t n, const int64_t* pos_off, const int32_t* pos_items,
                                 int64_t n_pos, void* scratch, int32_t* above, int32_t* pos, hipStream_t st);

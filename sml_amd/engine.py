@@ -948,7 +948,12 @@ class HipEngine(object):
         """(int64 items [n, k], float32 scores [n, k]): each user's k best items not in Seen(u), score descending then id
         ascending; missing slots are (-1, -inf) (include/sml_hip.h, sml_topk_items / sml_topk_items_f16: fp32 or fp16 tables).
         allow: an item filter (_allow); only allowed items enter the lists (sml_topk_items_filtered).  adjust: per-item score
-        terms (_adjust); order and returned scores are then A(u, i) (sml_topk_items_adjusted)."""
+        terms (_adjust); order and returned scores are then A(u, i) (sml_topk_items_adjusted).  1 <= k <= 128.  A call with
+        sml_amd.retrieval.DEEP_FROM <= k <= 128 is handed to topk_deep, which returns the same bytes from the radix select:
+        its scratch is topk_deep's (about 1 KB per user) and an argument error then names sml_topk_deep."""
+        from .retrieval import DEEP_FROM
+        if DEEP_FROM <= int(k) <= 128:       # the same bytes from the radix select (sml_amd.retrieval.DEEP_FROM says from which k)
+            return self.topk_deep(user_tab, item_tab, users, int(k), seen, allow, adjust)[:2]
         wu, wi, sfx = self._retrieval_tables(user_tab, item_tab)
         allow = self._allow(allow, wi.shape[0])
         call, name, eb, flt = self._retrieval_call("sml_topk_items", wi, sfx, allow, self._adjust(adjust, wi))
@@ -971,6 +976,38 @@ class HipEngine(object):
             check(call(self._ctx, _ptr(wu), _ptr(wi), *eb, wi.shape[0], _ptr(users[c0:]), m, k, _ptr(off), _ptr(seen_items), *flt,
                        _ptr(scratch), _ptr(items[c0:]), _ptr(scores[c0:]), self._stream()), name)
         return items.long(), scores
+
+    def topk_deep(self, user_tab, item_tab, users, k, seen=None, allow=None, adjust=None, slices=0):
+        """(int64 items [n, k], float32 scores [n, k], int32 n_elig [n]): topk_items' lists for 1 <= k <= 1024, selected by
+        radix instead of kept sorted -- a fixed number of catalogue walks whatever k is (include/sml_hip.h, DEEP LISTS;
+        sml_topk_deep).  For k <= 128 items and scores equal topk_items' byte for byte; n_elig counts each user's eligible
+        items.  seen, allow and adjust as in topk_items (adjust None: the bare score).  slices: 0 leaves the grid to the
+        call, 1 .. 256 forces the number of item slices (the bytes do not depend on it).  The users are walked in chunks
+        whose scratch (about 1 KB per user) fits TOPK_SCRATCH_BYTES."""
+        from .retrieval import deep_args
+        wu, wi, _ = self._retrieval_tables(user_tab, item_tab)
+        allow = self._allow(allow, wi.shape[0])
+        adj = self._adjust(adjust, wi)
+        users = self._dev(users, torch.int64).reshape(-1)
+        n, k, slices = users.shape[0], deep_args(k), int(slices)
+        off, seen_items = self._seen(seen)
+        items = torch.empty(n, k, device=self.device, dtype=torch.int32)
+        scores = torch.empty(n, k, device=self.device, dtype=torch.float32)
+        n_elig = torch.empty(n, device=self.device, dtype=torch.int32)
+        total = int(self.lib.sml_topk_deep_scratch_bytes(self._ctx, n, k, wi.shape[0], slices))
+        if total < 0:
+            check(-1, "sml_topk_deep_scratch_bytes")
+        chunk = n if total <= self.TOPK_SCRATCH_BYTES else max(1, int(n * self.TOPK_SCRATCH_BYTES // total))
+        scratch = None
+        for c0 in range(0, max(n, 1), max(chunk, 1)):        # (n == 0: one call, which checks the arguments and launches nothing)
+            m = min(chunk, n - c0)
+            nbytes = int(self.lib.sml_topk_deep_scratch_bytes(self._ctx, m, k, wi.shape[0], slices))
+            if m and (scratch is None or scratch.numel() < nbytes):
+                scratch = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+            check(self.lib.sml_topk_deep(self._ctx, _ptr(wu), _ptr(wi), wi.element_size(), wi.shape[0], _ptr(users[c0:]), m, k, _ptr(off),
+                                         _ptr(seen_items), _ptr(allow), _ptr(adj), slices, _ptr(scratch), _ptr(items[c0:]),
+                                         _ptr(scores[c0:]), _ptr(n_elig[c0:]), self._stream()), "sml_topk_deep")
+        return items.long(), scores, n_elig
 
     def topk_candidates(self, user_tab, item_tab, users, candidates, k, seen=None, allow=None, adjust=None, max_workgroups=0):
         """(int64 items [n, k], float32 scores [n, k], int32 n_elig [n]): for each user the k best DISTINCT eligible ids of

@@ -146,6 +146,34 @@ def test_model_users(model, test_pairs, seen=None, topK=(20, 10, 5), old_user=No
     return user_metrics(out, old_user, old_item)
 
 
+def recall_curve(model, held_out, ks, exclude=None, items=None, score=None):
+    """[recall@K for K in ks]: the mean over the users with a non-empty held-out set T(u) (retrieval.nonempty_users) of
+    |first K of the user's list AND T(u)| / |T(u)|, the lists being MFbasemode.recommend(users, max(ks)) -- one call, up to
+    K = 1,024 (HipEngine.topk_deep above 128).  held_out: a sml_amd.retrieval.SeenItems (retrieval.held_out) or a (off, items)
+    CSR over all users; exclude, items and score as recommend takes them.  At any K the value is the recall
+    test_model_users reports at that K: a held-out item hits when its place in the list is below K, and an item that is
+    excluded or filtered out is in no list."""
+    from .retrieval import deep_args, nonempty_users
+    ks = [deep_args(k) for k in ks]
+    if not ks:
+        return []
+    users, pos_off, pos_items = nonempty_users(held_out)
+    if len(users) == 0:
+        return [0.0 for _ in ks]
+    model.eval()
+    n_item = int(model.item_laten.weight.shape[0])
+    extra = dict(([("items", items)] if items is not None else []) + ([("score", score)] if score is not None else []))
+    lists = model.recommend(torch.from_numpy(users), max(ks), exclude=exclude, **extra)[0].cpu().numpy()
+    m = np.diff(pos_off)
+    row = np.arange(len(users), dtype=np.int64)
+    held = np.repeat(row, m) * n_item + pos_items.astype(np.int64)             # ascending: users ascend, items ascend inside a user
+    keys = row[:, None] * n_item + lists
+    at = np.minimum(np.searchsorted(held, keys), len(held) - 1)
+    hit = (lists >= 0) & (held[at] == keys)
+    hits = np.concatenate([np.zeros((len(users), 1), np.int64), np.cumsum(hit, axis=1)], axis=1)
+    return [float(np.mean(hits[:, k].astype(np.float64) / m.astype(np.float64))) for k in ks]
+
+
 def intra_list_similarity(model, lists, metric="cosine"):
     """float32 [n]: the mean pairwise similarity of each list's items -- the number that shows what
     MFbasemode.recommend(diversify=) did.  lists: item ids [n, m <= 128], padded with -1 (ids outside the catalogue and

