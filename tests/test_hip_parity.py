@@ -1112,23 +1112,26 @@ def test_library_switches_are_read_per_call_not_per_process(monkeypatch, capfd):
 
 
 
-def test_evaluation_with_its_table_sized_forward_queued_on_the_side_stream():
+@pytest.mark.parametrize("d,U,I", [(32, 3000, 2500), (32, 9000, 8300), (64, 9000, 8300)])
+def test_evaluation_with_its_table_sized_forward_queued_on_the_side_stream(d, U, I):
     """HipEngine.eval_submit_transferred (round 4): the ranks under the tables updata() WOULD write -- forward and rank pass
     queued on the evaluation stream over snapshots of the four input tables and theta -- equal updata() + eval_ranks in place,
     bit for bit; the caller's tables are not written, and inputs overwritten right after the call (more submissions than the
-    ring has slots) do not reach the queued work."""
-    eng = engine(32, 256)
-    U, I, n = 3000, 2500, 4000
+    ring has slots) do not reach the queued work.  Tables above 8192 rows: the evaluation stream's own kernels
+    (k_transfer_fwd_bx3<32,true>, k_side_transfer_fwd<64>), which the timing classes count."""
+    eng = engine(d, 256)
+    n = 4000
     g = torch.Generator(device=DEV).manual_seed(8)
-    net = make_transfer(32, device=DEV)
+    net = make_transfer(d, device=DEV)
     rows = torch.cat([torch.randint(0, U, (n, 1), device=DEV, generator=g), torch.randint(0, I, (n, 101), device=DEV, generator=g)], 1)
-    tabs = lambda: [torch.randn(r, 32, device=DEV, generator=g) * 0.3 for r in (U, U, I, I)]
+    tabs = lambda: [torch.randn(r, d, device=DEV, generator=g) * 0.3 for r in (U, U, I, I)]
     theta = eng.adopt(net)
+    eng.profile(True)
     want, handles = [], []
     with eng.partition():
         for k in range(eng.SNAPSHOTS + 2):
             lu, hu, li, hi = tabs()
-            wu, wi = torch.zeros(U, 32, device=DEV), torch.zeros(I, 32, device=DEV)
+            wu, wi = torch.zeros(U, d, device=DEV), torch.zeros(I, d, device=DEV)
             eng.updata(net, lu, hu, li, hi, wu, wi)
             want.append(eng.eval_ranks(wu, wi, rows).clone())
             keep_u, keep_i = wu.clone(), wi.clone()
@@ -1144,6 +1147,10 @@ def test_evaluation_with_its_table_sized_forward_queued_on_the_side_stream():
     for w, h in zip(want, handles):
         assert torch.equal(w, h["ranks"])
     assert len({int(w.sum()) for w in want}) > 1                                  # (the evaluations did differ from one another)
+    side = {k: v[0] for k, v in eng.profile_read("side").items()}
+    eng.profile(False)
+    assert side.get("k_side_transfer_fwd", 0) == (2 * len(handles) if min(U, I) > 8192 else 0), side
+    assert side.get("k_side_transfer_fwd", 0) + side.get("k_transfer_fwd", 0) == 2 * len(handles), side
 
 
 def test_bare_step_hot_rows_vs_oracle():
