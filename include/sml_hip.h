@@ -635,6 +635,71 @@ int sml_topk_candidates(sml_ctx* ctx, const void* w_user, const void* w_item, in
                         int k, const int64_t* seen_off, const int32_t* seen_items,
                         const uint32_t* allow, const float* adj, int max_workgroups,
                         int32_t* items, float* scores, int32_t* n_elig, void* stream);
+/* ---- CLUSTERED INDEX: an inverted-file (IVF) index over the item table -- k-means lists, and a query that scores only the
+ * members of the lists nearest the user instead of the whole catalogue.  The approximation lives ONLY in which lists are
+ * probed: everything the calls below return is an exact, byte-defined function of (tables, lists, probes).
+ * An index over an item table [n_item, d] of element type T (fp32: d = 32 / 64; fp16: d = 32 / 64 / 128; any other pair is
+ * refused) is three device arrays:
+ *   centroids   T [n_list, d], in the table's own element type, so that sml_topk_items[_adjusted][_f16] takes it as an item
+ *               table: "assign each item to its nearest centroid" and "choose each user's lists" are that call;
+ *   list_off    int64 [n_list + 1], from 0, non-decreasing, ending at n_item;
+ *   list_items  int32 [n_item], a partition of [0, n_item), ids ascending inside each list (what sml_iset_build writes for
+ *               the rows (list, item)).
+ * The index holds no rows and no scores: search reads the CURRENT w_item, so a stale index can cost recall but can never
+ * return a wrong score.
+ * SEARCH.  probes int32 [n, nprobe], 1 <= nprobe <= 128: the lists of users[x] are probes[x][0], probes[x][1], ...  A probe
+ * outside [0, n_list) is padding and forms no address; a list probed twice is walked twice.  1 <= k <= 128.  Seen, allow, adj
+ * (NULL accepted: the bare score, no fmaf), eligibility, the order, the (-1, -inf) padding, the repeat rule and n_elig ("the
+ * number of eligible entries, repeats counted as they occur") are exactly those of sml_topk_candidates.
+ * Defining identity: row x equals, byte for byte in items, scores and n_elig, row x of sml_topk_candidates with the ragged list
+ * "the members of probes[x][0], then of probes[x][1], ...".  Hence, through that call's own identity, row x also equals
+ * sml_topk_items_filtered for that user alone under the filter (allow AND bitmap(union of the probed lists)).  Consequences:
+ *   - probing every list once returns the bytes of sml_topk_items[_filtered|_adjusted][_f16] on the same arguments;
+ *   - at d = 32 / 64 a call on fp16 tables equals the call on fp32 copies of them bit for bit;
+ *   - the bytes are the same for every max_workgroups (0 leaves the grid to the call, a positive value caps it; one wavefront
+ *     serves one user, users are walked grid-stride).
+ * No scratch, no allocation, no copy to the host, no synchronise.  Refused (sml_last_error): what sml_topk_candidates refuses
+ * (exactly one of seen_off / seen_items NULL; a (d, elem_bytes) pair the kernels do not exist for; k out of range;
+ * max_workgroups < 0; a misaligned adj or table; an output that overlaps an input or another output as far as the pointers and
+ * the sizes known to the call show it), and nprobe outside [1, 128] and n_list <= 0.  n == 0 is a valid call that launches
+ * nothing.  Indices (users, list_off, list_items) are trusted.
+ * sml_host_ivf_search: the same definition as a single-threaded walk over HOST memory (the host and the device share the text
+ * of the score chain); d is the caller's (no context), and nothing has to be aligned.
+ * CENTROID UPDATE.  For list c with members m_0 < m_1 < ... (len of them) and every dim s:
+ *   acc = 0.0 as a double; acc += (double)x[m_j][s] for j ascending (the widening is exact);
+ *   out[c][s] = (T)(float)(acc / (double)len) -- the fp64 division correctly rounded, each conversion to nearest even.
+ * An empty list copies centroids_in[c].  centroids_in and centroids_out may be the same pointer (any other overlap is refused).
+ * The order of the additions is part of the definition, so the bytes do not depend on the launch; there are no floating-point
+ * atomics.  sml_host_ivf_centroids: the host walk of the same text, compiled so that nothing is contracted or reassociated.
+ * Refused: a (d, elem_bytes) pair outside the family, n_item outside (0, 2^31), n_list <= 0, a null pointer, an output that
+ * overlaps the table or the lists.
+ * BUILD (sml_amd.retrieval.ItemIndex; plumbing over existing calls).  Initialise: n_list distinct item rows chosen on the host
+ * from a seed.  Per iteration -- assign: item i joins the list of its best centroid, by sml_topk_items[_adjusted] with the item
+ * table as the user table and k = 1 (metric "dot": the centroid maximising S(x_i, centroid_c); "cosine", the default: the
+ * adjusted score fmaf(S, 1 / ||centroid_c||, +0) through sml_item_adjust_cosine on the centroid table; ties go to the lower list
+ * id; an item whose every centroid score is NaN joins list 0, so the lists stay a partition); lists: sml_iset_build on the rows
+ * (assign[i], i); update: sml_ivf_centroids.  Probe at query time: sml_topk_items[_adjusted] of the users against the centroids
+ * with k = nprobe and the same metric's table, narrowed to int32; Seen and item filters do not apply to centroids.  The same
+ * seed, table and arguments give the same index bytes on every run.
+ * Not measured: trained (non-random) SML tables, and recall across periods under a refreshed index. */
+int sml_ivf_search(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item,
+                   const int64_t* users, int64_t n,
+                   const int64_t* list_off, const int32_t* list_items, int n_list,
+                   const int32_t* probes, int nprobe, int k,
+                   const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                   int max_workgroups, int32_t* items, float* scores, int32_t* n_elig, void* stream);
+int sml_host_ivf_search(const void* w_user, const void* w_item, int elem_bytes, int d, int64_t n_item,
+                        const int64_t* users, int64_t n,
+                        const int64_t* list_off, const int32_t* list_items, int n_list,
+                        const int32_t* probes, int nprobe, int k,
+                        const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj,
+                        int32_t* items, float* scores, int32_t* n_elig);
+int sml_ivf_centroids(sml_ctx* ctx, const void* w_item, int elem_bytes, int64_t n_item,
+                      const int64_t* list_off, const int32_t* list_items, int n_list,
+                      const void* centroids_in, void* centroids_out, void* stream);
+int sml_host_ivf_centroids(const void* w_item, int elem_bytes, int d, int64_t n_item,
+                           const int64_t* list_off, const int32_t* list_items, int n_list,
+                           const void* centroids_in, void* centroids_out);
 /* ---- DEEP LISTS: candidate generation at depth -- lists of up to 1,024 items per user over the whole catalogue, for a
  * downstream re-ranker, a recall@K curve or a pool.  sml_topk_items keeps a sorted list per (user, slice) and its cost grows
  * with k; sml_topk_deep selects by radix: a fixed number of catalogue walks (four counting passes over the order-preserving

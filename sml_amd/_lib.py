@@ -142,6 +142,14 @@ SIGNATURES = {
     "sml_topk_candidates": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, c_void, ctypes.c_int,
                                            c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_void, c_void, c_void, c_void,
                                            ctypes.c_int, c_void, c_void, c_void, c_void]),
+    "sml_ivf_search": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void, ctypes.c_int,
+                                      c_void, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void, c_void, ctypes.c_int, c_void, c_void, c_void,
+                                      c_void]),
+    "sml_host_ivf_search": (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, c_void, c_void,
+                                           ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void, c_void, c_void, c_void,
+                                           c_void]),
+    "sml_ivf_centroids": (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, c_void, ctypes.c_int, c_void, c_void, c_void]),
+    "sml_host_ivf_centroids": (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_void, c_void, ctypes.c_int, c_void, c_void]),
     "sml_topk_deep_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
     "sml_topk_deep": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
                                      c_void, c_void, ctypes.c_int, c_void, c_void, c_void, c_void, c_void]),

@@ -1998,6 +1998,107 @@ int sml_topk_candidates(sml_ctx* ctx, const void* w_user, const void* w_item, in
     return SML_OK;
 }
 
+// clustered index: what sml_ivf_search and sml_host_ivf_search refuse alike (NULL: nothing), in sml_topk_candidates' order.  The
+// tables, the lists and Seen are of unknown extent: they count from their first entry only
+static const char* ivf_search_refusal(int d, int elem_bytes, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users,
+                                      int64_t n, const int64_t* list_off, const int32_t* list_items, int n_list, const int32_t* probes,
+                                      int nprobe, int k, const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow,
+                                      const float* adj, int max_workgroups, const int32_t* items, const float* scores, const int32_t* n_elig) {
+    if (!elem_ok(elem_bytes)) return "bad argument (elem_bytes must be 4 or 2)";
+    if (nprobe < 1 || nprobe > 128) return "bad argument (1 <= nprobe <= 128)";
+    if (n_list <= 0) return "bad argument (n_list must be positive)";
+    if (!sml_retrieval_supports(d, elem_bytes) || n_item <= 0 || n_item >= ((int64_t)1 << 31) || (!seen_off) != (!seen_items) || k < 1 ||
+        k > 128 || n < 0 || max_workgroups < 0)
+        return "bad argument (d must be 32/64, or 128 for fp16 tables; 1 <= k <= 128, 0 < n_item < 2^31, n >= 0, max_workgroups >= 0, seen_off and seen_items both or neither)";
+    if (n == 0) return nullptr;
+    if (!w_user || !w_item || !users || !list_off || !list_items || !probes || !items || !scores) return "null argument";
+    const int64_t out_bytes = 4 * n * (int64_t)k;
+    const int64_t n_pad = sml_item_adjust_pad(n_item);
+    const struct { const void* p; int64_t bytes; } in[] = {
+        {users, 8 * n}, {list_off, 8 * ((int64_t)n_list + 1)}, {list_items, 4}, {probes, 4 * n * (int64_t)nprobe},
+        {w_user, (int64_t)d * elem_bytes}, {w_item, n_item * d * elem_bytes}, {seen_off, 8}, {seen_items, 4}, {allow, n_pad / 8},
+        {adj, 8 * n_pad}};
+    const struct { const void* p; int64_t bytes; } out[] = {{items, out_bytes}, {scores, out_bytes}, {n_elig, 4 * n}};
+    for (const auto& o : out)
+        for (const auto& i : in)
+            if (iset_overlap(o.p, o.bytes, i.p, i.bytes)) return "an output overlaps an input";
+    if (iset_overlap(items, out_bytes, scores, out_bytes) || iset_overlap(items, out_bytes, n_elig, 4 * n) ||
+        iset_overlap(scores, out_bytes, n_elig, 4 * n))
+        return "the outputs overlap each other";
+    return nullptr;
+}
+
+int sml_ivf_search(sml_ctx* ctx, const void* w_user, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* users, int64_t n,
+                   const int64_t* list_off, const int32_t* list_items, int n_list, const int32_t* probes, int nprobe, int k,
+                   const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj, int max_workgroups,
+                   int32_t* items, float* scores, int32_t* n_elig, void* stream) {
+    const char* what = "sml_ivf_search";
+    if (!ctx) return fail(SML_EINVAL, what, "null argument");
+    if (adj && ((uintptr_t)adj & 15)) return fail(SML_EINVAL, what, "adj must be 16-byte aligned");
+    if (const char* why = ivf_search_refusal(ctx->d, elem_bytes, w_user, w_item, n_item, users, n, list_off, list_items, n_list, probes, nprobe, k,
+                                             seen_off, seen_items, allow, adj, max_workgroups, items, scores, n_elig))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    if (((uintptr_t)w_user | (uintptr_t)w_item) & 15) return fail(SML_EINVAL, what, "the tables must be 16-byte aligned");
+    const SmlCatalogue c = {ctx->d, elem_bytes, w_user, w_item, n_item, seen_off, seen_items, allow, adj};
+    const SmlIvfLists l = {list_off, list_items, n_list, probes, nprobe};
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_ivf_search(c, users, n, l, k, max_workgroups, items, scores, n_elig, st)));
+    return SML_OK;
+}
+
+int sml_host_ivf_search(const void* w_user, const void* w_item, int elem_bytes, int d, int64_t n_item, const int64_t* users, int64_t n,
+                        const int64_t* list_off, const int32_t* list_items, int n_list, const int32_t* probes, int nprobe, int k,
+                        const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, const float* adj, int32_t* items,
+                        float* scores, int32_t* n_elig) {
+    const char* what = "sml_host_ivf_search";
+    if (const char* why = ivf_search_refusal(d, elem_bytes, w_user, w_item, n_item, users, n, list_off, list_items, n_list, probes, nprobe, k,
+                                             seen_off, seen_items, allow, adj, 0, items, scores, n_elig))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    const SmlCatalogue c = {d, elem_bytes, w_user, w_item, n_item, seen_off, seen_items, allow, adj};
+    const SmlIvfLists l = {list_off, list_items, n_list, probes, nprobe};
+    if (!sml_ivf_host_walk(c, users, n, l, k, items, scores, n_elig)) return fail(SML_EINVAL, what, "no walk for this (d, elem_bytes) pair");
+    return SML_OK;
+}
+
+// the centroid update: what the device call and the host walk refuse alike (NULL: nothing).  centroids_in == centroids_out is the
+// in-place call; any other overlap of the two, or of the output with the table or the lists, is refused
+static const char* ivf_centroids_refusal(int d, int elem_bytes, const void* w_item, int64_t n_item, const int64_t* list_off,
+                                         const int32_t* list_items, int n_list, const void* cin, const void* cout) {
+    if (!elem_ok(elem_bytes)) return "bad argument (elem_bytes must be 4 or 2)";
+    if (!sml_retrieval_supports(d, elem_bytes) || n_item <= 0 || n_item >= ((int64_t)1 << 31) || n_list <= 0)
+        return "bad argument (d must be 32/64, or 128 for fp16 tables; 0 < n_item < 2^31, n_list > 0)";
+    if (!w_item || !list_off || !list_items || !cin || !cout) return "null argument";
+    const int64_t cb = (int64_t)n_list * d * elem_bytes;
+    if (cin != cout && iset_overlap(cin, cb, cout, cb)) return "centroids_in and centroids_out overlap without being the same array";
+    if (iset_overlap(cout, cb, w_item, n_item * d * elem_bytes) || iset_overlap(cout, cb, list_off, 8 * ((int64_t)n_list + 1)) ||
+        iset_overlap(cout, cb, list_items, 4 * n_item))
+        return "an output overlaps an input";
+    return nullptr;
+}
+
+int sml_ivf_centroids(sml_ctx* ctx, const void* w_item, int elem_bytes, int64_t n_item, const int64_t* list_off, const int32_t* list_items,
+                      int n_list, const void* centroids_in, void* centroids_out, void* stream) {
+    const char* what = "sml_ivf_centroids";
+    if (!ctx) return fail(SML_EINVAL, what, "null argument");
+    if (const char* why = ivf_centroids_refusal(ctx->d, elem_bytes, w_item, n_item, list_off, list_items, n_list, centroids_in, centroids_out))
+        return fail(SML_EINVAL, what, why);
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_ivf_centroids(ctx->d, elem_bytes, w_item, list_off, list_items, n_list, centroids_in, centroids_out, st)));
+    return SML_OK;
+}
+
+int sml_host_ivf_centroids(const void* w_item, int elem_bytes, int d, int64_t n_item, const int64_t* list_off, const int32_t* list_items,
+                           int n_list, const void* centroids_in, void* centroids_out) {
+    const char* what = "sml_host_ivf_centroids";
+    if (const char* why = ivf_centroids_refusal(d, elem_bytes, w_item, n_item, list_off, list_items, n_list, centroids_in, centroids_out))
+        return fail(SML_EINVAL, what, why);
+    if (!sml_ivf_centroids_host_walk(d, elem_bytes, w_item, list_off, list_items, n_list, centroids_in, centroids_out))
+        return fail(SML_EINVAL, what, "no walk for this (d, elem_bytes) pair");
+    return SML_OK;
+}
+
 // deep lists: what sml_topk_deep and sml_host_topk_items refuse alike (NULL: nothing).  The tables' heights are unknown: they
 // count from their first row only
 static const char* deep_refusal(int d, int elem_bytes, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,

@@ -78,6 +78,11 @@
 // score_chain on the VALU, the K best in the wave's LDS.  It shares score_chain, better, adjusted, offset_plane and
 // lower_bound with the kernels above and changes none of them.
 //
+// Clustered index (sml_ivf_search): k_ivf_search<D, T>, beside k_topk_cand, is that kernel with another source of candidates --
+// the members of the lists a user probes, walked as one virtual sequence through cumulative lengths in the wave's LDS -- and
+// uses FullRow, score_chain, adjusted, better and cand_insert unchanged; ivf_host_walk is the same definition on the host
+// (sml_host_ivf_search).  The centroid update of the index lives in ivf.hip.
+//
 // Deep lists (sml_topk_deep, 1 <= k <= 1,024): k_deep_count / k_deep_pick / k_deep_collect / k_deep_sort behind it select each
 // user's k best by radix over an integer key of the score -- walk_slice callables that keep nothing sorted, so the cost is a
 // fixed number of walks whatever k is -- and deep_host_walk is the same definition on the host (sml_host_topk_items).  For
@@ -1023,6 +1028,146 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_topk_cand(const T* __restri
     }
 }
 
+// ---- clustered index (sml_ivf_search) ------------------------------------------------------------------------------------
+
+constexpr int kIvfMaxProbe = 128;  // probes per user: two per lane
+
+// inclusive sum over the wave's lanes, in lane order (integers: exact whatever the order)
+__device__ __forceinline__ long long wave_scan(long long v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long t = __shfl_up(v, d);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+// k_topk_cand with another source of candidates: the members of the lists a user probes, in probe order, as ONE virtual
+// sequence -- the lists are short and uneven, and a wave that walked them one by one would run most rounds partly empty.
+// Per user: lane l reads probes l and l + 64 (a probe outside [0, n_list) is padding: length 0, no address is formed) and both
+// ends of their lists; a wave scan leaves the inclusive cumulative lengths and the list starts in the wave's LDS; then, in
+// rounds of 64 (kCandRounds in flight), lane l maps virtual index e to (probe j, e - cum[j - 1]) by a bisection of the
+// cumulative lengths (empty lists have no index, so they are stepped over), reads list_items[start[j] + that] and goes on
+// exactly as k_topk_cand does with a candidate: range, filter bit, Seen bisection, row gather, chain, optional fmaf, ballot,
+// threshold, insert.  A list probed twice is walked twice; cand_insert drops the repeats, n_elig counts them.
+template <int D, class T>
+__global__ __launch_bounds__(64 * kCandWaves) void k_ivf_search(const T* __restrict__ wu, const T* __restrict__ wi, int64_t n_item,
+                                                                 const int64_t* __restrict__ users, int64_t n,
+                                                                 const int64_t* __restrict__ list_off, const int32_t* __restrict__ list_items,
+                                                                 int n_list, const int32_t* __restrict__ probes, int nprobe, int k,
+                                                                 const int64_t* __restrict__ seen_off, const int32_t* __restrict__ seen_items,
+                                                                 const uint32_t* __restrict__ allow, const float* __restrict__ adj,
+                                                                 int32_t* __restrict__ items, float* __restrict__ scores,
+                                                                 int32_t* __restrict__ n_elig) {
+    __shared__ float l_s[kCandWaves][kCandMaxK];
+    __shared__ int32_t l_i[kCandWaves][kCandMaxK];
+    __shared__ FullRow<D, T> l_u[kCandWaves];
+    __shared__ long long l_cum[kCandWaves][kIvfMaxProbe];      // inclusive cumulative lengths of the probed lists
+    __shared__ int32_t l_start[kCandWaves][kIvfMaxProbe];      // where each probed list starts in list_items (< n_item < 2^31)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    float* const ls = l_s[wave];
+    int32_t* const li = l_i[wave];
+    long long* const cum = l_cum[wave];
+    int32_t* const start = l_start[wave];
+    const float* const offset = adj ? offset_plane(adj, n_item) : nullptr;
+
+    for (int64_t x = (int64_t)blockIdx.x * kCandWaves + wave; x < n; x += (int64_t)gridDim.x * kCandWaves) {
+        const int64_t u = users[x];
+        l_u[wave].load_by_wave(wu + u * D, lane);
+        long long len0 = 0, len1 = 0;
+        int st0 = 0, st1 = 0;
+        if (lane < nprobe) {
+            const int p = probes[x * nprobe + lane];
+            if (p >= 0 && p < n_list) {
+                const int64_t lo = list_off[p], hi = list_off[p + 1];
+                if (hi > lo) { len0 = hi - lo; st0 = (int)lo; }
+            }
+        }
+        if (lane + 64 < nprobe) {
+            const int p = probes[x * nprobe + lane + 64];
+            if (p >= 0 && p < n_list) {
+                const int64_t lo = list_off[p], hi = list_off[p + 1];
+                if (hi > lo) { len1 = hi - lo; st1 = (int)lo; }
+            }
+        }
+        const long long c0 = wave_scan(len0, lane);
+        const long long half = __shfl(c0, 63);
+        const long long c1 = half + wave_scan(len1, lane);
+        const long long len = __shfl(c1, 63);
+        cum[lane] = c0;
+        cum[lane + 64] = c1;
+        start[lane] = st0;
+        start[lane + 64] = st1;
+        __builtin_amdgcn_wave_barrier();
+        const int64_t s_lo = seen_off ? seen_off[u] : 0, s_hi = seen_off ? seen_off[u + 1] : 0;
+        int cnt = 0, ne = 0;
+        float thr_s = -INFINITY;              // the K-th entry once the list is full
+        int thr_i = INT_MAX;
+        for (long long b = 0; b < len; b += 64 * kCandRounds) {
+            FullRow<D, T> xr[kCandRounds];
+            int ci[kCandRounds];
+            bool ok[kCandRounds];
+            float sc[kCandRounds], of[kCandRounds];
+            asm volatile("" ::: "memory");    // cum / start are read below what other lanes wrote above
+#pragma unroll
+            for (int r = 0; r < kCandRounds; ++r) {
+                const long long e = b + 64 * r + lane;
+                long long c = -1;
+                if (e < len) {
+                    // the first probe whose cumulative length exceeds e: e < len = cum[nprobe - 1], so j < nprobe
+                    const int j = lower_bound(0, nprobe, [&](int m) { return cum[m] <= e; });
+                    c = list_items[start[j] + (e - (j ? cum[j - 1] : 0))];
+                }
+                bool good = c >= 0 && c < n_item;         // (a list is trusted to hold item ids; anything else forms no address)
+                if (good && allow) good = (allow[c >> 5] >> (c & 31)) & 1u;
+                if (good && s_lo < s_hi) {
+                    const int32_t cc = (int32_t)c;
+                    const int64_t at = lower_bound(s_lo, s_hi, [&](int64_t m) { return seen_items[m] < cc; });
+                    good = !(at < s_hi && seen_items[at] == cc);
+                }
+                xr[r].zero();
+                sc[r] = 1.0f;
+                of[r] = 0.0f;
+                if (good) {
+                    xr[r].load(wi + c * D);
+                    if (adj) { sc[r] = adj[c]; of[r] = offset[c]; }
+                }
+                ci[r] = good ? (int)c : -1;
+                ok[r] = good;
+            }
+            asm volatile("" ::: "memory");    // (the user row is read from LDS where a value feeds its fmaf, as in k_topk_cand)
+#pragma unroll
+            for (int r = 0; r < kCandRounds; ++r) {
+                float s = score_chain<D, T>(l_u[wave].v, xr[r].v);
+                if (adj) s = adjusted<true>(s, &sc[r], &of[r], 0);
+                const bool elig = ok[r] && s == s;
+                ne += __popcll(__ballot(elig));
+                unsigned long long m = __ballot(elig && (cnt < k || better(s, ci[r], thr_s, thr_i)));
+                while (m) {
+                    const int l = __builtin_ctzll(m);
+                    cand_insert(ls, li, k, lane, cnt, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), l)),
+                                __builtin_amdgcn_readlane(ci[r], l));
+                    m &= m - 1;
+                    if (cnt == k) {
+                        thr_s = ls[k - 1];
+                        thr_i = li[k - 1];
+                        m &= __ballot(elig && better(s, ci[r], thr_s, thr_i));
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int q = lane; q < k; q += 64) {
+            const bool live = q < cnt;
+            items[x * k + q] = live ? li[q] : -1;
+            scores[x * k + q] = live ? ls[q] : -INFINITY;
+        }
+        if (n_elig && lane == 0) n_elig[x] = ne;
+        __builtin_amdgcn_wave_barrier();      // the next user's scan and inserts come after these reads
+    }
+}
+
 // ---- deep lists (sml_topk_deep): top-K up to 1,024 by radix select -----------------------------------------------------------
 //
 // The cost of a list must not grow with k, so nothing is kept sorted during the walks.  Per user: the key of the k-th best
@@ -1360,6 +1505,57 @@ void deep_host_walk(const T* wu, const T* wi, int64_t n_item, const int64_t* use
     }
 }
 
+// sml_ivf_search as a single-threaded walk over host memory: the probed lists in probe order, every member tested and scored as
+// k_ivf_search does (score_chain, adjusted), the distinct eligible ones kept as a sorted list of at most k under `better`.
+template <int D, class T>
+void ivf_host_walk(const T* wu, const T* wi, int64_t n_item, const int64_t* users, int64_t n, const int64_t* list_off,
+                   const int32_t* list_items, int n_list, const int32_t* probes, int nprobe, int k, const int64_t* seen_off,
+                   const int32_t* seen_items, const uint32_t* allow, const float* adj, int32_t* items, float* scores, int32_t* n_elig) {
+    const float* offset = adj ? adj + (n_item + RT - 1) / RT * RT : nullptr;
+    float ls[kCandMaxK];
+    int32_t li[kCandMaxK];
+    for (int64_t x = 0; x < n; ++x) {
+        const int64_t u = users[x];
+        const int64_t s_lo = seen_off ? seen_off[u] : 0, s_hi = seen_off ? seen_off[u + 1] : 0;
+        int cnt = 0, ne = 0;
+        for (int j = 0; j < nprobe; ++j) {
+            const int p = probes[x * nprobe + j];
+            if (p < 0 || p >= n_list) continue;
+            for (int64_t m = list_off[p]; m < list_off[p + 1]; ++m) {
+                const int64_t c = list_items[m];
+                if (c < 0 || c >= n_item) continue;
+                if (allow && !((allow[c >> 5] >> (c & 31)) & 1u)) continue;
+                int64_t lo = s_lo, hi = s_hi;
+                while (lo < hi) {
+                    const int64_t mid = lo + ((hi - lo) >> 1);
+                    if (seen_items[mid] < c) lo = mid + 1; else hi = mid;
+                }
+                if (lo < s_hi && seen_items[lo] == c) continue;
+                float s = score_chain<D, T>(wu + u * D, wi + c * D);
+                if (adj) s = adjusted<true>(s, adj, offset, c);
+                if (s != s) continue;
+                ++ne;
+                int pos = 0;
+                bool repeat = false;
+                for (int q = 0; q < cnt; ++q) {
+                    repeat |= ls[q] == s && li[q] == (int32_t)c;
+                    pos += better(ls[q], li[q], s, (int)c);
+                }
+                if (repeat || pos >= k) continue;
+                if (cnt < k) ++cnt;
+                for (int q = cnt - 1; q > pos; --q) { ls[q] = ls[q - 1]; li[q] = li[q - 1]; }
+                ls[pos] = s;
+                li[pos] = (int32_t)c;
+            }
+        }
+        for (int q = 0; q < k; ++q) {
+            items[x * k + q] = q < cnt ? li[q] : -1;
+            scores[x * k + q] = q < cnt ? ls[q] : -INFINITY;
+        }
+        if (n_elig) n_elig[x] = ne;
+    }
+}
+
 }  // namespace
 
 bool sml_retrieval_supports(int d, int elem_bytes) {
@@ -1472,6 +1668,29 @@ hipError_t sml_launch_topk_candidates(const SmlCatalogue& c, const int64_t* user
     }))
         return hipErrorInvalidValue;
     return hipGetLastError();
+}
+
+hipError_t sml_launch_ivf_search(const SmlCatalogue& c, const int64_t* users, int64_t n, const SmlIvfLists& l, int k, int max_workgroups,
+                                 int32_t* items, float* scores, int32_t* n_elig, hipStream_t st) {
+    int64_t blocks = (n + kCandWaves - 1) / kCandWaves;
+    if (blocks > 65536) blocks = 65536;                  // beyond this the users are walked grid-stride
+    if (max_workgroups > 0 && blocks > max_workgroups) blocks = max_workgroups;
+    const dim3 grid((unsigned)blocks), block(64 * kCandWaves);
+    if (!with_width(c, [&](auto dd, auto, auto, auto* tu, auto* ti) {
+        k_ivf_search<dd(), elem_t<decltype(tu)>><<<grid, block, 0, st>>>(
+            tu, ti, c.n_item, users, n, l.off, l.items, l.n_list, l.probes, l.nprobe, k, c.seen_off, c.seen_items, c.allow, c.adj, items, scores,
+            n_elig);
+    }))
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+bool sml_ivf_host_walk(const SmlCatalogue& c, const int64_t* users, int64_t n, const SmlIvfLists& l, int k, int32_t* items, float* scores,
+                       int32_t* n_elig) {
+    return with_width(c, [&](auto dd, auto, auto, auto* tu, auto* ti) {
+        ivf_host_walk<dd(), elem_t<decltype(tu)>>(tu, ti, c.n_item, users, n, l.off, l.items, l.n_list, l.probes, l.nprobe, k, c.seen_off,
+                                                  c.seen_items, c.allow, c.adj, items, scores, n_elig);
+    });
 }
 
 hipError_t sml_launch_item_filter(const int32_t* ids, int64_t n_ids, int64_t n_item, int invert, uint32_t* words, hipStream_t st) {

@@ -441,6 +441,26 @@ struct SmlCandidates {
 // one wavefront per list, no scratch; max_workgroups > 0 caps the grid (lists are walked grid-stride)
 hipError_t sml_launch_topk_candidates(const SmlCatalogue& c, const int64_t* users, int64_t n, const SmlCandidates& l, int k,
                                       int max_workgroups, int32_t* items, float* scores, int32_t* n_elig, hipStream_t st);
+// the clustered index of sml_ivf_search (include/sml_hip.h): the lists' CSR and each user's probes int32 [n, nprobe]
+struct SmlIvfLists {
+    const int64_t* off;
+    const int32_t* items;
+    int n_list;
+    const int32_t* probes;
+    int nprobe;
+};
+// one wavefront per user over the members of its probed lists, no scratch; max_workgroups > 0 caps the grid.
+// sml_ivf_host_walk: the same definition as a single-threaded walk over host memory (false: no walk for this (d, elem_bytes) pair)
+hipError_t sml_launch_ivf_search(const SmlCatalogue& c, const int64_t* users, int64_t n, const SmlIvfLists& l, int k, int max_workgroups,
+                                 int32_t* items, float* scores, int32_t* n_elig, hipStream_t st);
+bool sml_ivf_host_walk(const SmlCatalogue& c, const int64_t* users, int64_t n, const SmlIvfLists& l, int k, int32_t* items, float* scores,
+                       int32_t* n_elig);
+// ivf.hip: the centroid update of the clustered index (the (d, elem_bytes) pairs of sml_retrieval_supports, any other is
+// hipErrorInvalidValue / false; in == out allowed; no atomics, no allocation, copy or synchronise) and its host walk
+hipError_t sml_launch_ivf_centroids(int d, int elem_bytes, const void* wi, const int64_t* list_off, const int32_t* list_items, int n_list,
+                                    const void* cin, void* cout, hipStream_t st);
+bool sml_ivf_centroids_host_walk(int d, int elem_bytes, const void* wi, const int64_t* list_off, const int32_t* list_items, int n_list,
+                                 const void* cin, void* cout);
 // deep lists (sml_topk_deep, include/sml_hip.h): 1 <= k <= 1024 by a per-user radix select, a fixed number of catalogue walks
 // whatever k is; slices 0 = the planner's, 1 .. 256 forced.  scratch: sml_topk_deep_scratch_size bytes.  No allocation, copy to
 // the host or synchronise.  sml_topk_host_walk: the same definition as a single-threaded walk over host memory (c holds host

@@ -1040,6 +1040,62 @@ class HipEngine(object):
                                            _ptr(n_elig), self._stream()), "sml_topk_candidates")
         return items.long(), scores, n_elig
 
+    def _ivf_lists(self, index_arrays, n_item):
+        """index_arrays: an ItemIndex (anything with .list_off / .list_items) or a (list_off, list_items) pair -> (list_off int64
+        [n_list + 1], list_items int32 [n_item]) on this device."""
+        if hasattr(index_arrays, "list_off") and hasattr(index_arrays, "list_items"):
+            index_arrays = (index_arrays.list_off, index_arrays.list_items)
+        if not isinstance(index_arrays, (tuple, list)) or len(index_arrays) != 2:
+            raise ValueError("an index is an ItemIndex or a (list_off, list_items) pair")
+        off, items = (self._dev(t, dt) for t, dt in zip(index_arrays, (torch.int64, torch.int32)))
+        if off.dim() != 1 or off.shape[0] < 2 or items.dim() != 1 or items.shape[0] != int(n_item):
+            raise ValueError("expected list_off int64 [n_list + 1] and list_items int32 [%d], got %s and %s"
+                             % (int(n_item), tuple(off.shape), tuple(items.shape)))
+        return off, items
+
+    def ivf_search(self, user_tab, item_tab, users, index_arrays, probes, k, seen=None, allow=None, adjust=None, max_workgroups=0):
+        """(int64 items [n, k], float32 scores [n, k], int32 n_elig [n]): for each user the k best distinct eligible members of
+        the lists it probes -- topk_candidates on "the members of probes[x, 0], then of probes[x, 1], ...", byte for byte, with
+        no candidate matrix written (include/sml_hip.h, CLUSTERED INDEX; sml_ivf_search: one wavefront per user, no scratch).
+        index_arrays: an ItemIndex or its (list_off, list_items); probes: int [n, nprobe], 1 <= nprobe <= 128, entries outside
+        [0, n_list) are padding (ItemIndex.probe makes them).  seen, allow and adjust as in topk_candidates.  Probing every
+        list once returns topk_items' bytes.  max_workgroups > 0 caps the grid (the bytes do not depend on it)."""
+        wu, wi, _ = self._retrieval_tables(user_tab, item_tab)
+        allow = self._allow(allow, wi.shape[0])
+        adj = self._adjust(adjust, wi)
+        users = self._dev(users, torch.int64).reshape(-1)
+        list_off, list_items = self._ivf_lists(index_arrays, wi.shape[0])
+        probes = self._dev(probes, torch.int32)
+        n, k = users.shape[0], int(k)
+        if probes.dim() != 2 or probes.shape[0] != n:
+            raise ValueError("probes must be int [%d, nprobe], got shape %s" % (n, tuple(probes.shape)))
+        off, seen_items = self._seen(seen)
+        items = torch.empty(n, max(k, 0), device=self.device, dtype=torch.int32)
+        scores = torch.empty(n, max(k, 0), device=self.device, dtype=torch.float32)
+        n_elig = torch.empty(n, device=self.device, dtype=torch.int32)
+        check(self.lib.sml_ivf_search(self._ctx, _ptr(wu), _ptr(wi), wi.element_size(), wi.shape[0], _ptr(users), n, _ptr(list_off),
+                                      _ptr(list_items), list_off.shape[0] - 1, _ptr(probes), probes.shape[1], k, _ptr(off),
+                                      _ptr(seen_items), _ptr(allow), _ptr(adj), int(max_workgroups), _ptr(items), _ptr(scores),
+                                      _ptr(n_elig), self._stream()), "sml_ivf_search")
+        return items.long(), scores, n_elig
+
+    def ivf_centroids(self, item_tab, list_off, list_items, centroids, out=None):
+        """The centroids [n_list, d] (the table's element type) of the lists (list_off, list_items) over item_tab: per list and
+        dim the members' values added in member order in fp64, divided by the count and rounded to the element type; an empty
+        list keeps its row of `centroids` (sml_ivf_centroids).  out: where to write (None: a new tensor; `centroids` itself:
+        in place)."""
+        _, wi, _ = self._retrieval_tables(item_tab, item_tab)
+        off, items = self._ivf_lists((list_off, list_items), wi.shape[0])
+        n_list = off.shape[0] - 1
+        out = torch.empty_like(centroids) if out is None else out
+        for t in (centroids, out):
+            if t.dtype != wi.dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n_list, self.d):
+                raise ValueError("expected contiguous %s centroids [%d, %d] on %s, got %s %s on %s"
+                                 % (wi.dtype, n_list, self.d, self.device, t.dtype, tuple(t.shape), t.device))
+        check(self.lib.sml_ivf_centroids(self._ctx, _ptr(wi), wi.element_size(), wi.shape[0], _ptr(off), _ptr(items), n_list,
+                                         _ptr(centroids), _ptr(out), self._stream()), "sml_ivf_centroids")
+        return out
+
     def rerank_mmr(self, item_tab, pool_items, pool_scores, k, lam, metric="cosine", normalize=True, max_workgroups=0, nrm=None):
         """Greedy MMR re-ranking of per-list pools (include/sml_hip.h, RE-RANKING; sml_rerank_mmr: one wavefront per list, no
         scratch).  pool_items int [n, C <= 128] (int64 as recommend returns them is narrowed on the device; entries outside

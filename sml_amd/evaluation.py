@@ -174,6 +174,22 @@ def recall_curve(model, held_out, ks, exclude=None, items=None, score=None):
     return [float(np.mean(hits[:, k].astype(np.float64) / m.astype(np.float64))) for k in ks]
 
 
+def index_recall(model, index, users, topK=20, nprobe=None, exclude=None):
+    """What the approximation of MFbasemode.recommend(index=) costs: the mean over `users` of
+    |indexed list AND exact list| / (number of live slots of the exact list), the two lists being recommend(users, topK,
+    exclude=) with and without the index (nprobe as recommend takes it); users whose exact list is empty do not count (0.0
+    when none is left).  Exactly 1.0 when every list is probed.  The lists are compared on the host in float64."""
+    users = torch.as_tensor(users).reshape(-1)
+    exact = model.recommend(users, topK, exclude=exclude)[0].cpu().numpy()
+    got = model.recommend(users, topK, exclude=exclude, index=index, nprobe=nprobe)[0].cpu().numpy()
+    live = (exact >= 0).sum(1)
+    both = ((got[:, :, None] == exact[:, None, :]) & (got >= 0)[:, :, None]).any(2).sum(1)
+    keep = live > 0
+    if not keep.any():
+        return 0.0
+    return float(np.mean(both[keep].astype(np.float64) / live[keep].astype(np.float64)))
+
+
 def intra_list_similarity(model, lists, metric="cosine"):
     """float32 [n]: the mean pairwise similarity of each list's items -- the number that shows what
     MFbasemode.recommend(diversify=) did.  lists: item ids [n, m <= 128], padded with -1 (ids outside the catalogue and

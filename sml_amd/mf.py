@@ -79,7 +79,7 @@ class MFbasemode(nn.Module):
         return hit_rows, ranks, hits * 1.0, (torch.tensor(ndcg) if hits > 0 else 0)
 
     def recommend(self, users, topK=20, exclude=None, items=None, score=None, candidates=None, diversify=None, pool=None,
-                  metric="cosine"):
+                  metric="cosine", index=None, nprobe=None):
         """(items int64 [n, topK], scores float32 [n, topK]): each user's topK items over the whole catalogue by the score
         test() uses (no bias terms), score descending then item id ascending, leaving out `exclude` (a
         sml_amd.retrieval.SeenItems or a (seen_off, seen_items) CSR); missing slots are (-1, -inf).  1 <= topK <= 1024: above
@@ -97,12 +97,24 @@ class MFbasemode(nn.Module):
         above) and re-ranks them greedily by lam * r - (1 - lam) * max similarity to the items already picked (r: the score,
         min-max scaled per list; similarity by `metric`, "cosine" or "dot" of the item rows; HipEngine.rerank_mmr).  The
         returned scores are the model's scores of the picked items, gathered from the pool.  diversify=1 returns the plain
-        list; sml_amd.evaluation.intra_list_similarity says how alike a list's items are."""
+        list; sml_amd.evaluation.intra_list_similarity says how alike a list's items are.
+        index: None -- the call as above, the same bytes -- or a sml_amd.retrieval.ItemIndex over this model's item table: each
+        user then scores only the members of its nprobe nearest lists (default min(8, n_list); at most 128) instead of the
+        catalogue (HipEngine.ivf_search).  What is returned is exact for the items that were scored; what may be missing is an
+        item of a list that was not probed (sml_amd.evaluation.index_recall measures it; nprobe = n_list returns the exact
+        lists).  topK <= 128; exclude, items and score apply as above, diversify takes its pool from the indexed call, and
+        candidates= together with index= is a ValueError, as is an index over another catalogue size or element type."""
         from .retrieval import as_csr, as_filter, as_score
+        if index is not None:
+            from .retrieval import index_args
+            # (with diversify the indexed call makes the pool, whose size diversify_args checks)
+            nprobe = index_args(index, nprobe, topK if diversify is None else 1, self.item_laten.weight.shape[0],
+                                self.item_laten.weight.dtype, candidates)
         if diversify is not None:
             from .retrieval import diversify_args
             pool = diversify_args(topK, diversify, pool, metric)
-            it, sc = self.recommend(users, pool, exclude=exclude, items=items, score=score, candidates=candidates)
+            it, sc = self.recommend(users, pool, exclude=exclude, items=items, score=score, candidates=candidates, index=index,
+                                    nprobe=nprobe)
             picked, at, _, _, _ = _engine_for(self).rerank_mmr(self.item_laten.weight.data, it, sc, topK, diversify, metric=metric)
             return picked, torch.where(at >= 0, sc.gather(1, at.clamp(min=0).long()), sc.new_full((), float("-inf")))
         eng = _engine_for(self)
@@ -110,6 +122,11 @@ class MFbasemode(nn.Module):
         if candidates is not None:
             it, sc, _ = eng.topk_candidates(w.data, self.item_laten.weight.data, users, candidates, topK, as_csr(exclude, w.device),
                                             as_filter(items, self.item_laten.weight.shape[0], w.device), as_score(score, self))
+            return it, sc
+        if index is not None:
+            it, sc, _ = eng.ivf_search(w.data, self.item_laten.weight.data, users, index, index.probe(w.data, users, nprobe), topK,
+                                       as_csr(exclude, w.device), as_filter(items, self.item_laten.weight.shape[0], w.device),
+                                       as_score(score, self))
             return it, sc
         return _topk(eng, int(topK))(w.data, self.item_laten.weight.data, users, topK, as_csr(exclude, w.device),
                                      as_filter(items, self.item_laten.weight.shape[0], w.device), as_score(score, self))
@@ -129,7 +146,7 @@ class MFbasemode(nn.Module):
             inputs_data = CandidateRows(inputs_data, 1)
         return self.recommend(None, topK, exclude=exclude, score=score, candidates=inputs_data)
 
-    def similar_items(self, items, topK=20, metric="cosine", among=None, exclude_self=True):
+    def similar_items(self, items, topK=20, metric="cosine", among=None, exclude_self=True, index=None, nprobe=None):
         """(int64 [n, topK], float32 [n, topK]): for each query item its topK most similar items of the catalogue, the item
         table serving as both tables (score descending, then id ascending; missing slots (-1, -inf)).  metric="dot": the
         bare dot product <x_q, x_i>.  metric="cosine": the order is the kernel's A(q, i) = <x_q, x_i> / ||x_i|| (the query's
@@ -137,14 +154,23 @@ class MFbasemode(nn.Module):
         it is the cosine up to three roundings, not a correctly rounded one.  among: an item filter (as recommend's items=)
         on the returned items; exclude_self: leave the query out of its own list.  Every cosine call rebuilds the norm table
         of the whole catalogue from the current weights (one pass over the item table, never stale): batch small query sets
-        into one call rather than paying it per query."""
+        into one call rather than paying it per query.  index / nprobe: as in recommend -- the query item probes the index's
+        lists with its own row and only their members are scored (topK <= 128)."""
         from .retrieval import as_filter, self_seen
+        if index is not None:
+            from .retrieval import index_args
+            nprobe = index_args(index, nprobe, topK, self.item_laten.weight.shape[0], self.item_laten.weight.dtype)
         eng = _engine_for(self)
         w = self.item_laten.weight.data
         q = torch.as_tensor(items).to(w.device).long().reshape(-1)
         seen = self_seen(w.shape[0], w.device) if exclude_self else None
         allow = as_filter(among, w.shape[0], w.device)
         topk = _topk(eng, int(topK))
+        if index is not None:
+            probes = index.probe(w, q, nprobe)
+
+            def topk(wu, wi, users, k, seen_, allow_, adjust=None):
+                return eng.ivf_search(wu, wi, users, index, probes, k, seen_, allow_, adjust)[:2]
         if metric == "dot":
             return topk(w, w, q, topK, seen, allow)
         if metric != "cosine":

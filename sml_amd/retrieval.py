@@ -26,6 +26,10 @@ On the device the terms are one padded table,
 Candidates / CandidateRows / as_candidates describe per-user candidate lists, the allow list of one user each that
 sml_topk_candidates orders (HipEngine.topk_candidates, MFbasemode.recommend(candidates=), MFbasemode.test_lists): a ragged
 (cand_off, cand_items) pair or a dense matrix read in place, e.g. the rows [user, positive, negatives] of a test set.
+
+ItemIndex is a clustered (inverted-file) index over the item table: k-means lists built on the device, so that
+MFbasemode.recommend(index=) scores only the members of each user's nearest lists (HipEngine.ivf_search) instead of the
+catalogue; sml_amd.evaluation.index_recall measures what that costs.
 """
 import os
 
@@ -529,6 +533,147 @@ def as_candidates(x, n, device):
     if n is not None and got.n != int(n):
         raise ValueError("the candidates hold %d lists, the call has %d users" % (got.n, int(n)))
     return got
+
+
+IVF_MAX_PROBE = 128   # probes per user of sml_ivf_search
+IVF_MAX_K = 128       # its longest list
+
+
+def default_n_list(n_item):
+    """round(sqrt(n_item)), at least 1 and at most n_item: the convention ItemIndex.build follows when n_list is None."""
+    n_item = int(n_item)
+    return max(1, min(n_item, int(round(float(np.sqrt(n_item))))))
+
+
+class ItemIndex(object):
+    """A clustered (inverted-file) index over an item table [n_item, d] (include/sml_hip.h, CLUSTERED INDEX): k-means lists
+    of the items, so that a query scores only the members of the lists nearest the user (HipEngine.ivf_search,
+    MFbasemode.recommend(index=)).  Three device arrays:
+
+        centroids   [n_list, d] in the table's element type   list_off  int64 [n_list + 1]
+        list_items  int32 [n_item]: a partition of the item ids, ascending inside each list
+
+    The index holds no rows and no scores -- search reads the current item table -- so an index built on last period's
+    table costs recall on a retrained one, never a wrong score; refresh() moves it along with a couple of iterations.
+    metric: how items (and later users) choose lists: "cosine" (the default: spherical assignment, S / ||centroid||) or
+    "dot".  The same seed, table and arguments give the same bytes on every run."""
+
+    def __init__(self, centroids, list_off, list_items, metric="cosine", engine=None):
+        if metric not in ("cosine", "dot"):
+            raise ValueError('metric is "cosine" or "dot", got %r' % (metric,))
+        if centroids.dim() != 2 or centroids.dtype not in (torch.float32, torch.float16):
+            raise ValueError("centroids are an fp32 or fp16 table [n_list, d], got %s %s" % (centroids.dtype, tuple(centroids.shape)))
+        if list_off.dim() != 1 or list_off.shape[0] != centroids.shape[0] + 1 or list_off.dtype != torch.int64:
+            raise ValueError("list_off must be int64 [%d], got %s %s" % (centroids.shape[0] + 1, list_off.dtype, tuple(list_off.shape)))
+        if list_items.dim() != 1 or list_items.dtype != torch.int32:
+            raise ValueError("list_items must be int32 [n_item], got %s %s" % (list_items.dtype, tuple(list_items.shape)))
+        self.centroids, self.list_off, self.list_items = centroids, list_off, list_items
+        self.metric, self.engine = metric, engine
+        self._adj = None
+
+    @property
+    def n_list(self):
+        return int(self.centroids.shape[0])
+
+    @property
+    def n_item(self):
+        return int(self.list_items.shape[0])
+
+    @property
+    def dtype(self):
+        return self.centroids.dtype
+
+    def sizes(self):
+        """int64 [n_list]: the lists' lengths (on the index's device)."""
+        return self.list_off[1:] - self.list_off[:-1]
+
+    def host(self):
+        """{"centroids", "list_off", "list_items"} as numpy arrays."""
+        return {"centroids": self.centroids.cpu().numpy(), "list_off": self.list_off.cpu().numpy(),
+                "list_items": self.list_items.cpu().numpy()}
+
+    def _check_table(self, item_tab):
+        if item_tab.dim() != 2 or item_tab.shape[0] != self.n_item or item_tab.shape[1] != self.centroids.shape[1] or \
+                item_tab.dtype != self.dtype:
+            raise ValueError("the index is over a %s table [%d, %d], got %s %s"
+                             % (self.dtype, self.n_item, self.centroids.shape[1], item_tab.dtype, tuple(item_tab.shape)))
+
+    def _centroid_adjust(self):
+        """The metric's score terms over the CENTROID table (None for "dot"); rebuilt only when the centroids change."""
+        if self.metric == "dot":
+            return None
+        if self._adj is None:
+            self._adj = self.engine.item_adjust_cosine(self.centroids)
+        return self._adj
+
+    def _iterate(self, item_tab, iters):
+        """iters times: assign every item to its best centroid, rebuild the lists, move the centroids to their lists' means."""
+        eng = self.engine
+        n_item = item_tab.shape[0]
+        ids = torch.arange(n_item, device=eng.device, dtype=torch.int64)
+        for _ in range(int(iters)):
+            best, _ = eng.topk_items(item_tab, self.centroids, ids, 1, adjust=self._centroid_adjust())
+            assign = best[:, 0].clamp(min=0)            # an item whose every centroid score is NaN joins list 0
+            self.list_off, self.list_items = eng.iset_build(torch.stack([assign, ids], 1), self.n_list, n_item)
+            self.centroids = eng.ivf_centroids(item_tab, self.list_off, self.list_items, self.centroids)
+            self._adj = None
+        return self
+
+    @classmethod
+    def build(cls, item_tab, n_list=None, iters=10, seed=0, metric="cosine", engine=None):
+        """k-means over the rows of item_tab (fp32 or fp16, on the GPU): n_list (None: round(sqrt(n_item))) distinct rows
+        drawn by numpy.random.RandomState(seed) start the centroids; then `iters` >= 1 iterations of assign / lists / update."""
+        if metric not in ("cosine", "dot"):
+            raise ValueError('metric is "cosine" or "dot", got %r' % (metric,))
+        if not torch.is_tensor(item_tab) or item_tab.dim() != 2:
+            raise ValueError("item_tab is a tensor [n_item, d]")
+        n_item = int(item_tab.shape[0])
+        n_list = default_n_list(n_item) if n_list is None else int(n_list)
+        if not 1 <= n_list <= n_item:
+            raise ValueError("n_list must lie in 1..n_item = %d, got %d" % (n_item, n_list))
+        if int(iters) < 1:
+            raise ValueError("iters must be at least 1, got %d" % int(iters))
+        if engine is None:
+            from .engine import get_engine
+            engine = get_engine(item_tab.device, item_tab.shape[1])
+        first = np.random.RandomState(seed).choice(n_item, size=n_list, replace=False).astype(np.int64)
+        centroids = item_tab[torch.from_numpy(first).to(item_tab.device)].contiguous()
+        idx = cls(centroids, torch.zeros(n_list + 1, device=item_tab.device, dtype=torch.int64),
+                  torch.zeros(n_item, device=item_tab.device, dtype=torch.int32), metric, engine)
+        return idx._iterate(item_tab, iters)
+
+    def refresh(self, item_tab, iters=2):
+        """Continue from the current centroids on a retrained table of the same shape and type: `iters` more iterations, no
+        re-initialisation.  On an unchanged table refresh(iters=1) is one more iteration of build."""
+        self._check_table(item_tab)
+        if int(iters) < 1:
+            raise ValueError("iters must be at least 1, got %d" % int(iters))
+        return self._iterate(item_tab, iters)
+
+    def probe(self, user_tab, users, nprobe):
+        """int32 [n, nprobe]: each user's nprobe best lists by the index's metric against the centroids, best first (-1 past
+        n_list): what HipEngine.ivf_search takes.  Seen and item filters do not apply to centroids."""
+        nprobe = int(nprobe)
+        if not 1 <= nprobe <= IVF_MAX_PROBE:
+            raise ValueError("nprobe must lie in 1..%d, got %d" % (IVF_MAX_PROBE, nprobe))
+        lists, _ = self.engine.topk_items(user_tab, self.centroids, users, nprobe, adjust=self._centroid_adjust())
+        return lists.to(torch.int32)
+
+
+def index_args(index, nprobe, topK, n_item, dtype, candidates=None):
+    """nprobe as MFbasemode.recommend(index=) passes it on (None: min(8, n_list)), checked without a device."""
+    if not isinstance(index, ItemIndex):
+        raise ValueError("index= is a sml_amd.retrieval.ItemIndex, got %s" % type(index).__name__)
+    if candidates is not None:
+        raise ValueError("candidates= and index= both name the items to score: give one of them")
+    if index.n_item != int(n_item) or index.dtype != dtype:
+        raise ValueError("the index is over %d %s items, the model has %d %s" % (index.n_item, index.dtype, int(n_item), dtype))
+    if not 1 <= int(topK) <= IVF_MAX_K:
+        raise ValueError("topK must lie in 1..%d with an index, got %d" % (IVF_MAX_K, int(topK)))
+    nprobe = min(8, index.n_list) if nprobe is None else int(nprobe)
+    if not 1 <= nprobe <= IVF_MAX_PROBE:
+        raise ValueError("nprobe must lie in 1..%d, got %d" % (IVF_MAX_PROBE, nprobe))
+    return nprobe
 
 
 _SELF_SEEN = {}
