@@ -700,6 +700,62 @@ int sml_ivf_centroids(sml_ctx* ctx, const void* w_item, int elem_bytes, int64_t 
 int sml_host_ivf_centroids(const void* w_item, int elem_bytes, int d, int64_t n_item,
                            const int64_t* list_off, const int32_t* list_items, int n_list,
                            const void* centroids_in, void* centroids_out);
+/* ---- FOLD-IN: the closed-form row of a user or an item the last training run did not see -- the iALS half-step.  The other
+ * side's table Y [n_other, d] is held fixed and the row solves its regularised least-squares problem from its interaction set S:
+ *   p = argmin_p  sum_{i in S} (1 - p.y_i)^2 + alpha0 sum_{all i} (p.y_i)^2 + reg |p|^2
+ *     = (alpha0 Y^T Y + sum_{i in S} y_i y_i^T + reg I)^-1 sum_{i in S} y_i.
+ * With the user table as Y and the item -> users CSR the same call folds in items; alternating the two is iALS.
+ * All arithmetic is fp64 and every rounding is named below, so the bytes depend on no launch geometry; the host walks share
+ * the text of the steps with the kernels, compiled so that nothing is contracted or reassociated: every fused step is an explicit
+ * fma().  There are no floating-point atomics and no matrix instructions.
+ * Tables: element type T and width d of the retrieval family without d = 128 -- fp32: d = 32 / 64; fp16: d = 32 / 64; any other
+ * pair is refused.  d = 128 needs a different register / LDS plan (one lane cannot hold a row of the triangle) and is out of scope.
+ * GRAM.  G = Y^T Y over rows [0, n_rows) of a table, in chunks of SML_GRAM_CHUNK = 1024 rows, a constant of the definition.  For
+ * chunk c and every (a, b): part = 0.0; for the chunk's rows i ascending: part = part + (double)y[i][a] * (double)y[i][b] -- the
+ * product of two widened fp32 / fp16 values is exact in fp64, so fused or not gives the same bits and only the add rounds.  Then
+ * G[a][b] = 0.0 and G[a][b] += part_c for c ascending.  G is double [d][d]; both triangles are written and are equal bit for bit
+ * (the product commutes exactly).  NaN / Inf propagate.  scratch: sml_gram_scratch_bytes = n_chunks * d * d * 8 bytes, the
+ * partials; scratch and gram 16-byte aligned.
+ * ROW SOLVE, for a row with members m_0 < m_1 < ... (its range of the set CSR, ids ascending, as sml_iset_build writes them).
+ * Only the lower triangle a >= b is formed:
+ *   A[a][b] = fma(alpha0, G[a][b], a == b ? reg : 0.0); for members ascending: A[a][b] = A[a][b] + (double)y[m][a] * (double)y[m][b];
+ *   rhs[a] = 0.0; for members ascending: rhs[a] += (double)y[m][a].
+ * LDL^T without square roots, for j = 0 .. d - 1:
+ *   v[k] = L[j][k] * D[k] for k < j;  D[j] = A[j][j]; for k = 0 .. j - 1: D[j] = fma(-L[j][k], v[k], D[j]);
+ *   if !(D[j] > 0) the row fails;
+ *   for i > j: t = A[i][j]; for k ascending: t = fma(-L[i][k], v[k], t); L[i][j] = t / D[j], the correctly rounded fp64 division.
+ * Forward: z[j] = rhs[j]; for k < j ascending: z[j] = fma(-L[j][k], z[k], z[j]); then w[j] = z[j] / D[j].
+ * Backward, j = d - 1 .. 0: p[j] = w[j]; for k = j + 1 .. d - 1 ascending: p[j] = fma(-L[k][j], p[k], p[j]).
+ * Output: out[row][s] = (T)(float)p[s], each conversion to nearest even.
+ * STATUS, int32 per solved row (status[x] belongs to rows[x]):
+ *   0  solved and written;
+ *   1  empty set: the row is written as +0.0 in every dim (the exact solution); nothing is factored;
+ *   2  a pivot was not > 0, or some p[s] is not finite (reg = alpha0 = 0 with a rank-deficient set, a NaN / Inf member row, a
+ *      NaN Gram): the output row is left untouched.
+ * rows int64 [n]: which rows of w_out to solve; rows[x] also indexes set_off.  rows == NULL means rows 0 .. n - 1.  A row named
+ * twice is written twice with the same bytes; rows not named are not touched.  w_out [n_out, d] has the element type of w_other.
+ * gram == NULL is accepted only with alpha0 == 0 (G is then read as +0.0).  set_off == set_items == NULL: every set is empty.
+ * max_workgroups = 0 leaves the grid to the call, a positive value caps it (one wavefront serves one row, rows are walked
+ * grid-stride); it never changes a byte.  No allocation, no copy to the host, no synchronise; n == 0 launches nothing.  Indices
+ * (rows, set_off, set_items) are trusted, like Seen.
+ * Refused (sml_last_error): a (d, elem_bytes) pair outside the list above; reg or alpha0 negative or NaN; n_other, n_out outside
+ * (0, 2^31); max_workgroups < 0; exactly one of set_off / set_items NULL; w_out overlapping w_other, gram, the set or status, where
+ * the pointers and known sizes show it; a gram or scratch not 16-byte aligned.
+ * sml_host_gram / sml_host_als_solve: the same definitions as single-threaded walks over HOST memory; d is the caller's (no
+ * context), and nothing has to be aligned.
+ * Not measured: trained (non-random) tables, recall of folded-in new users on real periods, shapes beyond the Yelp one. */
+#define SML_GRAM_CHUNK 1024
+/* n_chunks * d * d * 8; < 0: bad argument (0 < n_rows < 2^31) */
+int64_t sml_gram_scratch_bytes(sml_ctx* ctx, int64_t n_rows);
+int sml_gram(sml_ctx* ctx, const void* w, int elem_bytes, int64_t n_rows, void* scratch, double* gram, void* stream);
+int sml_host_gram(const void* w, int elem_bytes, int d, int64_t n_rows, double* gram);
+int sml_als_solve(sml_ctx* ctx, const void* w_other, int elem_bytes, int64_t n_other, const double* gram,
+                  double alpha0, double reg, const int64_t* set_off, const int32_t* set_items,
+                  const int64_t* rows, int64_t n, void* w_out, int64_t n_out, int max_workgroups,
+                  int32_t* status, void* stream);
+int sml_host_als_solve(const void* w_other, int elem_bytes, int d, int64_t n_other, const double* gram,
+                       double alpha0, double reg, const int64_t* set_off, const int32_t* set_items,
+                       const int64_t* rows, int64_t n, void* w_out, int64_t n_out, int32_t* status);
 /* ---- DEEP LISTS: candidate generation at depth -- lists of up to 1,024 items per user over the whole catalogue, for a
  * downstream re-ranker, a recall@K curve or a pool.  sml_topk_items keeps a sorted list per (user, slice) and its cost grows
  * with k; sml_topk_deep selects by radix: a fixed number of catalogue walks (four counting passes over the order-preserving

@@ -150,6 +150,13 @@ SIGNATURES = {
                                            c_void]),
     "sml_ivf_centroids": (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, c_void, ctypes.c_int, c_void, c_void, c_void]),
     "sml_host_ivf_centroids": (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_void, c_void, ctypes.c_int, c_void, c_void]),
+    "sml_gram_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64]),
+    "sml_gram": (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void]),
+    "sml_host_gram": (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_void]),
+    "sml_als_solve": (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_double, ctypes.c_double, c_void, c_void,
+                                     c_void, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void]),
+    "sml_host_als_solve": (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_double, ctypes.c_double, c_void,
+                                          c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void]),
     "sml_topk_deep_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
     "sml_topk_deep": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
                                      c_void, c_void, ctypes.c_int, c_void, c_void, c_void, c_void, c_void]),

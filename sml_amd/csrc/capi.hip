@@ -2099,6 +2099,93 @@ int sml_host_ivf_centroids(const void* w_item, int elem_bytes, int d, int64_t n_
     return SML_OK;
 }
 
+// fold-in: what the device calls and the host walks refuse alike (NULL: nothing)
+static const char* gram_refusal(int d, int elem_bytes, const void* w, int64_t n_rows, const void* scratch, int64_t scratch_bytes, const double* gram,
+                                bool device) {
+    if (!sml_als_supports(d, elem_bytes)) return "bad argument (fp32 or fp16 tables of d = 32 / 64; d = 128 is out of scope)";
+    if (n_rows <= 0 || n_rows >= ((int64_t)1 << 31)) return "bad argument (0 < n_rows < 2^31)";
+    if (!w || !gram || (device && !scratch)) return "null argument";
+    if (device && (((uintptr_t)scratch | (uintptr_t)gram) & 15)) return "scratch and gram must be 16-byte aligned";
+    const int64_t gb = (int64_t)d * d * 8, wb = n_rows * d * elem_bytes;
+    if (iset_overlap(gram, gb, w, wb) || iset_overlap(scratch, scratch_bytes, w, wb) || iset_overlap(gram, gb, scratch, scratch_bytes))
+        return "an output overlaps an input or the scratch";
+    return nullptr;
+}
+
+int64_t sml_gram_scratch_bytes(sml_ctx* ctx, int64_t n_rows) {
+    if (!ctx || n_rows <= 0 || n_rows >= ((int64_t)1 << 31)) return fail(SML_EINVAL, "sml_gram_scratch_bytes", "bad argument (0 < n_rows < 2^31)");
+    return sml_gram_chunks(n_rows) * ctx->d * ctx->d * 8;
+}
+
+int sml_gram(sml_ctx* ctx, const void* w, int elem_bytes, int64_t n_rows, void* scratch, double* gram, void* stream) {
+    const char* what = "sml_gram";
+    if (!ctx) return fail(SML_EINVAL, what, "null argument");
+    const int64_t sb = n_rows > 0 ? sml_gram_chunks(n_rows) * ctx->d * ctx->d * 8 : 0;
+    if (const char* why = gram_refusal(ctx->d, elem_bytes, w, n_rows, scratch, sb, gram, true)) return fail(SML_EINVAL, what, why);
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_gram(ctx->d, elem_bytes, w, n_rows, (double*)scratch, gram, st)));
+    return SML_OK;
+}
+
+int sml_host_gram(const void* w, int elem_bytes, int d, int64_t n_rows, double* gram) {
+    const char* what = "sml_host_gram";
+    if (const char* why = gram_refusal(d, elem_bytes, w, n_rows, nullptr, 0, gram, false)) return fail(SML_EINVAL, what, why);
+    if (!sml_gram_host_walk(d, elem_bytes, w, n_rows, gram)) return fail(SML_EINVAL, what, "no walk for this (d, elem_bytes) pair");
+    return SML_OK;
+}
+
+static const char* als_refusal(int d, int elem_bytes, const void* w_other, int64_t n_other, const double* gram, double alpha0, double reg,
+                               const int64_t* set_off, const int32_t* set_items, const int64_t* rows, int64_t n, const void* w_out, int64_t n_out,
+                               int max_workgroups, const int32_t* status, bool device) {
+    if (!sml_als_supports(d, elem_bytes)) return "bad argument (fp32 or fp16 tables of d = 32 / 64; d = 128 is out of scope)";
+    if (!(reg >= 0.0) || !(alpha0 >= 0.0)) return "bad argument (reg and alpha0 must be >= 0)";
+    if (n_other <= 0 || n_other >= ((int64_t)1 << 31) || n_out <= 0 || n_out >= ((int64_t)1 << 31) || n < 0 || n >= ((int64_t)1 << 31))
+        return "bad argument (0 < n_other < 2^31, 0 < n_out < 2^31, 0 <= n < 2^31)";
+    if (max_workgroups < 0) return "bad argument (max_workgroups >= 0)";
+    if ((!set_off) != (!set_items)) return "bad argument (set_off and set_items both or neither)";
+    if (!gram && alpha0 != 0.0) return "bad argument (gram == NULL only with alpha0 == 0)";
+    if (device && ((uintptr_t)gram & 15)) return "gram must be 16-byte aligned";
+    if (n == 0) return nullptr;
+    if (!w_other || !w_out || !status) return "null argument";
+    const int64_t ob = n_out * d * elem_bytes;
+    const struct { const void* p; int64_t bytes; } in[] = {
+        {w_other, n_other * d * elem_bytes}, {gram, (int64_t)d * d * 8}, {set_off, rows ? 8 : 8 * (n + 1)}, {set_items, 4}, {rows, 8 * n},
+        {status, 4 * n}};
+    for (const auto& i : in)
+        if (iset_overlap(w_out, ob, i.p, i.bytes)) return "w_out overlaps an input or status";
+    for (int a = 0; a < 5; ++a)
+        if (iset_overlap(status, 4 * n, in[a].p, in[a].bytes)) return "status overlaps an input";
+    return nullptr;
+}
+
+int sml_als_solve(sml_ctx* ctx, const void* w_other, int elem_bytes, int64_t n_other, const double* gram, double alpha0, double reg,
+                  const int64_t* set_off, const int32_t* set_items, const int64_t* rows, int64_t n, void* w_out, int64_t n_out,
+                  int max_workgroups, int32_t* status, void* stream) {
+    const char* what = "sml_als_solve";
+    if (!ctx) return fail(SML_EINVAL, what, "null argument");
+    if (const char* why = als_refusal(ctx->d, elem_bytes, w_other, n_other, gram, alpha0, reg, set_off, set_items, rows, n, w_out, n_out,
+                                      max_workgroups, status, true))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_als_solve(ctx->d, elem_bytes, w_other, gram, alpha0, reg, set_off, set_items, rows, n, w_out,
+                                                  max_workgroups, status, st)));
+    return SML_OK;
+}
+
+int sml_host_als_solve(const void* w_other, int elem_bytes, int d, int64_t n_other, const double* gram, double alpha0, double reg,
+                       const int64_t* set_off, const int32_t* set_items, const int64_t* rows, int64_t n, void* w_out, int64_t n_out,
+                       int32_t* status) {
+    const char* what = "sml_host_als_solve";
+    if (const char* why = als_refusal(d, elem_bytes, w_other, n_other, gram, alpha0, reg, set_off, set_items, rows, n, w_out, n_out, 0, status,
+                                      false))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    if (!sml_als_host_walk(d, elem_bytes, w_other, gram, alpha0, reg, set_off, set_items, rows, n, w_out, status))
+        return fail(SML_EINVAL, what, "no walk for this (d, elem_bytes) pair");
+    return SML_OK;
+}
+
 // deep lists: what sml_topk_deep and sml_host_topk_items refuse alike (NULL: nothing).  The tables' heights are unknown: they
 // count from their first row only
 static const char* deep_refusal(int d, int elem_bytes, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,

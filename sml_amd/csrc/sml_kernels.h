@@ -461,6 +461,19 @@ hipError_t sml_launch_ivf_centroids(int d, int elem_bytes, const void* wi, const
                                     const void* cin, void* cout, hipStream_t st);
 bool sml_ivf_centroids_host_walk(int d, int elem_bytes, const void* wi, const int64_t* list_off, const int32_t* list_items, int n_list,
                                  const void* cin, void* cout);
+// als.hip: the fold-in (include/sml_hip.h, FOLD-IN) -- the Gram matrix of a table in chunk order (part: sml_gram_chunks(n_rows)
+// * d * d doubles) and one LDL^T solve per named row, one wavefront each; sml_als_supports names the (d, elem_bytes) pairs (any
+// other is hipErrorInvalidValue / false).  No atomics, no allocation, copy or synchronise.  The host walks are the same
+// definitions over host memory
+bool sml_als_supports(int d, int elem_bytes);
+int64_t sml_gram_chunks(int64_t n_rows);
+hipError_t sml_launch_gram(int d, int elem_bytes, const void* w, int64_t n_rows, double* part, double* gram, hipStream_t st);
+bool sml_gram_host_walk(int d, int elem_bytes, const void* w, int64_t n_rows, double* gram);
+hipError_t sml_launch_als_solve(int d, int elem_bytes, const void* w_other, const double* gram, double alpha0, double reg, const int64_t* set_off,
+                                const int32_t* set_items, const int64_t* rows, int64_t n, void* w_out, int max_workgroups, int32_t* status,
+                                hipStream_t st);
+bool sml_als_host_walk(int d, int elem_bytes, const void* w_other, const double* gram, double alpha0, double reg, const int64_t* set_off,
+                       const int32_t* set_items, const int64_t* rows, int64_t n, void* w_out, int32_t* status);
 // deep lists (sml_topk_deep, include/sml_hip.h): 1 <= k <= 1024 by a per-user radix select, a fixed number of catalogue walks
 // whatever k is; slices 0 = the planner's, 1 .. 256 forced.  scratch: sml_topk_deep_scratch_size bytes.  No allocation, copy to
 // the host or synchronise.  sml_topk_host_walk: the same definition as a single-threaded walk over host memory (c holds host

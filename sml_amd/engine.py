@@ -1096,6 +1096,52 @@ class HipEngine(object):
                                          _ptr(centroids), _ptr(out), self._stream()), "sml_ivf_centroids")
         return out
 
+    def _als_table(self, t, what):
+        if t.dtype not in (torch.float32, torch.float16) or t.device != self.device or t.dim() != 2 or not t.is_contiguous() \
+                or t.shape[-1] != self.d:
+            raise ValueError("%s: expected a contiguous fp32 or fp16 [rows,%d] tensor on %s, got %s %s on %s"
+                             % (what, self.d, self.device, t.dtype, tuple(t.shape), t.device))
+        return t
+
+    def gram(self, table, n_rows=None):
+        """float64 [d, d] on the device: G = Y^T Y over the first n_rows rows (default: all) of an fp32 or fp16 table, added in
+        fp64 in the fixed chunk order of include/sml_hip.h, FOLD-IN (sml_gram: byte-defined, no atomics); d = 32 / 64."""
+        w = self._als_table(table, "gram")
+        n_rows = w.shape[0] if n_rows is None else int(n_rows)
+        if n_rows > w.shape[0]:
+            raise ValueError("gram: n_rows=%d exceeds the table's %d rows" % (n_rows, w.shape[0]))
+        scratch = self._scratch(self.lib.sml_gram_scratch_bytes(self._ctx, n_rows), "sml_gram_scratch_bytes")
+        g = torch.empty(self.d, self.d, device=self.device, dtype=torch.float64)
+        check(self.lib.sml_gram(self._ctx, _ptr(w), w.element_size(), n_rows, _ptr(scratch), _ptr(g), self._stream()), "sml_gram")
+        return g
+
+    def als_solve(self, other_tab, gram, sets, out_tab, rows=None, reg=0.1, alpha0=0.1, max_workgroups=0):
+        """The iALS half-step (include/sml_hip.h, FOLD-IN; sml_als_solve: one wavefront per row, no scratch): each named row of
+        out_tab becomes (alpha0 G + sum_{i in S} y_i y_i^T + reg I)^-1 sum_{i in S} y_i over the rows y of other_tab, S being the
+        row's range of sets = (off int64 [>= rows + 1], items int32), G = gram (float64 [d, d] from gram(); None only with
+        alpha0 == 0).  rows: int64 ids of the rows to solve (None: all rows of out_tab); out_tab is written IN PLACE and has
+        other_tab's element type.  Returns int32 status [n]: 0 solved, 1 empty set (the row is +0), 2 not solved (a pivot was
+        not positive or the solution is not finite; the row is left untouched).  max_workgroups > 0 caps the grid (the bytes
+        do not depend on it)."""
+        wo = self._als_table(other_tab, "als_solve")
+        out = self._als_table(out_tab, "als_solve")
+        if out.dtype != wo.dtype:
+            raise ValueError("als_solve: out_tab is %s, other_tab %s" % (out.dtype, wo.dtype))
+        if gram is not None and (gram.dtype != torch.float64 or gram.device != self.device or not gram.is_contiguous()
+                                 or tuple(gram.shape) != (self.d, self.d)):
+            raise ValueError("als_solve: gram must be a contiguous float64 [%d, %d] tensor on %s" % (self.d, self.d, self.device))
+        off, items = self._seen(sets)
+        if rows is not None:
+            rows = self._dev(rows, torch.int64).reshape(-1)
+        n = out.shape[0] if rows is None else rows.shape[0]
+        if off is not None and rows is None and off.shape[0] < n + 1:
+            raise ValueError("als_solve: the set has %d rows, out_tab %d" % (off.shape[0] - 1, n))
+        status = torch.empty(n, device=self.device, dtype=torch.int32)
+        check(self.lib.sml_als_solve(self._ctx, _ptr(wo), wo.element_size(), wo.shape[0], _ptr(gram), float(alpha0), float(reg), _ptr(off),
+                                     _ptr(items), _ptr(rows), n, _ptr(out), out.shape[0], int(max_workgroups), _ptr(status),
+                                     self._stream()), "sml_als_solve")
+        return status
+
     def rerank_mmr(self, item_tab, pool_items, pool_scores, k, lam, metric="cosine", normalize=True, max_workgroups=0, nrm=None):
         """Greedy MMR re-ranking of per-list pools (include/sml_hip.h, RE-RANKING; sml_rerank_mmr: one wavefront per list, no
         scratch).  pool_items int [n, C <= 128] (int64 as recommend returns them is narrowed on the device; entries outside

@@ -212,6 +212,43 @@ class MFbasemode(nn.Module):
         out.update(users=users, pos_off=pos_off, pos_items=pos_items, ks=ks)
         return out
 
+    def _fold_in_check(self):
+        from . import als
+        if isinstance(self, MF2):
+            raise ValueError("fold-in solves the bare dot-product model: MF2's biased score has no closed-form row here")
+        if self.hidden_dim not in als.WIDTHS:
+            raise ValueError("fold-in exists at laten_factor 32 / 64 only (128 is out of scope), got %d" % self.hidden_dim)
+
+    def _fold_in(self, out_emb, other_emb, sets, rows, reg, alpha0):
+        from . import als
+        with torch.no_grad():
+            return als.fold_in(out_emb.weight.data, other_emb.weight.data, sets, rows, reg=reg, alpha0=alpha0, engine=_engine_for(self))
+
+    def fold_in_users(self, history, users=None, reg=0.1, alpha0=0.1):
+        """Give users the closed-form row of the iALS half-step against the current item table (sml_amd.als.fold_in;
+        include/sml_hip.h, FOLD-IN): user_laten's rows are rewritten in place, nothing else changes.  history: the users'
+        interaction sets -- a sml_amd.retrieval.SeenItems, a DeviceSeen or a (off, items) CSR over all users.  users: the ids to
+        solve (None: every user with a non-empty history, sml_amd.retrieval.nonempty_users).  Works on fp32 and .half()
+        models at laten_factor 32 / 64; 128, or MF2's biased score, is a ValueError.  reg and alpha0 default to conventions,
+        not tuned values.  Returns a sml_amd.als.FoldIn (solved / empty / failed counts and the status per row)."""
+        from .retrieval import as_csr, nonempty_users
+        self._fold_in_check()
+        if users is None:
+            users = nonempty_users(history)[0]
+        return self._fold_in(self.user_laten, self.item_laten, as_csr(history, self.user_laten.weight.device), users, reg, alpha0)
+
+    def fold_in_items(self, history, items=None, reg=0.1, alpha0=0.1):
+        """fold_in_users with the roles swapped: items get their closed-form row against the current user table, from the
+        users that interacted with them.  history is the same user -> items set; it is transposed on the device
+        (sml_amd.als.transpose_sets).  items: the ids to solve (None: every item with at least one user)."""
+        from . import als
+        from .retrieval import as_csr, nonempty_users
+        self._fold_in_check()
+        by_item = als.transpose_sets(as_csr(history, self.user_laten.weight.device), self.user_num, self.item_num, _engine_for(self))
+        if items is None:
+            items = nonempty_users(by_item)[0]
+        return self._fold_in(self.item_laten, self.user_laten, by_item, items, reg, alpha0)
+
     def set_parameters(self, user_weight, item_weight):
         # last column is the bias (model/MF.py:108-112)
         self.user_laten.weight.data.copy_(user_weight[:, 0:-1])
