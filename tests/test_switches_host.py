@@ -13,7 +13,7 @@ CSRC = os.path.join(REPO, "sml_amd", "csrc")
 # read by bench.py, tests/ or tools/ alone: neither declaration knows them, INTEGRATION.md's table lists them
 ELSEWHERE = {"SML_A3_INPROC", "SML_A3_ORDER", "SML_BENCH_STRONG_LEG",                      # bench.py
              "SML_TEST_EIGHT_PROCESSES", "SML_TEST_JOB_TIMEOUT_S", "SML_GRAD_PIN_RATIOS",  # tests/
-             "SML_FWD_F64_RATIOS",
+             "SML_FWD_F64_RATIOS", "SML_BARE_F64_RATIOS",
              "SML_HARNESS_EXTRA_PERIODS", "SML_PREFETCH", "SML_EVS_DBG"}                   # tools/
 # (spelled without their prefix, so that this file passes its own last test)
 RETIRED = ["SML_" + n for n in ("BWD_PRE", "PEER_POLL_IN_ADAM", "REPLAY_K0", "A3_KNOWN_LISTS", "PREP_NOWAVE", "PREP_COUNT", "EVENT_FLAGS")]
