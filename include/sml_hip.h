@@ -756,6 +756,86 @@ int sml_als_solve(sml_ctx* ctx, const void* w_other, int elem_bytes, int64_t n_o
 int sml_host_als_solve(const void* w_other, int elem_bytes, int d, int64_t n_other, const double* gram,
                        double alpha0, double reg, const int64_t* set_off, const int32_t* set_items,
                        const int64_t* rows, int64_t n, void* w_out, int64_t n_out, int32_t* status);
+/* ---- NEIGHBOURS: the neighbourhood model (ItemKNN) -- item-to-item neighbours from co-occurrence, and the list of a history that
+ * has no row in any table.  One sparse operation underlies both: for a row x, accumulate over the lists of x's members and keep
+ * the K best,  out(x) = top-K over j of sum_{m in R(x)} W[m, j].  The device entry points take a context and read no embedding
+ * table, so any engine's context serves (any width, d = 128 included); the host walks take none.  All pointers of the device calls
+ * are device memory.  The only atomics are integer, exact and order-free; similarities are accumulated in fixed point; there are no
+ * floating-point atomics, so the bytes depend on no launch geometry.
+ * NEIGHBOURS OF ITEMS (sml_cooc_topk).  by_item_off / by_item_users (int64 [n_item + 1] / int32): the item -> users CSR;
+ * by_user_off / by_user_items (int64 [n_user + 1] / int32): the user -> items CSR -- the same set and its transpose, both as
+ * sml_iset_build writes them.  rows int64 [n]: the query items; rows == NULL means 0 .. n - 1.  norm_a, norm_b: double [n_item],
+ * both NULL or both given.  shrink: double >= 0.  min_co: int >= 1.  allow: filter words (ITEM FILTER), may be NULL.  1 <= k <= 128.
+ * For query item i with users U(i), S(u) the items of user u:
+ *   c(j) = #{u in U(i) : j in S(u)}, an integer;
+ *   the candidates are the j != i with c(j) >= min_co that are allowed;
+ *   without norms the score is s = (float)c;
+ *   with norms, four roundings and no contraction:  den = norm_a[i] * norm_b[j], one fp64 rounding;  den = den + shrink;
+ *     s64 = (double)c / den, the correctly rounded fp64 division;  s = (float)s64, to nearest even;
+ *   an s that is NaN is not eligible (den = 0 gives inf, which is eligible, as in the family);
+ *   the order is the family's: s descending, then id ascending.
+ * Outputs: items int32 [n, k] and sims float [n, k], missing slots hold (-1, -inf); n_elig int32 [n] (may be NULL) = the number
+ * of eligible candidates.  The definition contains no square root: the metric lives in the tables, which the caller makes (cosine:
+ * a = b = deg^1/2; asymmetric: a = deg^alpha, b = deg^(1 - alpha)).  With norm_a == norm_b the product commutes exactly, so
+ * sim(i, j) and sim(j, i) are the same bits.  With norms NULL and k >= the number of neighbours, the row is exactly the non-zero
+ * off-diagonal of row i of X^T X, X the 0/1 interaction matrix.
+ * THE LIST OF A HISTORY (sml_knn_topk).  nbr_items int32 and nbr_sims float, both [n_rows_nbr, k_nbr], 1 <= k_nbr <= 128: the
+ * output form of the call above, but any table of that shape is accepted.  hist_off / hist_items: the CSR of histories.  users
+ * int64 [n] indexes hist_off and seen_off; users == NULL means 0 .. n - 1.  frac_bits F in [0, 32].  seen_off / seen_items, allow:
+ * the family's exclusion forms.  1 <= k <= 128.
+ *   A history member m outside [0, n_rows_nbr) is skipped before any address is formed.
+ *   A neighbour slot contributes nothing when its id is outside [0, n_item), or its sim is not finite, or |q| > 2^32, where
+ *     q = llrint(ldexp((double)sim, F)), round to nearest even.
+ *   acc(j) = sum of q, an int64.  It cannot overflow: a history has < 2^31 members and j occurs at most once per list.
+ *   A candidate is every j that occurs in a contributing slot, whatever its sum: a j whose sum cancels to 0 is still a candidate
+ *     with score 0.
+ *   A candidate is eligible if it is allowed and not in Seen(users[x]).  History members are not excluded unless Seen says so.
+ *   Score A = (float)ldexp((double)acc, -F); both conversions round to nearest even.
+ *   Order, padding and n_elig are the family's.
+ * Defining identities:
+ *   - a k'-call is the prefix of a k-call;
+ *   - a filtered call equals the unfiltered call with the filter's complement added to every Seen range;
+ *   - max_workgroups and path never change a byte;
+ *   - a row named twice is written twice with the same bytes;
+ *   - a history {i} with no Seen and no filter returns item i's neighbour list, ids in the same order, and the scores are bit-equal
+ *     when every sim is a multiple of 2^-F (with F = 30: every float >= 2^-7 in magnitude).
+ * Two paths, one definition.  A row whose total list length (sum over its members of their lists' lengths, a bound on its distinct
+ * ids known before the walk) is at most sml_knn_lds_limit() accumulates in an open-addressing table in LDS of at least twice that
+ * many slots, which therefore can never fill; any other row owns a dense accumulator over [0, n_item) in scratch (int32 counts for
+ * the neighbours of items; int64 sums plus a touched bitmap for the list of a history), adds with integer atomics, and then
+ * claims every touched candidate once -- on a second walk of its lists, or from the bitmap's words when a history's lists hold more
+ * slots than the catalogue has items -- and the lane that claims it takes its sum and resets the slot.  path: 0 auto, 1 dense
+ * everywhere, 2 LDS wherever it fits.  max_workgroups = 0 leaves the grid to the call, a positive value caps it (one wavefront serves one row, rows
+ * are walked grid-stride).
+ * scratch: sml_knn_scratch_bytes(ctx, n_item, max_workgroups, kind) bytes (kind 0: neighbours of items, 1: the list of a history;
+ * < 0: bad argument) for the same n_item and max_workgroups, 256-byte aligned.  The call zeroes what it uses of its scratch at the
+ * start and leaves it zero.  No allocation, no copy to the host and no synchronise inside; n == 0 launches nothing.  Indices (rows,
+ * users, the CSRs' offsets and entries) are trusted, like Seen.
+ * Refused (sml_last_error; a refused call writes nothing): k, k_nbr, frac_bits, min_co, max_workgroups or path out of range;
+ * shrink negative or NaN; exactly one of a CSR's two pointers NULL; exactly one of the norms NULL; n_item or n_user outside
+ * (0, 2^31); a misaligned scratch; an output overlapping an input or another output, where pointers and known sizes show it.
+ * sml_host_cooc_topk / sml_host_knn_topk: the same definitions as single-threaded walks over HOST memory (a plain dense array, then
+ * a full sort by the order); they share the text of the scores with the kernels.
+ * Not measured: real periods, trained tables as the neighbour table, anything beyond the Yelp shape. */
+int sml_knn_lds_limit(void);
+int64_t sml_knn_scratch_bytes(sml_ctx* ctx, int64_t n_item, int max_workgroups, int kind);
+int sml_cooc_topk(sml_ctx* ctx, const int64_t* by_item_off, const int32_t* by_item_users,
+                  const int64_t* by_user_off, const int32_t* by_user_items, int64_t n_user, int64_t n_item,
+                  const int64_t* rows, int64_t n, const double* norm_a, const double* norm_b, double shrink, int min_co,
+                  const uint32_t* allow, int k, int max_workgroups, int path, void* scratch,
+                  int32_t* items, float* sims, int32_t* n_elig, void* stream);
+int sml_host_cooc_topk(const int64_t* by_item_off, const int32_t* by_item_users,
+                       const int64_t* by_user_off, const int32_t* by_user_items, int64_t n_user, int64_t n_item,
+                       const int64_t* rows, int64_t n, const double* norm_a, const double* norm_b, double shrink, int min_co,
+                       const uint32_t* allow, int k, int32_t* items, float* sims, int32_t* n_elig);
+int sml_knn_topk(sml_ctx* ctx, const int32_t* nbr_items, const float* nbr_sims, int64_t n_rows_nbr, int k_nbr, int64_t n_item,
+                 const int64_t* hist_off, const int32_t* hist_items, const int64_t* users, int64_t n, int frac_bits,
+                 const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int k,
+                 int max_workgroups, int path, void* scratch, int32_t* items, float* scores, int32_t* n_elig, void* stream);
+int sml_host_knn_topk(const int32_t* nbr_items, const float* nbr_sims, int64_t n_rows_nbr, int k_nbr, int64_t n_item,
+                      const int64_t* hist_off, const int32_t* hist_items, const int64_t* users, int64_t n, int frac_bits,
+                      const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int k,
+                      int32_t* items, float* scores, int32_t* n_elig);
 /* ---- DEEP LISTS: candidate generation at depth -- lists of up to 1,024 items per user over the whole catalogue, for a
  * downstream re-ranker, a recall@K curve or a pool.  sml_topk_items keeps a sorted list per (user, slice) and its cost grows
  * with k; sml_topk_deep selects by radix: a fixed number of catalogue walks (four counting passes over the order-preserving

@@ -157,6 +157,18 @@ SIGNATURES = {
                                      c_void, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void]),
     "sml_host_als_solve": (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_double, ctypes.c_double, c_void,
                                           c_void, c_void, ctypes.c_int64, c_void, ctypes.c_int64, c_void]),
+    "sml_knn_lds_limit": (ctypes.c_int, []),
+    "sml_knn_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "sml_cooc_topk": (ctypes.c_int, [c_void, c_void, c_void, c_void, c_void, ctypes.c_int64, ctypes.c_int64, c_void, ctypes.c_int64, c_void,
+                                     c_void, ctypes.c_double, ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, c_void,
+                                     c_void, c_void, c_void]),
+    "sml_host_cooc_topk": (ctypes.c_int, [c_void, c_void, c_void, c_void, ctypes.c_int64, ctypes.c_int64, c_void, ctypes.c_int64, c_void,
+                                          c_void, ctypes.c_double, ctypes.c_int, c_void, ctypes.c_int, c_void, c_void, c_void]),
+    "sml_knn_topk": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void,
+                                    ctypes.c_int64, ctypes.c_int, c_void, c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void,
+                                    c_void, c_void, c_void, c_void]),
+    "sml_host_knn_topk": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void,
+                                         ctypes.c_int64, ctypes.c_int, c_void, c_void, c_void, ctypes.c_int, c_void, c_void, c_void]),
     "sml_topk_deep_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
     "sml_topk_deep": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
                                      c_void, c_void, ctypes.c_int, c_void, c_void, c_void, c_void, c_void]),

@@ -2186,6 +2186,119 @@ int sml_host_als_solve(const void* w_other, int elem_bytes, int d, int64_t n_oth
     return SML_OK;
 }
 
+// neighbours: what the device calls and the host walks refuse alike (NULL: nothing).  The CSRs, Seen and the neighbour table's
+// height are of unknown extent where the arguments do not give it: they count from their first entry only
+struct KnnSpan { const void* p; int64_t bytes; };
+
+static const char* knn_overlap(const KnnSpan* in, int n_in, const KnnSpan (&out)[4]) {
+    for (const auto& o : out)
+        for (int i = 0; i < n_in; ++i)
+            if (iset_overlap(o.p, o.bytes, in[i].p, in[i].bytes)) return "an output overlaps an input";
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            if (iset_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) return "the outputs overlap each other";
+    return nullptr;
+}
+
+static const char* cooc_refusal(const SmlCooc& a, int max_workgroups, int path, const void* scratch, int64_t scratch_bytes, const int32_t* items,
+                                const float* sims, const int32_t* n_elig, bool device) {
+    if (a.k < 1 || a.k > 128) return "bad argument (1 <= k <= 128)";
+    if (a.min_co < 1) return "bad argument (min_co >= 1)";
+    if (max_workgroups < 0 || path < 0 || path > 2) return "bad argument (max_workgroups >= 0, path 0 / 1 / 2)";
+    if (!(a.shrink >= 0.0)) return "bad argument (shrink must be >= 0)";
+    if ((!a.item_off) != (!a.item_users) || (!a.user_off) != (!a.user_items)) return "bad argument (a CSR's two pointers both or neither)";
+    if ((!a.norm_a) != (!a.norm_b)) return "bad argument (norm_a and norm_b both or neither)";
+    if (a.n_item <= 0 || a.n_item >= ((int64_t)1 << 31) || a.n_user <= 0 || a.n_user >= ((int64_t)1 << 31) || a.n < 0 || a.n >= ((int64_t)1 << 31))
+        return "bad argument (0 < n_user < 2^31, 0 < n_item < 2^31, 0 <= n < 2^31)";
+    if (device && ((uintptr_t)scratch & 255)) return "scratch must be 256-byte aligned";
+    if (a.n == 0) return nullptr;
+    if (!items || !sims || (device && !scratch) || (a.item_off && !a.user_off)) return "null argument";
+    const int64_t ob = 4 * a.n * (int64_t)a.k;
+    const KnnSpan in[] = {{a.item_off, 8 * (a.n_item + 1)}, {a.item_users, 4}, {a.user_off, 8 * (a.n_user + 1)}, {a.user_items, 4},
+                          {a.rows, 8 * a.n}, {a.norm_a, 8 * a.n_item}, {a.norm_b, 8 * a.n_item}, {a.allow, (a.n_item + 31) / 32 * 4}};
+    const KnnSpan out[4] = {{items, ob}, {sims, ob}, {n_elig, 4 * a.n}, {scratch, scratch_bytes}};
+    return knn_overlap(in, 8, out);
+}
+
+static const char* knn_refusal(const SmlKnn& a, int max_workgroups, int path, const void* scratch, int64_t scratch_bytes, const int32_t* items,
+                               const float* scores, const int32_t* n_elig, bool device) {
+    if (a.k < 1 || a.k > 128 || a.k_nbr < 1 || a.k_nbr > 128) return "bad argument (1 <= k <= 128, 1 <= k_nbr <= 128)";
+    if (a.frac_bits < 0 || a.frac_bits > 32) return "bad argument (0 <= frac_bits <= 32)";
+    if (max_workgroups < 0 || path < 0 || path > 2) return "bad argument (max_workgroups >= 0, path 0 / 1 / 2)";
+    if ((!a.hist_off) != (!a.hist_items) || (!a.seen_off) != (!a.seen_items)) return "bad argument (a CSR's two pointers both or neither)";
+    if (a.n_item <= 0 || a.n_item >= ((int64_t)1 << 31) || a.n_rows_nbr < 0 || a.n_rows_nbr >= ((int64_t)1 << 31) || a.n < 0 ||
+        a.n >= ((int64_t)1 << 31))
+        return "bad argument (0 < n_item < 2^31, 0 <= n_rows_nbr < 2^31, 0 <= n < 2^31)";
+    if (device && ((uintptr_t)scratch & 255)) return "scratch must be 256-byte aligned";
+    if (a.n == 0) return nullptr;
+    if (!items || !scores || (device && !scratch) || (a.n_rows_nbr > 0 && (!a.nbr_items || !a.nbr_sims))) return "null argument";
+    const int64_t ob = 4 * a.n * (int64_t)a.k, nb = 4 * a.n_rows_nbr * (int64_t)a.k_nbr;
+    const KnnSpan in[] = {{a.nbr_items, nb}, {a.nbr_sims, nb}, {a.hist_off, a.users ? 8 : 8 * (a.n + 1)}, {a.hist_items, 4},
+                          {a.users, 8 * a.n}, {a.seen_off, a.users ? 8 : 8 * (a.n + 1)}, {a.seen_items, 4}, {a.allow, (a.n_item + 31) / 32 * 4}};
+    const KnnSpan out[4] = {{items, ob}, {scores, ob}, {n_elig, 4 * a.n}, {scratch, scratch_bytes}};
+    return knn_overlap(in, 8, out);
+}
+
+int sml_knn_lds_limit(void) { return sml_knn_lds_entries(); }
+
+int64_t sml_knn_scratch_bytes(sml_ctx* ctx, int64_t n_item, int max_workgroups, int kind) {
+    if (!ctx || n_item <= 0 || n_item >= ((int64_t)1 << 31) || max_workgroups < 0 || (kind != 0 && kind != 1))
+        return fail(SML_EINVAL, "sml_knn_scratch_bytes", "bad argument (0 < n_item < 2^31, max_workgroups >= 0, kind 0 / 1)");
+    return sml_knn_scratch_size(n_item, max_workgroups, kind);
+}
+
+int sml_cooc_topk(sml_ctx* ctx, const int64_t* by_item_off, const int32_t* by_item_users, const int64_t* by_user_off,
+                  const int32_t* by_user_items, int64_t n_user, int64_t n_item, const int64_t* rows, int64_t n, const double* norm_a,
+                  const double* norm_b, double shrink, int min_co, const uint32_t* allow, int k, int max_workgroups, int path, void* scratch,
+                  int32_t* items, float* sims, int32_t* n_elig, void* stream) {
+    const char* what = "sml_cooc_topk";
+    if (!ctx) return fail(SML_EINVAL, what, "null argument");
+    const SmlCooc a = {by_item_off, by_item_users, by_user_off, by_user_items, n_user, n_item, rows, n, norm_a, norm_b, shrink, min_co, allow, k};
+    const int64_t sb = n_item > 0 && n_item < ((int64_t)1 << 31) && max_workgroups >= 0 ? sml_knn_scratch_size(n_item, max_workgroups, 0) : 0;
+    if (const char* why = cooc_refusal(a, max_workgroups, path, scratch, sb, items, sims, n_elig, true)) return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_cooc_topk(a, max_workgroups, path, scratch, items, sims, n_elig, st)));
+    return SML_OK;
+}
+
+int sml_host_cooc_topk(const int64_t* by_item_off, const int32_t* by_item_users, const int64_t* by_user_off, const int32_t* by_user_items,
+                       int64_t n_user, int64_t n_item, const int64_t* rows, int64_t n, const double* norm_a, const double* norm_b,
+                       double shrink, int min_co, const uint32_t* allow, int k, int32_t* items, float* sims, int32_t* n_elig) {
+    const char* what = "sml_host_cooc_topk";
+    const SmlCooc a = {by_item_off, by_item_users, by_user_off, by_user_items, n_user, n_item, rows, n, norm_a, norm_b, shrink, min_co, allow, k};
+    if (const char* why = cooc_refusal(a, 0, 0, nullptr, 0, items, sims, n_elig, false)) return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    sml_cooc_host_walk(a, items, sims, n_elig);
+    return SML_OK;
+}
+
+int sml_knn_topk(sml_ctx* ctx, const int32_t* nbr_items, const float* nbr_sims, int64_t n_rows_nbr, int k_nbr, int64_t n_item,
+                 const int64_t* hist_off, const int32_t* hist_items, const int64_t* users, int64_t n, int frac_bits, const int64_t* seen_off,
+                 const int32_t* seen_items, const uint32_t* allow, int k, int max_workgroups, int path, void* scratch, int32_t* items,
+                 float* scores, int32_t* n_elig, void* stream) {
+    const char* what = "sml_knn_topk";
+    if (!ctx) return fail(SML_EINVAL, what, "null argument");
+    const SmlKnn a = {nbr_items, nbr_sims, n_rows_nbr, k_nbr, n_item, hist_off, hist_items, users, n, frac_bits, seen_off, seen_items, allow, k};
+    const int64_t sb = n_item > 0 && n_item < ((int64_t)1 << 31) && max_workgroups >= 0 ? sml_knn_scratch_size(n_item, max_workgroups, 1) : 0;
+    if (const char* why = knn_refusal(a, max_workgroups, path, scratch, sb, items, scores, n_elig, true)) return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_knn_topk(a, max_workgroups, path, scratch, items, scores, n_elig, st)));
+    return SML_OK;
+}
+
+int sml_host_knn_topk(const int32_t* nbr_items, const float* nbr_sims, int64_t n_rows_nbr, int k_nbr, int64_t n_item, const int64_t* hist_off,
+                      const int32_t* hist_items, const int64_t* users, int64_t n, int frac_bits, const int64_t* seen_off,
+                      const int32_t* seen_items, const uint32_t* allow, int k, int32_t* items, float* scores, int32_t* n_elig) {
+    const char* what = "sml_host_knn_topk";
+    const SmlKnn a = {nbr_items, nbr_sims, n_rows_nbr, k_nbr, n_item, hist_off, hist_items, users, n, frac_bits, seen_off, seen_items, allow, k};
+    if (const char* why = knn_refusal(a, 0, 0, nullptr, 0, items, scores, n_elig, false)) return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    sml_knn_host_walk(a, items, scores, n_elig);
+    return SML_OK;
+}
+
 // deep lists: what sml_topk_deep and sml_host_topk_items refuse alike (NULL: nothing).  The tables' heights are unknown: they
 // count from their first row only
 static const char* deep_refusal(int d, int elem_bytes, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,

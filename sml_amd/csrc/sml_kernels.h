@@ -474,6 +474,49 @@ hipError_t sml_launch_als_solve(int d, int elem_bytes, const void* w_other, cons
                                 hipStream_t st);
 bool sml_als_host_walk(int d, int elem_bytes, const void* w_other, const double* gram, double alpha0, double reg, const int64_t* set_off,
                        const int32_t* set_items, const int64_t* rows, int64_t n, void* w_out, int32_t* status);
+// knn.hip: the neighbourhood model (include/sml_hip.h, NEIGHBOURS) -- co-occurrence neighbours of items and the list of a
+// history, one wavefront per row.  scratch: sml_knn_scratch_size(n_item, max_workgroups, kind) bytes (kind 0: counts, 1: sums),
+// zeroed by the launch and left zero; path 0 auto, 1 dense everywhere, 2 LDS wherever it fits (never changes a byte).  Only
+// integer atomics; no allocation, copy to the host or synchronise.  The host walks are the same definitions over host memory
+struct SmlCooc {
+    const int64_t* item_off;
+    const int32_t* item_users;
+    const int64_t* user_off;
+    const int32_t* user_items;
+    int64_t n_user, n_item;
+    const int64_t* rows;
+    int64_t n;
+    const double* norm_a;
+    const double* norm_b;
+    double shrink;
+    int min_co;
+    const uint32_t* allow;
+    int k;
+};
+struct SmlKnn {
+    const int32_t* nbr_items;
+    const float* nbr_sims;
+    int64_t n_rows_nbr;
+    int k_nbr;
+    int64_t n_item;
+    const int64_t* hist_off;
+    const int32_t* hist_items;
+    const int64_t* users;
+    int64_t n;
+    int frac_bits;
+    const int64_t* seen_off;
+    const int32_t* seen_items;
+    const uint32_t* allow;
+    int k;
+};
+int sml_knn_lds_entries(void);
+int64_t sml_knn_scratch_size(int64_t n_item, int max_workgroups, int kind);
+hipError_t sml_launch_cooc_topk(const SmlCooc& a, int max_workgroups, int path, void* scratch, int32_t* items, float* sims, int32_t* n_elig,
+                                hipStream_t st);
+hipError_t sml_launch_knn_topk(const SmlKnn& a, int max_workgroups, int path, void* scratch, int32_t* items, float* scores, int32_t* n_elig,
+                               hipStream_t st);
+void sml_cooc_host_walk(const SmlCooc& a, int32_t* items, float* sims, int32_t* n_elig);
+void sml_knn_host_walk(const SmlKnn& a, int32_t* items, float* scores, int32_t* n_elig);
 // deep lists (sml_topk_deep, include/sml_hip.h): 1 <= k <= 1024 by a per-user radix select, a fixed number of catalogue walks
 // whatever k is; slices 0 = the planner's, 1 .. 256 forced.  scratch: sml_topk_deep_scratch_size bytes.  No allocation, copy to
 // the host or synchronise.  sml_topk_host_walk: the same definition as a single-threaded walk over host memory (c holds host

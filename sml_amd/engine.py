@@ -1142,6 +1142,84 @@ class HipEngine(object):
                                      self._stream()), "sml_als_solve")
         return status
 
+    # ------------------------------------------------------------------ neighbourhood model (knn.hip)
+    def knn_lds_limit(self):
+        """The largest total list length of a row that accumulates on chip (sml_knn_lds_limit)."""
+        return int(self.lib.sml_knn_lds_limit())
+
+    def _knn_scratch(self, n_item, n, max_workgroups, kind):
+        """(scratch, max_workgroups) of a call over n rows.  With the grid left to the call, a call of few rows asks for n
+        workgroups when that makes the scratch smaller: a row never needs more than one, and the grid never changes a byte."""
+        mw = int(max_workgroups)
+        nbytes = self.lib.sml_knn_scratch_bytes(self._ctx, int(n_item), mw, kind)
+        if mw == 0 and n > 0 and nbytes > 0:
+            fewer = self.lib.sml_knn_scratch_bytes(self._ctx, int(n_item), int(n), kind)
+            if 0 < fewer < nbytes:
+                mw, nbytes = int(n), fewer
+        return self._scratch(nbytes, "sml_knn_scratch_bytes"), mw
+
+    def _knn_out(self, n, k):
+        return (torch.empty(n, max(k, 0), device=self.device, dtype=torch.int32),
+                torch.empty(n, max(k, 0), device=self.device, dtype=torch.float32),
+                torch.empty(n, device=self.device, dtype=torch.int32))
+
+    def cooc_topk(self, by_item, by_user, k, rows=None, norm=None, shrink=0.0, min_co=1, allow=None, max_workgroups=0, path=0):
+        """(int64 items [n, k], float32 sims [n, k], int32 n_elig [n]): the co-occurrence neighbours of the query items (include/
+        sml_hip.h, NEIGHBOURS; sml_cooc_topk: one wavefront per row, integer atomics only).  by_item = (off int64 [n_item + 1],
+        users int32) and by_user = (off int64 [n_user + 1], items int32) are the set and its transpose as iset_build writes them.
+        rows: int64 query items (None: all).  norm: None -- the score is the count -- or a float64 [n_item] table (a = b) or a
+        pair (a, b) of them: sim = count / (a[i] * b[j] + shrink).  min_co: the smallest count that makes a neighbour; allow: an
+        item filter on the neighbours.  Score descending then id ascending; missing slots (-1, -inf).  max_workgroups > 0 caps the
+        grid and path forces the accumulator (0 auto, 1 dense, 2 LDS where it fits); neither changes a byte.  No read-back."""
+        i_off, i_users = self._seen(by_item)
+        u_off, u_items = self._seen(by_user)
+        n_item, n_user = i_off.shape[0] - 1, u_off.shape[0] - 1
+        allow = self._allow(allow, n_item)
+        if norm is None:
+            na = nb = None
+        else:
+            na, nb = norm if isinstance(norm, (tuple, list)) else (norm, norm)
+            for t in (na, nb):
+                if t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n_item,):
+                    raise ValueError("cooc_topk: a norm table is a contiguous float64 [%d] tensor on %s" % (n_item, self.device))
+        if rows is not None:
+            rows = self._dev(rows, torch.int64).reshape(-1)
+        n, k = n_item if rows is None else rows.shape[0], int(k)
+        scratch, mw = self._knn_scratch(n_item, n, max_workgroups, 0)
+        items, sims, n_elig = self._knn_out(n, k)
+        check(self.lib.sml_cooc_topk(self._ctx, _ptr(i_off), _ptr(i_users), _ptr(u_off), _ptr(u_items), n_user, n_item, _ptr(rows), n,
+                                     _ptr(na), _ptr(nb), float(shrink), int(min_co), _ptr(allow), k, mw, int(path),
+                                     _ptr(scratch), _ptr(items), _ptr(sims), _ptr(n_elig), self._stream()), "sml_cooc_topk")
+        return items.long(), sims, n_elig
+
+    def knn_topk(self, nbr_items, nbr_sims, n_item, history, k, users=None, frac_bits=30, seen=None, allow=None, max_workgroups=0,
+                 path=0):
+        """(int64 items [n, k], float32 scores [n, k], int32 n_elig [n]): the list of each history under a neighbour table
+        (include/sml_hip.h, NEIGHBOURS; sml_knn_topk).  nbr_items int [n_rows, k_nbr] / nbr_sims float32 [n_rows, k_nbr]: what
+        cooc_topk returns, or any table of that shape; history = (off, items): the CSR of histories; users: int64 rows of
+        history and seen (None: all).  A candidate's score is the sum, in fixed point with frac_bits fractional bits, of its sims
+        over the history's members' lists; candidates in seen or outside allow are left out.  Score descending then id
+        ascending; missing slots (-1, -inf).  max_workgroups and path as in cooc_topk.  No read-back."""
+        nbr_items = self._dev(nbr_items, torch.int32)
+        nbr_sims = self._dev(nbr_sims, torch.float32)
+        if nbr_items.dim() != 2 or nbr_items.shape != nbr_sims.shape:
+            raise ValueError("knn_topk: nbr_items and nbr_sims are [n_rows, k_nbr], got %s and %s"
+                             % (tuple(nbr_items.shape), tuple(nbr_sims.shape)))
+        n_item = int(n_item)
+        h_off, h_items = self._seen(history)
+        if users is not None:
+            users = self._dev(users, torch.int64).reshape(-1)
+        n, k = h_off.shape[0] - 1 if users is None else users.shape[0], int(k)
+        s_off, s_items = self._seen(seen)
+        allow = self._allow(allow, n_item)
+        scratch, mw = self._knn_scratch(n_item, n, max_workgroups, 1)
+        items, scores, n_elig = self._knn_out(n, k)
+        check(self.lib.sml_knn_topk(self._ctx, _ptr(nbr_items), _ptr(nbr_sims), nbr_items.shape[0], nbr_items.shape[1], n_item,
+                                    _ptr(h_off), _ptr(h_items), _ptr(users), n, int(frac_bits), _ptr(s_off), _ptr(s_items), _ptr(allow),
+                                    k, mw, int(path), _ptr(scratch), _ptr(items), _ptr(scores), _ptr(n_elig),
+                                    self._stream()), "sml_knn_topk")
+        return items.long(), scores, n_elig
+
     def rerank_mmr(self, item_tab, pool_items, pool_scores, k, lam, metric="cosine", normalize=True, max_workgroups=0, nrm=None):
         """Greedy MMR re-ranking of per-list pools (include/sml_hip.h, RE-RANKING; sml_rerank_mmr: one wavefront per list, no
         scratch).  pool_items int [n, C <= 128] (int64 as recommend returns them is narrowed on the device; entries outside

@@ -174,6 +174,42 @@ def recall_curve(model, held_out, ks, exclude=None, items=None, score=None):
     return [float(np.mean(hits[:, k].astype(np.float64) / m.astype(np.float64))) for k in ks]
 
 
+def recall_of_lists(lists, users, held_out, ks):
+    """[recall@K for K in ks] of lists that are given rather than made: lists int [n, >= max(ks)] (a tensor or an array; -1 pads
+    a short list) belongs row by row to `users` [n]; the value is the mean, over the rows whose user has a non-empty held-out set
+    T(u), of |first K of the row AND T(u)| / |T(u)| -- the list half of recall_curve, for any source of lists (a neighbourhood
+    model has no tables for recall_curve to call).  held_out: a sml_amd.retrieval.SeenItems (retrieval.held_out) or a (off,
+    items) CSR over all users.  With users = retrieval.nonempty_users(held_out)[0] and lists = model.recommend(users, max(ks),
+    exclude=e)[0] the result equals recall_curve(model, held_out, ks, exclude=e)."""
+    from .retrieval import DeviceSeen, SeenItems
+    ks = [int(k) for k in ks]
+    if not ks:
+        return []
+    lists = np.asarray(lists.cpu() if torch.is_tensor(lists) else lists).astype(np.int64)
+    users = np.asarray(users.cpu() if torch.is_tensor(users) else users).astype(np.int64).reshape(-1)
+    if lists.ndim != 2 or lists.shape[0] != len(users) or min(ks) < 1 or max(ks) > lists.shape[1]:
+        raise ValueError("recall_of_lists: lists is [len(users), >= max(ks)] and every K >= 1, got %s for %d users and ks %s"
+                         % (lists.shape, len(users), ks))
+    off, held_items = held_out.host() if isinstance(held_out, (SeenItems, DeviceSeen)) else \
+        (np.asarray(t.cpu() if torch.is_tensor(t) else t) for t in held_out)
+    off, held_items = np.asarray(off, dtype=np.int64), np.asarray(held_items, dtype=np.int64)
+    m = off[users + 1] - off[users]
+    keep = m > 0
+    if not keep.any():
+        return [0.0 for _ in ks]
+    lists, users, m = lists[keep], users[keep], m[keep]
+    row = np.arange(len(users), dtype=np.int64)
+    start = np.cumsum(m) - m
+    pos_items = held_items[np.repeat(off[users] - start, m) + np.arange(int(m.sum()), dtype=np.int64)]
+    base = int(max(lists.max(), pos_items.max())) + 1
+    held = np.repeat(row, m) * base + pos_items                                 # ascending: rows ascend, items ascend inside a row
+    keys = row[:, None] * base + lists
+    at = np.minimum(np.searchsorted(held, keys), len(held) - 1)
+    hit = (lists >= 0) & (held[at] == keys)
+    hits = np.concatenate([np.zeros((len(users), 1), np.int64), np.cumsum(hit, axis=1)], axis=1)
+    return [float(np.mean(hits[:, k].astype(np.float64) / m.astype(np.float64))) for k in ks]
+
+
 def index_recall(model, index, users, topK=20, nprobe=None, exclude=None):
     """What the approximation of MFbasemode.recommend(index=) costs: the mean over `users` of
     |indexed list AND exact list| / (number of live slots of the exact list), the two lists being recommend(users, topK,
