@@ -836,6 +836,57 @@ int sml_host_knn_topk(const int32_t* nbr_items, const float* nbr_sims, int64_t n
                       const int64_t* hist_off, const int32_t* hist_items, const int64_t* users, int64_t n, int frac_bits,
                       const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int k,
                       int32_t* items, float* scores, int32_t* n_elig);
+/* ---- PROPAGATION: one hop along the user-item graph -- the LightGCN layer E' = D^-1/2 A D^-1/2 E, and a plain smoothing operator
+ * in its own right.  One sparse-times-dense product underlies it:  out[x] = a[row] * sum_{m in S(row)} b[m] * src[m].
+ * With src the item table, S the user -> items set, a = deg_u^-1/2 and b = deg_i^-1/2 it is the user half of a layer; the item half
+ * is the same call on the transposed set with the two scale tables swapped, and so is the transpose of either (the operator is
+ * linear), which makes the backward pass the same call.  Every fp32 operation and its order are named below, so the bytes depend
+ * on no launch geometry; the host walk shares the text of the steps with the kernels, compiled so that nothing is contracted or
+ * reassociated: every fused step is an explicit fmaf().  There are no floating-point atomics and no matrix instructions.
+ * Inputs: src [n_src, d] of element type T -- fp32 (elem_bytes 4) or fp16 (elem_bytes 2) -- and width d = 32 / 64 / 128, the
+ * context's; all six pairs are accepted.  set_off int64 / set_items int32: the CSR of members, ids ascending, as sml_iset_build
+ * writes them.  rows int64 [n], may be NULL: rows == NULL means rows 0 .. n - 1; rows[x] indexes set_off and a.  a: float indexed
+ * by row id (at least max(rows) + 1 entries); b: float [n_src]; either may be NULL, which means 1.0f.  out: float [n, d] whatever
+ * T is; out[x] belongs to rows[x].
+ * For a row with members m_0 < m_1 < ... < m_{L-1} at positions p = 0 .. L - 1, and for every dimension s:
+ *   1. position p belongs to segment c = p / SML_PROP_SEG and to strand j = p % SML_PROP_STRANDS; SML_PROP_SEG = 256 and
+ *      SML_PROP_STRANDS = 8 are constants of the definition;
+ *   2. per (c, j), over the positions of that segment and strand ascending: acc = +0.0f, then
+ *      acc = fmaf(b[m_p], (float)src[m_p][s], acc);
+ *   3. the segment value is a fixed tree of fp32 adds: u_j = acc_j + acc_{j+4} for j = 0 .. 3; v_j = u_j + u_{j+2} for j = 0, 1;
+ *      seg_c = v_0 + v_1;
+ *   4. tot = +0.0f, then for c ascending: tot = tot + seg_c;
+ *   5. out[x][s] = a[row] * tot, one fp32 rounding.
+ * An empty set gives a[row] * +0.0f.  NaN / Inf propagate with no special case.  A row named twice is written twice with the same
+ * bytes.  The fp16 result equals the result on the widened fp32 copy bit for bit (the widening is exact).
+ * Two paths, one definition.  A row of fewer than sml_graph_split_from() segments is summed by one wavefront; any other row has
+ * its segments summed by separate wavefronts into scratch, and a further pass adds them in segment order (step 4).  path: 0 auto,
+ * 1 never split (scratch is not touched and may be NULL), 2 split every row of more than one segment.  max_workgroups = 0 leaves
+ * the grid to the call, a positive value caps it.  Neither ever changes a byte.
+ * scratch: sml_graph_scratch_bytes(ctx, n, nnz, max_workgroups) bytes of device memory, 256-byte aligned, for the same n; nnz is
+ * the number of members of the n named rows, a row named twice counted twice (rows == NULL: set_off[n]) -- a larger value is
+ * fine, a smaller one is not: the call cannot check it.  < 0: bad argument.  The scratch holds nothing between calls.
+ * No allocation, no copy to the host and no synchronise inside; n == 0 launches nothing.  The only atomic is an integer one (a
+ * split row reserves its slots of scratch).  Indices (rows, set_off, set_items) are trusted, like Seen.
+ * Refused (sml_last_error; a refused call writes nothing): elem_bytes outside {2, 4}; a width other than 32 / 64 / 128; n_src
+ * outside (0, 2^31) or n outside [0, 2^31); max_workgroups < 0 or path outside 0 .. 2; exactly one of set_off / set_items NULL
+ * (both NULL: every set is empty); a scratch not 256-byte aligned, or a src or out not 16-byte aligned; out overlapping src, the
+ * set, rows, a, b or the scratch, where the pointers and known sizes show it.
+ * sml_host_graph_propagate: the same definition as a single-threaded walk over HOST memory; d is the caller's (no context),
+ * there is no scratch and nothing has to be aligned.
+ * Not measured: trained tables, the recall of a fitted LightGCN on real periods, shapes beyond the Yelp one. */
+#define SML_PROP_SEG 256
+#define SML_PROP_STRANDS 8
+/* the number of segments from which a row is split (a measured value) */
+int sml_graph_split_from(void);
+int64_t sml_graph_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t nnz, int max_workgroups);
+int sml_graph_propagate(sml_ctx* ctx, const void* src, int elem_bytes, int64_t n_src,
+                        const int64_t* set_off, const int32_t* set_items, const int64_t* rows, int64_t n,
+                        const float* a, const float* b, int max_workgroups, int path, void* scratch,
+                        float* out, void* stream);
+int sml_host_graph_propagate(const void* src, int elem_bytes, int d, int64_t n_src,
+                             const int64_t* set_off, const int32_t* set_items, const int64_t* rows, int64_t n,
+                             const float* a, const float* b, float* out);
 /* ---- DEEP LISTS: candidate generation at depth -- lists of up to 1,024 items per user over the whole catalogue, for a
  * downstream re-ranker, a recall@K curve or a pool.  sml_topk_items keeps a sorted list per (user, slice) and its cost grows
  * with k; sml_topk_deep selects by radix: a fixed number of catalogue walks (four counting passes over the order-preserving

@@ -169,6 +169,12 @@ SIGNATURES = {
                                     c_void, c_void, c_void, c_void]),
     "sml_host_knn_topk": (ctypes.c_int, [c_void, c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void,
                                          ctypes.c_int64, ctypes.c_int, c_void, c_void, c_void, ctypes.c_int, c_void, c_void, c_void]),
+    "sml_graph_split_from": (ctypes.c_int, []),
+    "sml_graph_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "sml_graph_propagate": (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void, ctypes.c_int64, c_void,
+                                           c_void, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void]),
+    "sml_host_graph_propagate": (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void, ctypes.c_int64,
+                                                c_void, c_void, c_void]),
     "sml_topk_deep_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
     "sml_topk_deep": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int, c_void, c_void,
                                      c_void, c_void, ctypes.c_int, c_void, c_void, c_void, c_void, c_void]),

@@ -2299,6 +2299,61 @@ int sml_host_knn_topk(const int32_t* nbr_items, const float* nbr_sims, int64_t n
     return SML_OK;
 }
 
+// propagation: what the device call and the host walk refuse alike (NULL: nothing).  The set's items, a and the scratch's slot
+// records are of unknown extent: they count from their first entry, respectively up to what n alone fixes
+static const char* graph_refusal(int d, int elem_bytes, const void* src, int64_t n_src, const int64_t* set_off, const int32_t* set_items,
+                                 const int64_t* rows, int64_t n, const float* a, const float* b, int max_workgroups, int path,
+                                 const void* scratch, const float* out, bool device) {
+    if (elem_bytes != 2 && elem_bytes != 4) return "bad argument (elem_bytes 4: fp32 rows, 2: fp16 rows)";
+    if (!sml_graph_supports(d, elem_bytes)) return "bad argument (d = 32 / 64 / 128)";
+    if (n_src <= 0 || n_src >= ((int64_t)1 << 31) || n < 0 || n >= ((int64_t)1 << 31)) return "bad argument (0 < n_src < 2^31, 0 <= n < 2^31)";
+    if (max_workgroups < 0 || path < 0 || path > 2) return "bad argument (max_workgroups >= 0, path 0 / 1 / 2)";
+    if ((!set_off) != (!set_items)) return "bad argument (set_off and set_items both or neither)";
+    if (device && ((uintptr_t)scratch & 255)) return "scratch must be 256-byte aligned";
+    if (device && (((uintptr_t)src | (uintptr_t)out) & 15)) return "src and out must be 16-byte aligned";
+    if (n == 0) return nullptr;
+    if (!src || !out || (device && !scratch && path != 1 && set_off)) return "null argument";
+    const int64_t ob = 4 * n * (int64_t)d;
+    const KnnSpan in[] = {{src, n_src * d * elem_bytes}, {set_off, rows ? 8 : 8 * (n + 1)}, {set_items, 4}, {rows, 8 * n}, {a, rows ? 4 : 4 * n},
+                          {b, 4 * n_src}, {scratch, scratch ? sml_graph_scratch_size(d, n, 0) : 0}};
+    for (const auto& i : in)
+        if (iset_overlap(out, ob, i.p, i.bytes)) return "out overlaps an input or the scratch";
+    return nullptr;
+}
+
+int sml_graph_split_from(void) { return sml_graph_split_segments(); }
+
+int64_t sml_graph_scratch_bytes(sml_ctx* ctx, int64_t n, int64_t nnz, int max_workgroups) {
+    if (!ctx || n < 0 || n >= ((int64_t)1 << 31) || nnz < 0 || max_workgroups < 0)
+        return fail(SML_EINVAL, "sml_graph_scratch_bytes", "bad argument (0 <= n < 2^31, nnz >= 0, max_workgroups >= 0)");
+    return sml_graph_scratch_size(ctx->d, n, nnz);
+}
+
+int sml_graph_propagate(sml_ctx* ctx, const void* src, int elem_bytes, int64_t n_src, const int64_t* set_off, const int32_t* set_items,
+                        const int64_t* rows, int64_t n, const float* a, const float* b, int max_workgroups, int path, void* scratch,
+                        float* out, void* stream) {
+    const char* what = "sml_graph_propagate";
+    if (!ctx) return fail(SML_EINVAL, what, "null argument");
+    if (const char* why = graph_refusal(ctx->d, elem_bytes, src, n_src, set_off, set_items, rows, n, a, b, max_workgroups, path, scratch, out, true))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_graph_propagate(ctx->d, elem_bytes, src, set_off, set_items, rows, n, a, b, max_workgroups, path, scratch,
+                                                        out, st)));
+    return SML_OK;
+}
+
+int sml_host_graph_propagate(const void* src, int elem_bytes, int d, int64_t n_src, const int64_t* set_off, const int32_t* set_items,
+                             const int64_t* rows, int64_t n, const float* a, const float* b, float* out) {
+    const char* what = "sml_host_graph_propagate";
+    if (const char* why = graph_refusal(d, elem_bytes, src, n_src, set_off, set_items, rows, n, a, b, 0, 0, nullptr, out, false))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    if (!sml_graph_host_walk(d, elem_bytes, src, set_off, set_items, rows, n, a, b, out))
+        return fail(SML_EINVAL, what, "no walk for this (d, elem_bytes) pair");
+    return SML_OK;
+}
+
 // deep lists: what sml_topk_deep and sml_host_topk_items refuse alike (NULL: nothing).  The tables' heights are unknown: they
 // count from their first row only
 static const char* deep_refusal(int d, int elem_bytes, const void* w_user, const void* w_item, int64_t n_item, const int64_t* users, int64_t n,

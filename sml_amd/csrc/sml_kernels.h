@@ -474,6 +474,21 @@ hipError_t sml_launch_als_solve(int d, int elem_bytes, const void* w_other, cons
                                 hipStream_t st);
 bool sml_als_host_walk(int d, int elem_bytes, const void* w_other, const double* gram, double alpha0, double reg, const int64_t* set_off,
                        const int32_t* set_items, const int64_t* rows, int64_t n, void* w_out, int32_t* status);
+// graph.hip: graph propagation (include/sml_hip.h, PROPAGATION) -- out[x] = a[row] * sum_m b[m] * src[m] over the row's members in
+// the header's fixed order, fp32 or fp16 rows of d = 32 / 64 / 128 (sml_graph_supports; any other pair is hipErrorInvalidValue /
+// false), out always float.  A row of sml_graph_split_segments() segments or more has its segments summed by separate wavefronts
+// into scratch (sml_graph_scratch_size(d, n, nnz) bytes; nnz = 0 gives the part whose extent the call itself knows) and added in
+// order by a further pass; path 0 auto, 1 never split (scratch unused), 2 split every row of more than one segment (never changes
+// a byte).  One integer atomic per split row; no allocation, copy to the host or synchronise.  The host walk is the same
+// definition over host memory
+bool sml_graph_supports(int d, int elem_bytes);
+int sml_graph_split_segments(void);
+int64_t sml_graph_scratch_size(int d, int64_t n, int64_t nnz);
+hipError_t sml_launch_graph_propagate(int d, int elem_bytes, const void* src, const int64_t* set_off, const int32_t* set_items,
+                                      const int64_t* rows, int64_t n, const float* a, const float* b, int max_workgroups, int path,
+                                      void* scratch, float* out, hipStream_t st);
+bool sml_graph_host_walk(int d, int elem_bytes, const void* src, const int64_t* set_off, const int32_t* set_items, const int64_t* rows,
+                         int64_t n, const float* a, const float* b, float* out);
 // knn.hip: the neighbourhood model (include/sml_hip.h, NEIGHBOURS) -- co-occurrence neighbours of items and the list of a
 // history, one wavefront per row.  scratch: sml_knn_scratch_size(n_item, max_workgroups, kind) bytes (kind 0: counts, 1: sums),
 // zeroed by the launch and left zero; path 0 auto, 1 dense everywhere, 2 LDS wherever it fits (never changes a byte).  Only

@@ -1220,6 +1220,47 @@ class HipEngine(object):
                                     self._stream()), "sml_knn_topk")
         return items.long(), scores, n_elig
 
+    # ------------------------------------------------------------------ graph propagation (graph.hip)
+    def graph_split_from(self):
+        """The number of 256-member segments from which a row's segments are summed by separate wavefronts (sml_graph_split_from)."""
+        return int(self.lib.sml_graph_split_from())
+
+    def graph_propagate(self, src, sets, out=None, rows=None, a=None, b=None, max_workgroups=0, path=0):
+        """float32 [n, d]: out[x] = a[row] * sum over the members m of row's set of b[m] * src[m], every fp32 operation in the fixed
+        order of include/sml_hip.h, PROPAGATION (sml_graph_propagate: a random-row gather, no floating-point atomics).  src: a
+        contiguous fp32 or fp16 [n_src, d] table; sets = (off int64 [>= rows + 1], items int32); rows: int64 ids of the rows to
+        compute (None: every row of the set); a: float32 per row id, b: float32 [n_src] (None: 1).  out: where to write (None: a
+        new tensor).  max_workgroups > 0 caps the grid and path forces the split of long rows (0 auto, 1 never, 2 every row of
+        more than one segment); neither changes a byte.  No read-back unless rows is given (one scalar sizes the scratch)."""
+        w = self._als_table(src, "graph_propagate")
+        off, items = self._seen(sets)
+        if off is None:
+            raise ValueError("graph_propagate: sets is (off, items)")
+        if rows is not None:
+            rows = self._dev(rows, torch.int64).reshape(-1)
+        n = off.shape[0] - 1 if rows is None else rows.shape[0]
+        scales = []
+        for t, need, name in ((a, off.shape[0] - 1, "a"), (b, w.shape[0], "b")):
+            if t is not None and (t.dtype != torch.float32 or t.device != self.device or t.dim() != 1 or not t.is_contiguous()
+                                  or t.shape[0] < need):
+                raise ValueError("graph_propagate: %s is a contiguous float32 [>= %d] tensor on %s" % (name, need, self.device))
+            scales.append(t)
+        if out is None:
+            out = torch.empty(n, self.d, device=self.device, dtype=torch.float32)
+        elif out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or tuple(out.shape) != (n, self.d):
+            raise ValueError("graph_propagate: out is a contiguous float32 [%d, %d] tensor on %s" % (n, self.d, self.device))
+        if int(path) == 1 or n == 0:
+            nnz = 0
+        elif rows is None:
+            nnz = int(items.shape[0])
+        else:
+            nnz = int((off[rows + 1] - off[rows]).sum())
+        scratch = self._scratch(self.lib.sml_graph_scratch_bytes(self._ctx, n, nnz, int(max_workgroups)), "sml_graph_scratch_bytes")
+        check(self.lib.sml_graph_propagate(self._ctx, _ptr(w), w.element_size(), w.shape[0], _ptr(off), _ptr(items), _ptr(rows), n,
+                                           _ptr(scales[0]), _ptr(scales[1]), int(max_workgroups), int(path), _ptr(scratch), _ptr(out),
+                                           self._stream()), "sml_graph_propagate")
+        return out
+
     def rerank_mmr(self, item_tab, pool_items, pool_scores, k, lam, metric="cosine", normalize=True, max_workgroups=0, nrm=None):
         """Greedy MMR re-ranking of per-list pools (include/sml_hip.h, RE-RANKING; sml_rerank_mmr: one wavefront per list, no
         scratch).  pool_items int [n, C <= 128] (int64 as recommend returns them is narrowed on the device; entries outside
