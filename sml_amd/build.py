@@ -8,8 +8,8 @@ from . import switches
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsml_hip.so")
-SOURCES = ["transfer_net.hip", "mf_kernels.hip", "index_prep.hip", "retrieval.hip", "spmf.hip", "interaction_set.hip", "neg_sets.hip", "neg_sampler.hip", "rerank.hip", "ivf.hip", "als.hip", "knn.hip", "graph.hip", "capi.hip"]
-HEADERS = ["sml_dev.h", "sml_kernels.h", "radix_sort.h", "topk_list.h", "transfer_fwd_body.inc", os.path.join("..", "..", "include", "sml_hip.h")]
+SOURCES = ["transfer_net.hip", "mf_kernels.hip", "index_prep.hip", "retrieval.hip", "spmf.hip", "interaction_set.hip", "neg_sets.hip", "neg_sampler.hip", "rerank.hip", "ivf.hip", "als.hip", "knn.hip", "graph.hip", "capi.hip", "capi_ops.hip"]
+HEADERS = ["sml_dev.h", "sml_kernels.h", "radix_sort.h", "topk_list.h", "width_dispatch.h", "capi_internal.h", "transfer_fwd_body.inc", os.path.join("..", "..", "include", "sml_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          # leading scalar / pointer kernel parameters arrive in SGPRs with the wavefront (up to 16 SGPRs) instead of behind a
          # scalar-load round trip of the argument segment: 0.22-0.24 us per dependent kernel (tools/launch_boundary_probe.hip)

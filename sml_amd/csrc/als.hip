@@ -23,6 +23,7 @@
 #include <type_traits>
 #include "sml_dev.h"
 #include "sml_kernels.h"
+#include "width_dispatch.h"
 #include "../../include/sml_hip.h"
 
 #pragma clang fp contract(off)
@@ -268,30 +269,17 @@ int als_row_host(const T* y, const double* gram, double alpha0, double reg, cons
     return 0;
 }
 
-// f(D, typed null pointer) for the (d, elem_bytes) pairs of the fold-in; false: no such pair (d = 128 among them)
-template <class Fn>
-bool als_with_pair(int d, int elem_bytes, Fn&& f) {
-    if (elem_bytes == 4) {
-        if (d == 32) { f(std::integral_constant<int, 32>(), (float*)nullptr); return true; }
-        if (d == 64) { f(std::integral_constant<int, 64>(), (float*)nullptr); return true; }
-    } else if (elem_bytes == 2) {
-        if (d == 32) { f(std::integral_constant<int, 32>(), (_Float16*)nullptr); return true; }
-        if (d == 64) { f(std::integral_constant<int, 64>(), (_Float16*)nullptr); return true; }
-    }
-    return false;
-}
-
 }  // namespace
 
 bool sml_als_supports(int d, int elem_bytes) {
-    return als_with_pair(d, elem_bytes, [](auto, auto*) {});
+    return with_pair<FoldInPairs>(d, elem_bytes, [](auto, auto*) {});
 }
 
 int64_t sml_gram_chunks(int64_t n_rows) { return (n_rows + kGramChunk - 1) / kGramChunk; }
 
 hipError_t sml_launch_gram(int d, int elem_bytes, const void* w, int64_t n_rows, double* part, double* gram, hipStream_t st) {
     const int64_t chunks = sml_gram_chunks(n_rows);
-    if (!als_with_pair(d, elem_bytes, [&](auto dd, auto* t) {
+    if (!with_pair<FoldInPairs>(d, elem_bytes, [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         k_gram<dd(), T><<<dim3((unsigned)chunks), dim3(256), 0, st>>>(static_cast<const T*>(w), n_rows, part);
     }))
@@ -301,7 +289,7 @@ hipError_t sml_launch_gram(int d, int elem_bytes, const void* w, int64_t n_rows,
 }
 
 bool sml_gram_host_walk(int d, int elem_bytes, const void* w, int64_t n_rows, double* gram) {
-    return als_with_pair(d, elem_bytes, [&](auto dd, auto* t) {
+    return with_pair<FoldInPairs>(d, elem_bytes, [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         gram_host_walk<dd(), T>(static_cast<const T*>(w), n_rows, gram);
     });
@@ -314,7 +302,7 @@ hipError_t sml_launch_als_solve(int d, int elem_bytes, const void* w_other, cons
     const int64_t cap = max_workgroups > 0 ? max_workgroups : 1024;      // the kernel's own choice: 4 workgroups per CU of 256
     if (blocks > cap) blocks = cap;
     const dim3 grid((unsigned)blocks), block(64 * kAlsWaves);
-    if (!als_with_pair(d, elem_bytes, [&](auto dd, auto* t) {
+    if (!with_pair<FoldInPairs>(d, elem_bytes, [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         k_als_solve<dd(), T><<<grid, block, 0, st>>>(static_cast<const T*>(w_other), gram, alpha0, reg, set_off, set_items, rows, n,
                                                      static_cast<T*>(w_out), status);
@@ -325,7 +313,7 @@ hipError_t sml_launch_als_solve(int d, int elem_bytes, const void* w_other, cons
 
 bool sml_als_host_walk(int d, int elem_bytes, const void* w_other, const double* gram, double alpha0, double reg, const int64_t* set_off,
                        const int32_t* set_items, const int64_t* rows, int64_t n, void* w_out, int32_t* status) {
-    return als_with_pair(d, elem_bytes, [&](auto dd, auto* t) {
+    return with_pair<FoldInPairs>(d, elem_bytes, [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         constexpr int D = dd();
         for (int64_t x = 0; x < n; ++x) {

@@ -20,6 +20,7 @@
 #include <type_traits>
 #include "sml_dev.h"
 #include "sml_kernels.h"
+#include "width_dispatch.h"
 #include "../../include/sml_hip.h"
 
 #pragma clang fp contract(off)
@@ -273,25 +274,10 @@ void prop_row_host(const T* src, const float* b, const int32_t* mem, int64_t len
     }
 }
 
-// f(D, typed null pointer) for the six (d, elem_bytes) pairs; false: no such pair
-template <class Fn>
-bool prop_with_pair(int d, int elem_bytes, Fn&& f) {
-    if (elem_bytes == 4) {
-        if (d == 32) { f(std::integral_constant<int, 32>(), (float*)nullptr); return true; }
-        if (d == 64) { f(std::integral_constant<int, 64>(), (float*)nullptr); return true; }
-        if (d == 128) { f(std::integral_constant<int, 128>(), (float*)nullptr); return true; }
-    } else if (elem_bytes == 2) {
-        if (d == 32) { f(std::integral_constant<int, 32>(), (_Float16*)nullptr); return true; }
-        if (d == 64) { f(std::integral_constant<int, 64>(), (_Float16*)nullptr); return true; }
-        if (d == 128) { f(std::integral_constant<int, 128>(), (_Float16*)nullptr); return true; }
-    }
-    return false;
-}
-
 }  // namespace
 
 bool sml_graph_supports(int d, int elem_bytes) {
-    return prop_with_pair(d, elem_bytes, [](auto, auto*) {});
+    return with_pair<PropagationPairs>(d, elem_bytes, [](auto, auto*) {});
 }
 
 int sml_graph_split_segments(void) { return SML_GRAPH_SPLIT_FROM; }
@@ -314,7 +300,7 @@ hipError_t sml_launch_graph_propagate(int d, int elem_bytes, const void* src, co
         if (e != hipSuccess) return e;
     }
     const dim3 block(64 * kPropWaves);
-    if (!prop_with_pair(d, elem_bytes, [&](auto dd, auto* t) {
+    if (!with_pair<PropagationPairs>(d, elem_bytes, [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         constexpr int D = dd();
         k_prop_rows<D, T><<<dim3((unsigned)blocks), block, 0, st>>>(args, s.n_slots, s.base, s.slots);
@@ -332,7 +318,7 @@ hipError_t sml_launch_graph_propagate(int d, int elem_bytes, const void* src, co
 
 bool sml_graph_host_walk(int d, int elem_bytes, const void* src, const int64_t* set_off, const int32_t* set_items, const int64_t* rows,
                          int64_t n, const float* a, const float* b, float* out) {
-    return prop_with_pair(d, elem_bytes, [&](auto dd, auto* t) {
+    return with_pair<PropagationPairs>(d, elem_bytes, [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         constexpr int D = dd();
         for (int64_t x = 0; x < n; ++x) {

@@ -14,6 +14,7 @@
 #include <type_traits>
 #include "sml_dev.h"
 #include "sml_kernels.h"
+#include "width_dispatch.h"
 #include "../../include/sml_hip.h"
 
 #pragma clang fp contract(off)
@@ -84,26 +85,12 @@ void centroids_host_walk(const T* wi, const int64_t* list_off, const int32_t* li
     }
 }
 
-// f(D, typed null pointer) for the (d, elem_bytes) pairs of the retrieval family; false: no such pair
-template <class Fn>
-bool with_pair(int d, int elem_bytes, Fn&& f) {
-    if (elem_bytes == 4) {
-        if (d == 32) { f(std::integral_constant<int, 32>(), (float*)nullptr); return true; }
-        if (d == 64) { f(std::integral_constant<int, 64>(), (float*)nullptr); return true; }
-    } else if (elem_bytes == 2) {
-        if (d == 32) { f(std::integral_constant<int, 32>(), (_Float16*)nullptr); return true; }
-        if (d == 64) { f(std::integral_constant<int, 64>(), (_Float16*)nullptr); return true; }
-        if (d == 128) { f(std::integral_constant<int, 128>(), (_Float16*)nullptr); return true; }
-    }
-    return false;
-}
-
 }  // namespace
 
 hipError_t sml_launch_ivf_centroids(int d, int elem_bytes, const void* wi, const int64_t* list_off, const int32_t* list_items, int n_list,
                                     const void* cin, void* cout, hipStream_t st) {
     const dim3 grid((unsigned)((n_list + kCenWaves - 1) / kCenWaves)), block(64 * kCenWaves);
-    if (!with_pair(d, elem_bytes, [&](auto dd, auto* t) {
+    if (!with_pair<RetrievalPairs>(d, elem_bytes, [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         k_ivf_centroids<dd(), T><<<grid, block, 0, st>>>(static_cast<const T*>(wi), list_off, list_items, n_list, static_cast<const T*>(cin),
                                                          static_cast<T*>(cout));
@@ -114,7 +101,7 @@ hipError_t sml_launch_ivf_centroids(int d, int elem_bytes, const void* wi, const
 
 bool sml_ivf_centroids_host_walk(int d, int elem_bytes, const void* wi, const int64_t* list_off, const int32_t* list_items, int n_list,
                                  const void* cin, void* cout) {
-    return with_pair(d, elem_bytes, [&](auto dd, auto* t) {
+    return with_pair<RetrievalPairs>(d, elem_bytes, [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         centroids_host_walk<dd(), T>(static_cast<const T*>(wi), list_off, list_items, n_list, static_cast<const T*>(cin), static_cast<T*>(cout));
     });

@@ -26,6 +26,7 @@
 #include <type_traits>
 #include "sml_dev.h"
 #include "sml_kernels.h"
+#include "width_dispatch.h"
 #include "../../include/sml_hip.h"
 
 #pragma clang fp contract(off)
@@ -343,22 +344,6 @@ void rr_host_walk(const T* wi, int64_t n_item, const int32_t* pool_items, const 
     }
 }
 
-// f(dd, table pointer) on the (d, elem_bytes) pairs that have kernels: the pairs sml_retrieval_supports answers for
-template <class F>
-bool rr_with_width(int d, int elem_bytes, const void* wi, F&& f) {
-    if (elem_bytes == 4) {
-        const float* t = static_cast<const float*>(wi);
-        if (d == 32) { f(std::integral_constant<int, 32>(), t); return true; }
-        if (d == 64) { f(std::integral_constant<int, 64>(), t); return true; }
-    } else if (elem_bytes == 2) {
-        const _Float16* t = static_cast<const _Float16*>(wi);
-        if (d == 32) { f(std::integral_constant<int, 32>(), t); return true; }
-        if (d == 64) { f(std::integral_constant<int, 64>(), t); return true; }
-        if (d == 128) { f(std::integral_constant<int, 128>(), t); return true; }
-    }
-    return false;
-}
-
 }  // namespace
 
 hipError_t sml_launch_rerank_mmr(int d, int elem_bytes, const void* wi, int64_t n_item, const int32_t* pool_items, const float* pool_rel,
@@ -371,10 +356,10 @@ hipError_t sml_launch_rerank_mmr(int d, int elem_bytes, const void* wi, int64_t 
     if (max_workgroups > 0 && blocks > max_workgroups) blocks = max_workgroups;
     const dim3 grid((unsigned)blocks), block(64 * kRrWaves);
     const float oml = 1.0f - lam;
-    if (!rr_with_width(d, elem_bytes, wi, [&](auto dd, auto* t) {
-            typedef std::remove_const_t<std::remove_pointer_t<decltype(t)>> T;
-            k_rerank_mmr<dd(), T><<<grid, block, 0, st>>>(t, n_item, pool_items, pool_rel, n, pool_cols, pool_stride, nrm, lam, oml, normalize, k,
-                                                          items, pos, value, n_sel, sim_sum);
+    if (!with_pair<RetrievalPairs>(d, elem_bytes, [&](auto dd, auto* t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            k_rerank_mmr<dd(), T><<<grid, block, 0, st>>>(static_cast<const T*>(wi), n_item, pool_items, pool_rel, n, pool_cols, pool_stride, nrm,
+                                                          lam, oml, normalize, k, items, pos, value, n_sel, sim_sum);
         }))
         return hipErrorInvalidValue;
     return hipGetLastError();
@@ -383,9 +368,9 @@ hipError_t sml_launch_rerank_mmr(int d, int elem_bytes, const void* wi, int64_t 
 bool sml_rerank_host_walk(int d, int elem_bytes, const void* wi, int64_t n_item, const int32_t* pool_items, const float* pool_rel, int64_t n,
                           int pool_cols, int64_t pool_stride, const float* nrm, float lam, int normalize, int k, int32_t* items,
                           int32_t* pos, float* value, int32_t* n_sel, float* sim_sum) {
-    return rr_with_width(d, elem_bytes, wi, [&](auto dd, auto* t) {
-        typedef std::remove_const_t<std::remove_pointer_t<decltype(t)>> T;
-        rr_host_walk<dd(), T>(t, n_item, pool_items, pool_rel, n, pool_cols, pool_stride, nrm, lam, normalize, k, items, pos, value, n_sel,
-                              sim_sum);
+    return with_pair<RetrievalPairs>(d, elem_bytes, [&](auto dd, auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        rr_host_walk<dd(), T>(static_cast<const T*>(wi), n_item, pool_items, pool_rel, n, pool_cols, pool_stride, nrm, lam, normalize, k, items,
+                              pos, value, n_sel, sim_sum);
     });
 }

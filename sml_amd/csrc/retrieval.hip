@@ -92,6 +92,7 @@
 #include <type_traits>
 #include "sml_dev.h"
 #include "sml_kernels.h"
+#include "width_dispatch.h"
 #include "topk_list.h"
 #include "../../include/sml_hip.h"
 
@@ -497,7 +498,7 @@ SliceGrid topk_grid(int64_t n, int k, int64_t n_item) { return plan_grid(n, topk
 // called -- the launchers' refusal, and what sml_retrieval_supports asks
 template <class Fn>
 bool with_width(const SmlCatalogue& c, Fn&& f) {
-    const auto typed = [&](auto dd, auto* t) {
+    return with_pair<RetrievalPairs>(c.d, c.elem_bytes, [&](auto dd, auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         const T* wu = static_cast<const T*>(c.wu);
         const T* wi = static_cast<const T*>(c.wi);
@@ -505,17 +506,7 @@ bool with_width(const SmlCatalogue& c, Fn&& f) {
         else if (c.adj) f(dd, std::false_type(), std::true_type(), wu, wi);
         else if (c.allow) f(dd, std::true_type(), std::false_type(), wu, wi);
         else f(dd, std::false_type(), std::false_type(), wu, wi);
-        return true;
-    };
-    if (c.elem_bytes == 4) {
-        if (c.d == 32) return typed(std::integral_constant<int, 32>(), (float*)nullptr);
-        if (c.d == 64) return typed(std::integral_constant<int, 64>(), (float*)nullptr);
-    } else if (c.elem_bytes == 2) {
-        if (c.d == 32) return typed(std::integral_constant<int, 32>(), (_Float16*)nullptr);
-        if (c.d == 64) return typed(std::integral_constant<int, 64>(), (_Float16*)nullptr);
-        if (c.d == 128) return typed(std::integral_constant<int, 128>(), (_Float16*)nullptr);
-    }
-    return false;
+    });
 }
 
 // the element type of a typed table pointer, as the kernels' T

@@ -991,9 +991,7 @@ class HipEngine(object):
         users = self._dev(users, torch.int64).reshape(-1)
         n, k, slices = users.shape[0], deep_args(k), int(slices)
         off, seen_items = self._seen(seen)
-        items = torch.empty(n, k, device=self.device, dtype=torch.int32)
-        scores = torch.empty(n, k, device=self.device, dtype=torch.float32)
-        n_elig = torch.empty(n, device=self.device, dtype=torch.int32)
+        items, scores, n_elig = self._list_out(n, k)
         total = int(self.lib.sml_topk_deep_scratch_bytes(self._ctx, n, k, wi.shape[0], slices))
         if total < 0:
             check(-1, "sml_topk_deep_scratch_bytes")
@@ -1031,9 +1029,7 @@ class HipEngine(object):
         n, k = users.shape[0], int(k)
         off, seen_items = self._seen(seen)
         cand = cl.items if cl.items.numel() else torch.zeros(1, device=self.device, dtype=cl.items.dtype)   # (never a null pointer)
-        items = torch.empty(n, max(k, 0), device=self.device, dtype=torch.int32)
-        scores = torch.empty(n, max(k, 0), device=self.device, dtype=torch.float32)
-        n_elig = torch.empty(n, device=self.device, dtype=torch.int32)
+        items, scores, n_elig = self._list_out(n, k)
         check(self.lib.sml_topk_candidates(self._ctx, _ptr(wu), _ptr(wi), wi.element_size(), wi.shape[0], _ptr(users), n, _ptr(cand),
                                            cand.element_size(), _ptr(cl.off), cl.stride, cl.first, cl.cols, k, _ptr(off),
                                            _ptr(seen_items), _ptr(allow), _ptr(adj), int(max_workgroups), _ptr(items), _ptr(scores),
@@ -1070,9 +1066,7 @@ class HipEngine(object):
         if probes.dim() != 2 or probes.shape[0] != n:
             raise ValueError("probes must be int [%d, nprobe], got shape %s" % (n, tuple(probes.shape)))
         off, seen_items = self._seen(seen)
-        items = torch.empty(n, max(k, 0), device=self.device, dtype=torch.int32)
-        scores = torch.empty(n, max(k, 0), device=self.device, dtype=torch.float32)
-        n_elig = torch.empty(n, device=self.device, dtype=torch.int32)
+        items, scores, n_elig = self._list_out(n, k)
         check(self.lib.sml_ivf_search(self._ctx, _ptr(wu), _ptr(wi), wi.element_size(), wi.shape[0], _ptr(users), n, _ptr(list_off),
                                       _ptr(list_items), list_off.shape[0] - 1, _ptr(probes), probes.shape[1], k, _ptr(off),
                                       _ptr(seen_items), _ptr(allow), _ptr(adj), int(max_workgroups), _ptr(items), _ptr(scores),
@@ -1158,7 +1152,8 @@ class HipEngine(object):
                 mw, nbytes = int(n), fewer
         return self._scratch(nbytes, "sml_knn_scratch_bytes"), mw
 
-    def _knn_out(self, n, k):
+    def _list_out(self, n, k):
+        """The (items int32 [n, k], scores float32 [n, k], n_elig int32 [n]) outputs of a list-producing call."""
         return (torch.empty(n, max(k, 0), device=self.device, dtype=torch.int32),
                 torch.empty(n, max(k, 0), device=self.device, dtype=torch.float32),
                 torch.empty(n, device=self.device, dtype=torch.int32))
@@ -1186,7 +1181,7 @@ class HipEngine(object):
             rows = self._dev(rows, torch.int64).reshape(-1)
         n, k = n_item if rows is None else rows.shape[0], int(k)
         scratch, mw = self._knn_scratch(n_item, n, max_workgroups, 0)
-        items, sims, n_elig = self._knn_out(n, k)
+        items, sims, n_elig = self._list_out(n, k)
         check(self.lib.sml_cooc_topk(self._ctx, _ptr(i_off), _ptr(i_users), _ptr(u_off), _ptr(u_items), n_user, n_item, _ptr(rows), n,
                                      _ptr(na), _ptr(nb), float(shrink), int(min_co), _ptr(allow), k, mw, int(path),
                                      _ptr(scratch), _ptr(items), _ptr(sims), _ptr(n_elig), self._stream()), "sml_cooc_topk")
@@ -1213,7 +1208,7 @@ class HipEngine(object):
         s_off, s_items = self._seen(seen)
         allow = self._allow(allow, n_item)
         scratch, mw = self._knn_scratch(n_item, n, max_workgroups, 1)
-        items, scores, n_elig = self._knn_out(n, k)
+        items, scores, n_elig = self._list_out(n, k)
         check(self.lib.sml_knn_topk(self._ctx, _ptr(nbr_items), _ptr(nbr_sims), nbr_items.shape[0], nbr_items.shape[1], n_item,
                                     _ptr(h_off), _ptr(h_items), _ptr(users), n, int(frac_bits), _ptr(s_off), _ptr(s_items), _ptr(allow),
                                     k, mw, int(path), _ptr(scratch), _ptr(items), _ptr(scores), _ptr(n_elig),
