@@ -779,6 +779,40 @@ int sml_host_als_solve(const void* w_other, int elem_bytes, int d, int64_t n_oth
  * a = b = deg^1/2; asymmetric: a = deg^alpha, b = deg^(1 - alpha)).  With norm_a == norm_b the product commutes exactly, so
  * sim(i, j) and sim(j, i) are the same bits.  With norms NULL and k >= the number of neighbours, the row is exactly the non-zero
  * off-diagonal of row i of X^T X, X the 0/1 interaction matrix.
+ * WEIGHTED NEIGHBOURS OF ITEMS (sml_cooc_topk_weighted): the call above in which users do not count equally -- the random-walk
+ * similarities P3alpha and RP3beta (user_w = deg_u^-alpha, norm_a = deg^alpha, norm_b = deg^beta), inverse-user-frequency cosine,
+ * Adamic-Adar / resource allocation, any trust or recency weight per user.  Inputs are those of sml_cooc_topk, except: user_w float
+ * [n_user], required; frac_bits F in [0, 32]; there is no min_co.  For query item i:
+ *   a user's weight in fixed point is q(u) = llrint(ldexp((double)user_w[u], F)), round to nearest even (the quantisation of the
+ *     list of a history below, the same text);
+ *   a user contributes nothing when user_w[u] is not finite, or |q(u)| > 2^32, or q(u) <= 0; a user that contributes nothing
+ *     creates no candidate;
+ *   cw(j) = sum of q(u) over the contributing u in U(i) with j in S(u), an int64.  It cannot overflow: fewer than 2^31 users, each
+ *     at most 2^32;
+ *   the candidates are the j != i with cw(j) > 0 that are allowed;
+ *   num = ldexp((double)cw, -F); the int64 -> double conversion rounds to nearest even and is exact below 2^53;
+ *   without norms the score is s = (float)num;
+ *   with norms:  den = norm_a[i] * norm_b[j], one fp64 rounding;  den = den + shrink;  s64 = num / den, correctly rounded;
+ *     s = (float)s64;
+ *   a NaN score is not eligible, an inf score is;
+ *   order, padding (-1, -inf), n_elig, rows == NULL, 1 <= k <= 128 and a row named twice being written twice are the family's.
+ * Defining identities of the weighted call:
+ *   (a) unit weights: user_w == 1.0f everywhere with F = 0 returns sml_cooc_topk's bytes at min_co = 1 (items, sims, n_elig),
+ *       with norms and without;
+ *   (b) dropped users: a user that contributes nothing behaves like that user removed from both CSRs;
+ *   (c) power-of-two scaling: doubling every weight while lowering F by one leaves every q(u) and so every cw, the items and
+ *       n_elig the same bytes; num carries the scale 2^-F, so every sim is exactly doubled -- the same bytes once halved;
+ *   (d) symmetry: with norm_a == norm_b, weighted sim(i, j) and sim(j, i) are the same bits;
+ *   (e) prefix: a k'-call of the weighted call is the prefix of its k-call;
+ *   (f) geometry: max_workgroups and path never change a byte of the weighted call;
+ *   (g) filter: a filtered call returns the unfiltered row with the disallowed candidates removed, and its n_elig counts the rest.
+ * Paths: as above, with int64 sums in the on-chip table and one int64 [n_item] accumulator per wavefront in scratch; every
+ * contributing q is >= 1, so a touched slot is a non-zero slot and the claim is the exchange that returns a non-zero sum -- no
+ * bitmap.  scratch: sml_cooc_weighted_scratch_bytes(ctx, n_item, max_workgroups) bytes (< 0: bad argument), 256-byte aligned,
+ * zeroed by the call at the start as far as it is used and left zero.  Refused, a refused call writing nothing: everything
+ * sml_cooc_topk refuses; user_w NULL; F outside [0, 32]; a misaligned scratch.  sml_host_cooc_topk_weighted: the single-threaded
+ * walk over HOST memory (a dense int64 array, then a full sort), sharing the quantisation and the score text with the kernel.
+ * Not measured for the weighted call: real periods, trained comparisons, shapes beyond the Yelp one, sums above 2^53.
  * THE LIST OF A HISTORY (sml_knn_topk).  nbr_items int32 and nbr_sims float, both [n_rows_nbr, k_nbr], 1 <= k_nbr <= 128: the
  * output form of the call above, but any table of that shape is accepted.  hist_off / hist_items: the CSR of histories.  users
  * int64 [n] indexes hist_off and seen_off; users == NULL means 0 .. n - 1.  frac_bits F in [0, 32].  seen_off / seen_items, allow:
@@ -828,6 +862,18 @@ int sml_host_cooc_topk(const int64_t* by_item_off, const int32_t* by_item_users,
                        const int64_t* by_user_off, const int32_t* by_user_items, int64_t n_user, int64_t n_item,
                        const int64_t* rows, int64_t n, const double* norm_a, const double* norm_b, double shrink, int min_co,
                        const uint32_t* allow, int k, int32_t* items, float* sims, int32_t* n_elig);
+int64_t sml_cooc_weighted_scratch_bytes(sml_ctx* ctx, int64_t n_item, int max_workgroups);
+int sml_cooc_topk_weighted(sml_ctx* ctx, const int64_t* by_item_off, const int32_t* by_item_users,
+                           const int64_t* by_user_off, const int32_t* by_user_items, int64_t n_user, int64_t n_item,
+                           const int64_t* rows, int64_t n, const float* user_w, int frac_bits,
+                           const double* norm_a, const double* norm_b, double shrink,
+                           const uint32_t* allow, int k, int max_workgroups, int path, void* scratch,
+                           int32_t* items, float* sims, int32_t* n_elig, void* stream);
+int sml_host_cooc_topk_weighted(const int64_t* by_item_off, const int32_t* by_item_users,
+                                const int64_t* by_user_off, const int32_t* by_user_items, int64_t n_user, int64_t n_item,
+                                const int64_t* rows, int64_t n, const float* user_w, int frac_bits,
+                                const double* norm_a, const double* norm_b, double shrink,
+                                const uint32_t* allow, int k, int32_t* items, float* sims, int32_t* n_elig);
 int sml_knn_topk(sml_ctx* ctx, const int32_t* nbr_items, const float* nbr_sims, int64_t n_rows_nbr, int k_nbr, int64_t n_item,
                  const int64_t* hist_off, const int32_t* hist_items, const int64_t* users, int64_t n, int frac_bits,
                  const int64_t* seen_off, const int32_t* seen_items, const uint32_t* allow, int k,

@@ -164,6 +164,13 @@ SIGNATURES = {
                                      c_void, c_void, c_void]),
     "sml_host_cooc_topk": (ctypes.c_int, [c_void, c_void, c_void, c_void, ctypes.c_int64, ctypes.c_int64, c_void, ctypes.c_int64, c_void,
                                           c_void, ctypes.c_double, ctypes.c_int, c_void, ctypes.c_int, c_void, c_void, c_void]),
+    "sml_cooc_weighted_scratch_bytes": (ctypes.c_int64, [c_void, ctypes.c_int64, ctypes.c_int]),
+    "sml_cooc_topk_weighted": (ctypes.c_int, [c_void, c_void, c_void, c_void, c_void, ctypes.c_int64, ctypes.c_int64, c_void, ctypes.c_int64,
+                                              c_void, ctypes.c_int, c_void, c_void, ctypes.c_double, c_void, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, c_void, c_void, c_void, c_void, c_void]),
+    "sml_host_cooc_topk_weighted": (ctypes.c_int, [c_void, c_void, c_void, c_void, ctypes.c_int64, ctypes.c_int64, c_void, ctypes.c_int64,
+                                                   c_void, ctypes.c_int, c_void, c_void, ctypes.c_double, c_void, ctypes.c_int, c_void,
+                                                   c_void, c_void]),
     "sml_knn_topk": (ctypes.c_int, [c_void, c_void, c_void, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_void, c_void, c_void,
                                     ctypes.c_int64, ctypes.c_int, c_void, c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void,
                                     c_void, c_void, c_void, c_void]),

@@ -419,10 +419,14 @@ int sml_host_als_solve(const void* w_other, int elem_bytes, int d, int64_t n_oth
 
 // neighbours: what the device calls and the host walks refuse alike (NULL: nothing).  The CSRs, Seen and the neighbour table's
 // height are of unknown extent where the arguments do not give it: they count from their first entry only
+// weighted: the call takes the users' weights user_w (required) in fixed point with frac_bits fractional bits
 static const char* cooc_refusal(const SmlCooc& a, int max_workgroups, int path, const void* scratch, int64_t scratch_bytes, const int32_t* items,
-                                const float* sims, const int32_t* n_elig, bool device) {
+                                const float* sims, const int32_t* n_elig, bool device, bool weighted = false, const float* user_w = nullptr,
+                                int frac_bits = 0) {
     if (a.k < 1 || a.k > 128) return "bad argument (1 <= k <= 128)";
     if (a.min_co < 1) return "bad argument (min_co >= 1)";
+    if (weighted && (frac_bits < 0 || frac_bits > 32)) return "bad argument (0 <= frac_bits <= 32)";
+    if (weighted && !user_w) return "null argument";
     if (max_workgroups < 0 || path < 0 || path > 2) return "bad argument (max_workgroups >= 0, path 0 / 1 / 2)";
     if (!(a.shrink >= 0.0)) return "bad argument (shrink must be >= 0)";
     if ((!a.item_off) != (!a.item_users) || (!a.user_off) != (!a.user_items)) return "bad argument (a CSR's two pointers both or neither)";
@@ -434,7 +438,8 @@ static const char* cooc_refusal(const SmlCooc& a, int max_workgroups, int path, 
     if (!items || !sims || (device && !scratch) || (a.item_off && !a.user_off)) return "null argument";
     const int64_t ob = 4 * a.n * (int64_t)a.k;
     const Span in[] = {{a.item_off, 8 * (a.n_item + 1)}, {a.item_users, 4}, {a.user_off, 8 * (a.n_user + 1)}, {a.user_items, 4},
-                          {a.rows, 8 * a.n}, {a.norm_a, 8 * a.n_item}, {a.norm_b, 8 * a.n_item}, {a.allow, (a.n_item + 31) / 32 * 4}};
+                          {a.rows, 8 * a.n}, {a.norm_a, 8 * a.n_item}, {a.norm_b, 8 * a.n_item}, {a.allow, (a.n_item + 31) / 32 * 4},
+                          {user_w, 4 * a.n_user}};
     const Span out[] = {{items, ob}, {sims, ob}, {n_elig, 4 * a.n}, {scratch, scratch_bytes}};
     return overlap_refusal(in, out, kOutIn, kOutOut);
 }
@@ -488,6 +493,45 @@ int sml_host_cooc_topk(const int64_t* by_item_off, const int32_t* by_item_users,
     if (const char* why = cooc_refusal(a, 0, 0, nullptr, 0, items, sims, n_elig, false)) return fail(SML_EINVAL, what, why);
     if (n == 0) return SML_OK;
     sml_cooc_host_walk(a, items, sims, n_elig);
+    return SML_OK;
+}
+
+int64_t sml_cooc_weighted_scratch_bytes(sml_ctx* ctx, int64_t n_item, int max_workgroups) {
+    if (!ctx || !size_ok(n_item) || max_workgroups < 0)
+        return fail(SML_EINVAL, "sml_cooc_weighted_scratch_bytes", "bad argument (0 < n_item < 2^31, max_workgroups >= 0)");
+    return sml_cooc_weighted_scratch_size(n_item, max_workgroups);
+}
+
+int sml_cooc_topk_weighted(sml_ctx* ctx, const int64_t* by_item_off, const int32_t* by_item_users, const int64_t* by_user_off,
+                           const int32_t* by_user_items, int64_t n_user, int64_t n_item, const int64_t* rows, int64_t n, const float* user_w,
+                           int frac_bits, const double* norm_a, const double* norm_b, double shrink, const uint32_t* allow, int k,
+                           int max_workgroups, int path, void* scratch, int32_t* items, float* sims, int32_t* n_elig, void* stream) {
+    const char* what = "sml_cooc_topk_weighted";
+    if (!ctx) return fail(SML_EINVAL, what, "null argument");
+    const SmlCooc c = {by_item_off, by_item_users, by_user_off, by_user_items, n_user, n_item, rows, n, norm_a, norm_b, shrink, 1, allow, k};
+    const int64_t sb = size_ok(n_item) && max_workgroups >= 0 ? sml_cooc_weighted_scratch_size(n_item, max_workgroups) : 0;
+    if (const char* why = cooc_refusal(c, max_workgroups, path, scratch, sb, items, sims, n_elig, true, true, user_w, frac_bits))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    const SmlCoocWeighted a = {by_item_off, by_item_users, by_user_off, by_user_items, n_user, n_item, rows, n, user_w, frac_bits,
+                               norm_a, norm_b, shrink, allow, k};
+    DevGuard g(ctx->device); hipStream_t st = (hipStream_t)stream;
+    PROFILED(PC_MISC, HIPCHK(sml_launch_cooc_topk_weighted(a, max_workgroups, path, scratch, items, sims, n_elig, st)));
+    return SML_OK;
+}
+
+int sml_host_cooc_topk_weighted(const int64_t* by_item_off, const int32_t* by_item_users, const int64_t* by_user_off,
+                                const int32_t* by_user_items, int64_t n_user, int64_t n_item, const int64_t* rows, int64_t n,
+                                const float* user_w, int frac_bits, const double* norm_a, const double* norm_b, double shrink,
+                                const uint32_t* allow, int k, int32_t* items, float* sims, int32_t* n_elig) {
+    const char* what = "sml_host_cooc_topk_weighted";
+    const SmlCooc c = {by_item_off, by_item_users, by_user_off, by_user_items, n_user, n_item, rows, n, norm_a, norm_b, shrink, 1, allow, k};
+    if (const char* why = cooc_refusal(c, 0, 0, nullptr, 0, items, sims, n_elig, false, true, user_w, frac_bits))
+        return fail(SML_EINVAL, what, why);
+    if (n == 0) return SML_OK;
+    const SmlCoocWeighted a = {by_item_off, by_item_users, by_user_off, by_user_items, n_user, n_item, rows, n, user_w, frac_bits,
+                               norm_a, norm_b, shrink, allow, k};
+    sml_cooc_weighted_host_walk(a, items, sims, n_elig);
     return SML_OK;
 }
 

@@ -1,18 +1,20 @@
 // Neighbourhood model on gfx950 (include/sml_hip.h, "NEIGHBOURS"): for a row x, accumulate over the lists of x's members and keep
 // the K best -- out(x) = top-K over j of sum_{m in R(x)} W[m, j].  sml_cooc_topk is this with R(x) the users of item x and W[m, .]
 // the items of user m with unit weights; sml_knn_topk with R(x) a history and W[m, .] item m's neighbour list with its similarities
-// in fixed point.  The only atomics are integer (exact, order-free), so the bytes depend on no launch geometry.
+// in fixed point; sml_cooc_topk_weighted is sml_cooc_topk with user m's unit replaced by its weight in fixed point.  The only
+// atomics are integer (exact, order-free), so the bytes depend on no launch geometry.
 //
 // One wavefront per row, rows walked grid-stride, kKnnWaves rows per workgroup in flight.  Two paths, chosen per row from the
 // row's total list length (known before the walk, and a bound on its distinct ids):
 //   LDS path    total <= kKnnLdsLimit: an open-addressing table of kKnnTabSlots = 2 * kKnnLdsLimit slots per wave in LDS (key by
 //               ds compare-and-swap, sum by ds add).  The table can never fill, and the probe loop is bounded by its size anyway.
 //               The candidates are then read off the table's slots, which are reset as they are read.
-//   dense path  a dense accumulator over [0, n_item) per wave in scratch (int32 counts; int64 sums + a touched bitmap).  Pass 1
-//               adds with no-return global atomics; pass 2 walks the same lists again and the lane that claims a candidate (counts:
-//               the exchange that returns a non-zero count; sums: the atomic AND that clears its touched bit) takes the sum with
-//               an exchange that resets the slot to zero, so the scratch is zero again when the row is done.  A history with more
-//               slots than the catalogue has items skips the second walk: its candidates are claimed from the bitmap's words.
+//   dense path  a dense accumulator over [0, n_item) per wave in scratch (int32 counts; int64 weighted counts; int64 sums + a
+//               touched bitmap).  Pass 1 adds with no-return global atomics; pass 2 walks the same lists again and the lane that
+//               claims a candidate (counts, weighted or not: the exchange that returns a non-zero value -- every contribution is
+//               >= 1; sums: the atomic AND that clears its touched bit) takes the sum with an exchange that resets the slot to
+//               zero, so the scratch is zero again when the row is done.  A history with more slots than the catalogue has items
+//               skips the second walk: its candidates are claimed from the bitmap's words.
 // Either way the claimed (id, sum) pairs go through the same eligibility and score text and into the wave's sorted LDS list
 // (cand_insert, topk_list.h); the sums are integers and the order is total, so who claims what never shows in the output.
 // The kernels and the single-threaded host walks share the score functions.  Contraction is OFF in the whole file.
@@ -39,14 +41,19 @@ constexpr int kKnnGrid = 256;                      // workgroups when max_workgr
 static_assert(kKnnTabSlots >= 2 * kKnnLdsLimit, "the table holds at least twice the admitted entries: it can never fill");
 
 // ---- the scores: the text the header names, shared by the kernels and the host walks ------------------------------------------
-// count -> similarity: den = a[i] * b[j] (one fp64 rounding); den = den + shrink; s64 = c / den (correctly rounded); (float)s64
+// numerator -> similarity: den = a[i] * b[j] (one fp64 rounding); den = den + shrink; s64 = num / den (correctly rounded); (float)s64
+__host__ __device__ __forceinline__ float cooc_ratio(double num, const double* __restrict__ na, const double* __restrict__ nb, int64_t i, int64_t j,
+                                                     double shrink) {
+    double den = na[i] * nb[j];
+    den = den + shrink;
+    const double s64 = num / den;
+    return (float)s64;
+}
+// count -> similarity
 __host__ __device__ __forceinline__ float cooc_score(int c, const double* __restrict__ na, const double* __restrict__ nb, int64_t i, int64_t j,
                                                      double shrink) {
     if (!na) return (float)c;
-    double den = na[i] * nb[j];
-    den = den + shrink;
-    const double s64 = (double)c / den;
-    return (float)s64;
+    return cooc_ratio((double)c, na, nb, i, j, shrink);
 }
 // similarity -> fixed point: q = rint(ldexp((double)sim, F)), to nearest even; false: the slot contributes nothing
 __host__ __device__ __forceinline__ bool knn_quant(float sim, int F, long long* q) {
@@ -59,12 +66,25 @@ __host__ __device__ __forceinline__ bool knn_quant(float sim, int F, long long* 
 // fixed point -> score: (float)ldexp((double)acc, -F), both conversions to nearest even
 __host__ __device__ __forceinline__ float knn_score(long long acc, int F) { return (float)ldexp((double)acc, -F); }
 
+// weighted count -> similarity: num = ldexp((double)cw, -F), the conversion to nearest even; then the text of the count
+__host__ __device__ __forceinline__ float cooc_score_weighted(long long cw, int F, const double* __restrict__ na, const double* __restrict__ nb,
+                                                              int64_t i, int64_t j, double shrink) {
+    const double num = ldexp((double)cw, -F);
+    if (!na) return (float)num;
+    return cooc_ratio(num, na, nb, i, j, shrink);
+}
+// a user's weight in fixed point (knn_quant's text); false: the user contributes nothing
+__host__ __device__ __forceinline__ bool cooc_user_quant(const float* __restrict__ user_w, int64_t u, int F, long long* q) {
+    return knn_quant(user_w[u], F, q) && *q > 0;
+}
+
 __host__ __device__ __forceinline__ bool knn_allowed(const uint32_t* __restrict__ allow, int j) {
     return !allow || ((allow[j >> 5] >> (j & 31)) & 1u);
 }
 
 __host__ __device__ constexpr int64_t knn_pad256(int64_t b) { return (b + 255) / 256 * 256; }
-// one wave's slot of the scratch: kind 0 (counts) int32 [n_item]; kind 1 (sums) int64 [n_item], then the touched bitmap
+// one wave's slot of the scratch: kind 0 (counts) int32 [n_item]; kind 1 (sums) int64 [n_item], then the touched bitmap; the
+// weighted counts: int64 [n_item] (knn_acc_bytes(n_item, 1)) and no bitmap
 __host__ __device__ constexpr int64_t knn_acc_bytes(int64_t n_item, int kind) { return knn_pad256(n_item * (kind ? 8 : 4)); }
 __host__ __device__ constexpr int64_t knn_slot_bytes(int64_t n_item, int kind) {
     return knn_acc_bytes(n_item, kind) + (kind ? knn_pad256((n_item + 31) / 32 * 4) : 0);
@@ -182,6 +202,45 @@ __device__ __forceinline__ void cooc_walk(const int64_t* __restrict__ user_off, 
     }
 }
 
+// The weighted walk: f(valid, j, q) -- the walk above in which each entry comes with its user's weight in fixed point (the batch's
+// 64 values lie in w_q beside the starts) and a user that contributes nothing has a list of length 0: it deals no entry.  (A
+// sibling and not a parameter of cooc_walk, whose text stays what k_cooc_topk was compiled from.)
+template <class F>
+__device__ __forceinline__ void cooc_walk_weighted(const int64_t* __restrict__ user_off, const int32_t* __restrict__ user_items,
+                                                   const int32_t* __restrict__ users, int64_t lo, int64_t hi, int lane, long long* w_end,
+                                                   long long* w_base, const float* __restrict__ user_w, int frac_bits, long long* w_q,
+                                                   F&& f) {
+    for (int64_t b = lo; b < hi; b += 64) {
+        long long l0 = 0, len = 0, uq = 0;
+        if (b + lane < hi) {
+            const int64_t u = users[b + lane];
+            if (cooc_user_quant(user_w, u, frac_bits, &uq)) {
+                l0 = user_off[u];
+                len = user_off[u + 1] - l0;
+            }
+        }
+        const long long end = knn_scan(len, lane);        // entries of the batch up to and including this lane's list
+        knn_lds_order();
+        w_end[lane] = end;
+        w_base[lane] = l0 - (end - len);                  // entry t of the batch, if in this list, is user_items[w_base + t]
+        w_q[lane] = uq;
+        knn_lds_order();
+        const long long total = knn_readlane64(end, 63);
+        for (long long t0 = 0; t0 < total; t0 += 64) {
+            const long long t = t0 + lane;
+            const bool valid = t < total;
+            int j = -1;
+            long long q = 0;
+            if (valid) {
+                const int m = lower_bound(0, 63, [&](int c) { return w_end[c] <= t; });
+                j = user_items[w_base[m] + t];
+                q = w_q[m];
+            }
+            f(valid, j, q);
+        }
+    }
+}
+
 #endif
 
 // ---- neighbours of items ------------------------------------------------------------------------------------------------------
@@ -250,6 +309,88 @@ __global__ __launch_bounds__(64 * kKnnWaves) void k_cooc_topk(SmlCooc a, int pat
                 int c = 0;
                 if (valid) c = __hip_atomic_exchange(&acc[j], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 consume(c != 0, j, c);        // a non-zero count: this lane is the one that claimed j
+            });
+        }
+        top.write(lane, x, items, sims, n_elig);
+    }
+#endif
+}
+
+// ---- weighted neighbours of items: the kernel above with each user's unit replaced by its weight in fixed point ---------------
+// (a sibling and not a template parameter of k_cooc_topk, whose instructions stay as they are).  Static LDS: the two lists 2 KB
+// each, 16 KB of keys, 32 KB of sums, three per-wave arrays of 2 KB: 58 KB.
+__global__ __launch_bounds__(64 * kKnnWaves) void k_cooc_topk_weighted(SmlCoocWeighted a, int path, char* __restrict__ scratch,
+                                                                        int32_t* __restrict__ items, float* __restrict__ sims,
+                                                                        int32_t* __restrict__ n_elig) {
+#ifdef __HIP_DEVICE_COMPILE__
+    __shared__ float l_s[kKnnWaves][kKnnMaxK];
+    __shared__ int32_t l_i[kKnnWaves][kKnnMaxK];
+    __shared__ int32_t t_key[kKnnWaves][kKnnTabSlots];
+    __shared__ long long t_val[kKnnWaves][kKnnTabSlots];
+    __shared__ long long w_end[kKnnWaves][64];
+    __shared__ long long w_base[kKnnWaves][64];
+    __shared__ long long w_q[kKnnWaves][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int32_t* const keys = t_key[wave];
+    long long* const vals = t_val[wave];
+    for (int s = lane; s < kKnnTabSlots; s += 64) { keys[s] = -1; vals[s] = 0; }
+    knn_lds_order();
+    long long* const acc = reinterpret_cast<long long*>(scratch + ((int64_t)blockIdx.x * kKnnWaves + wave) * knn_acc_bytes(a.n_item, 1));
+    KnnList top;
+    top.ls = l_s[wave];
+    top.li = l_i[wave];
+    top.k = a.k;
+
+    for (int64_t x = (int64_t)blockIdx.x * kKnnWaves + wave; x < a.n; x += (int64_t)gridDim.x * kKnnWaves) {
+        const int64_t i = a.rows ? a.rows[x] : x;
+        const int64_t lo = a.item_off ? a.item_off[i] : 0, hi = a.item_off ? a.item_off[i + 1] : 0;
+        top.reset();
+        // the row's total list length over all its users, contributing or not: a bound on what the walk deals
+        bool lds = path != 1 && hi - lo <= kKnnLdsLimit;
+        if (lds) {
+            long long mine = 0;
+            for (int64_t e = lo + lane; e < hi; e += 64) {
+                const int64_t u = a.item_users[e];
+                mine += a.user_off[u + 1] - a.user_off[u];
+            }
+            lds = knn_wave_sum(mine) <= kKnnLdsLimit;
+        }
+        const auto consume = [&](bool have, int j, long long cw) {
+            bool elig = have && j != (int)i && knn_allowed(a.allow, j);
+            float s = 0.0f;
+            if (elig) {
+                s = cooc_score_weighted(cw, a.frac_bits, a.norm_a, a.norm_b, i, j, a.shrink);
+                elig = s == s;
+            }
+            top.offer(lane, elig, s, j);
+        };
+        const auto walk = [&](auto&& f) {
+            cooc_walk_weighted(a.user_off, a.user_items, a.item_users, lo, hi, lane, w_end[wave], w_base[wave], a.user_w, a.frac_bits,
+                               w_q[wave], f);
+        };
+        if (lds) {
+            walk([&](bool valid, int j, long long q) {
+                if (valid) knn_tab_add<long long>(keys, vals, j, q);
+            });
+            knn_lds_order();
+            for (int s0 = 0; s0 < kKnnTabSlots; s0 += 64) {
+                const int j = keys[s0 + lane];
+                const long long cw = vals[s0 + lane];
+                if (__ballot(j != -1) == 0) continue;
+                if (j != -1) { keys[s0 + lane] = -1; vals[s0 + lane] = 0; }
+                consume(j != -1, j, cw);
+            }
+            knn_lds_order();
+        } else {
+            walk([&](bool valid, int j, long long q) {
+                if (valid) __hip_atomic_fetch_add(&acc[j], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            });
+            __threadfence();                  // this wave's adds have landed before anything is claimed
+            walk([&](bool valid, int j, long long) {
+                long long cw = 0;
+                if (valid) cw = __hip_atomic_exchange(&acc[j], 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                consume(cw != 0, j, cw);      // every contribution is >= 1: a non-zero sum says this lane claimed j
             });
         }
         top.write(lane, x, items, sims, n_elig);
@@ -413,6 +554,19 @@ hipError_t sml_launch_cooc_topk(const SmlCooc& a, int max_workgroups, int path, 
     return hipGetLastError();
 }
 
+int64_t sml_cooc_weighted_scratch_size(int64_t n_item, int max_workgroups) {
+    return (max_workgroups > 0 ? (int64_t)max_workgroups : (int64_t)kKnnGrid) * kKnnWaves * knn_acc_bytes(n_item, 1);
+}
+
+hipError_t sml_launch_cooc_topk_weighted(const SmlCoocWeighted& a, int max_workgroups, int path, void* scratch, int32_t* items, float* sims,
+                                         int32_t* n_elig, hipStream_t st) {
+    const int64_t blocks = knn_blocks(a.n, max_workgroups);
+    const hipError_t e = hipMemsetAsync(scratch, 0, (size_t)(blocks * kKnnWaves * knn_acc_bytes(a.n_item, 1)), st);
+    if (e != hipSuccess) return e;
+    k_cooc_topk_weighted<<<dim3((unsigned)blocks), dim3(64 * kKnnWaves), 0, st>>>(a, path, static_cast<char*>(scratch), items, sims, n_elig);
+    return hipGetLastError();
+}
+
 hipError_t sml_launch_knn_topk(const SmlKnn& a, int max_workgroups, int path, void* scratch, int32_t* items, float* scores, int32_t* n_elig,
                                hipStream_t st) {
     const int64_t blocks = knn_blocks(a.n, max_workgroups);
@@ -444,6 +598,36 @@ void sml_cooc_host_walk(const SmlCooc& a, int32_t* items, float* sims, int32_t* 
             count[j] = 0;
             if (j == (int32_t)i || c < a.min_co || !knn_allowed(a.allow, j)) continue;
             const float s = cooc_score(c, a.norm_a, a.norm_b, i, j, a.shrink);
+            if (s == s) cand.emplace_back(s, j);
+        }
+        knn_host_emit(cand, a.k, items + x * a.k, sims + x * a.k, n_elig ? n_elig + x : nullptr);
+    }
+}
+
+void sml_cooc_weighted_host_walk(const SmlCoocWeighted& a, int32_t* items, float* sims, int32_t* n_elig) {
+    std::vector<long long> cw((size_t)a.n_item, 0);
+    std::vector<int32_t> seen_ids;
+    std::vector<std::pair<float, int32_t>> cand;
+    for (int64_t x = 0; x < a.n; ++x) {
+        const int64_t i = a.rows ? a.rows[x] : x;
+        const int64_t lo = a.item_off ? a.item_off[i] : 0, hi = a.item_off ? a.item_off[i + 1] : 0;
+        seen_ids.clear();
+        cand.clear();
+        for (int64_t e = lo; e < hi; ++e) {
+            const int64_t u = a.item_users[e];
+            long long q;
+            if (!cooc_user_quant(a.user_w, u, a.frac_bits, &q)) continue;
+            for (int64_t p = a.user_off[u]; p < a.user_off[u + 1]; ++p) {
+                const int32_t j = a.user_items[p];
+                if (cw[j] == 0) seen_ids.push_back(j);        // every q is >= 1: touched <=> non-zero
+                cw[j] += q;
+            }
+        }
+        for (const int32_t j : seen_ids) {
+            const long long sum = cw[j];
+            cw[j] = 0;
+            if (j == (int32_t)i || !knn_allowed(a.allow, j)) continue;
+            const float s = cooc_score_weighted(sum, a.frac_bits, a.norm_a, a.norm_b, i, j, a.shrink);
             if (s == s) cand.emplace_back(s, j);
         }
         knn_host_emit(cand, a.k, items + x * a.k, sims + x * a.k, n_elig ? n_elig + x : nullptr);

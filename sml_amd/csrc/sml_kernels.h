@@ -508,6 +508,23 @@ struct SmlCooc {
     const uint32_t* allow;
     int k;
 };
+// the weighted neighbours of items: SmlCooc without min_co, with the users' weights and their fixed point
+struct SmlCoocWeighted {
+    const int64_t* item_off;
+    const int32_t* item_users;
+    const int64_t* user_off;
+    const int32_t* user_items;
+    int64_t n_user, n_item;
+    const int64_t* rows;
+    int64_t n;
+    const float* user_w;
+    int frac_bits;
+    const double* norm_a;
+    const double* norm_b;
+    double shrink;
+    const uint32_t* allow;
+    int k;
+};
 struct SmlKnn {
     const int32_t* nbr_items;
     const float* nbr_sims;
@@ -531,6 +548,10 @@ hipError_t sml_launch_cooc_topk(const SmlCooc& a, int max_workgroups, int path, 
 hipError_t sml_launch_knn_topk(const SmlKnn& a, int max_workgroups, int path, void* scratch, int32_t* items, float* scores, int32_t* n_elig,
                                hipStream_t st);
 void sml_cooc_host_walk(const SmlCooc& a, int32_t* items, float* sims, int32_t* n_elig);
+int64_t sml_cooc_weighted_scratch_size(int64_t n_item, int max_workgroups);
+hipError_t sml_launch_cooc_topk_weighted(const SmlCoocWeighted& a, int max_workgroups, int path, void* scratch, int32_t* items, float* sims,
+                                         int32_t* n_elig, hipStream_t st);
+void sml_cooc_weighted_host_walk(const SmlCoocWeighted& a, int32_t* items, float* sims, int32_t* n_elig);
 void sml_knn_host_walk(const SmlKnn& a, int32_t* items, float* scores, int32_t* n_elig);
 // deep lists (sml_topk_deep, include/sml_hip.h): 1 <= k <= 1024 by a per-user radix select, a fixed number of catalogue walks
 // whatever k is; slices 0 = the planner's, 1 .. 256 forced.  scratch: sml_topk_deep_scratch_size bytes.  No allocation, copy to

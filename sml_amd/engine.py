@@ -1142,15 +1142,20 @@ class HipEngine(object):
         return int(self.lib.sml_knn_lds_limit())
 
     def _knn_scratch(self, n_item, n, max_workgroups, kind):
-        """(scratch, max_workgroups) of a call over n rows.  With the grid left to the call, a call of few rows asks for n
-        workgroups when that makes the scratch smaller: a row never needs more than one, and the grid never changes a byte."""
+        """(scratch, max_workgroups) of a call over n rows; kind 0 / 1 as sml_knn_scratch_bytes takes it, "weighted" for
+        sml_cooc_weighted_scratch_bytes.  With the grid left to the call, a call of few rows asks for n workgroups when that makes
+        the scratch smaller: a row never needs more than one, and the grid never changes a byte."""
+        if kind == "weighted":
+            what, size = "sml_cooc_weighted_scratch_bytes", lambda w: self.lib.sml_cooc_weighted_scratch_bytes(self._ctx, int(n_item), w)
+        else:
+            what, size = "sml_knn_scratch_bytes", lambda w: self.lib.sml_knn_scratch_bytes(self._ctx, int(n_item), w, kind)
         mw = int(max_workgroups)
-        nbytes = self.lib.sml_knn_scratch_bytes(self._ctx, int(n_item), mw, kind)
+        nbytes = size(mw)
         if mw == 0 and n > 0 and nbytes > 0:
-            fewer = self.lib.sml_knn_scratch_bytes(self._ctx, int(n_item), int(n), kind)
+            fewer = size(int(n))
             if 0 < fewer < nbytes:
                 mw, nbytes = int(n), fewer
-        return self._scratch(nbytes, "sml_knn_scratch_bytes"), mw
+        return self._scratch(nbytes, what), mw
 
     def _list_out(self, n, k):
         """The (items int32 [n, k], scores float32 [n, k], n_elig int32 [n]) outputs of a list-producing call."""
@@ -1185,6 +1190,38 @@ class HipEngine(object):
         check(self.lib.sml_cooc_topk(self._ctx, _ptr(i_off), _ptr(i_users), _ptr(u_off), _ptr(u_items), n_user, n_item, _ptr(rows), n,
                                      _ptr(na), _ptr(nb), float(shrink), int(min_co), _ptr(allow), k, mw, int(path),
                                      _ptr(scratch), _ptr(items), _ptr(sims), _ptr(n_elig), self._stream()), "sml_cooc_topk")
+        return items.long(), sims, n_elig
+
+    def cooc_topk_weighted(self, by_item, by_user, k, user_w, frac_bits=30, rows=None, norm=None, shrink=0.0, allow=None,
+                           max_workgroups=0, path=0):
+        """cooc_topk with users that do not count equally (include/sml_hip.h, WEIGHTED NEIGHBOURS OF ITEMS; sml_cooc_topk_weighted):
+        sim = (sum over the common users of user_w[u]) / (a[i] * b[j] + shrink), the sum taken in fixed point with frac_bits
+        fractional bits by integer atomics.  user_w: a contiguous float32 [n_user] tensor on the engine's device; a user whose
+        weight is not finite, not positive, rounds to 0 or exceeds 2^32 in fixed point contributes nothing.  There is no min_co.
+        Everything else as in cooc_topk.  No read-back."""
+        i_off, i_users = self._seen(by_item)
+        u_off, u_items = self._seen(by_user)
+        n_item, n_user = i_off.shape[0] - 1, u_off.shape[0] - 1
+        if not torch.is_tensor(user_w) or user_w.dtype != torch.float32 or user_w.device != self.device or not user_w.is_contiguous() \
+                or tuple(user_w.shape) != (n_user,):
+            raise ValueError("cooc_topk_weighted: user_w is a contiguous float32 [%d] tensor on %s" % (n_user, self.device))
+        allow = self._allow(allow, n_item)
+        if norm is None:
+            na = nb = None
+        else:
+            na, nb = norm if isinstance(norm, (tuple, list)) else (norm, norm)
+            for t in (na, nb):
+                if t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n_item,):
+                    raise ValueError("cooc_topk_weighted: a norm table is a contiguous float64 [%d] tensor on %s" % (n_item, self.device))
+        if rows is not None:
+            rows = self._dev(rows, torch.int64).reshape(-1)
+        n, k = n_item if rows is None else rows.shape[0], int(k)
+        scratch, mw = self._knn_scratch(n_item, n, max_workgroups, "weighted")
+        items, sims, n_elig = self._list_out(n, k)
+        check(self.lib.sml_cooc_topk_weighted(self._ctx, _ptr(i_off), _ptr(i_users), _ptr(u_off), _ptr(u_items), n_user, n_item,
+                                              _ptr(rows), n, _ptr(user_w), int(frac_bits), _ptr(na), _ptr(nb), float(shrink),
+                                              _ptr(allow), k, mw, int(path), _ptr(scratch), _ptr(items), _ptr(sims), _ptr(n_elig),
+                                              self._stream()), "sml_cooc_topk_weighted")
         return items.long(), sims, n_elig
 
     def knn_topk(self, nbr_items, nbr_sims, n_item, history, k, users=None, frac_bits=30, seen=None, allow=None, max_workgroups=0,

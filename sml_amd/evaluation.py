@@ -210,6 +210,22 @@ def recall_of_lists(lists, users, held_out, ks):
     return [float(np.mean(hits[:, k].astype(np.float64) / m.astype(np.float64))) for k in ks]
 
 
+def popularity_of_lists(lists, item_count):
+    """{"mean_count", "coverage"} of lists that are given: lists int [n, K] (a tensor or an array; -1 pads a short list),
+    item_count [n_item] the interaction count of every item.  mean_count: the mean of item_count over the listed slots (a listed
+    item counts once per slot it fills; 0.0 when nothing is listed); coverage: the share of the catalogue that appears in some
+    list.  Together they show what a popularity penalty (the beta of rp3beta) did to the lists.  Plain torch on the lists'
+    device, float64."""
+    lists = torch.as_tensor(lists).long()
+    count = torch.as_tensor(item_count).to(device=lists.device, dtype=torch.float64).reshape(-1)
+    if lists.dim() != 2 or (lists.numel() and int(lists.max()) >= count.shape[0]):
+        raise ValueError("popularity_of_lists: lists is [n, K] with ids below len(item_count) = %d, got %s" % (count.shape[0], tuple(lists.shape)))
+    listed = lists[lists >= 0]
+    if listed.numel() == 0:
+        return {"mean_count": 0.0, "coverage": 0.0}
+    return {"mean_count": float(count[listed].mean()), "coverage": float(torch.unique(listed).numel()) / float(count.shape[0])}
+
+
 def index_recall(model, index, users, topK=20, nprobe=None, exclude=None):
     """What the approximation of MFbasemode.recommend(index=) costs: the mean over `users` of
     |indexed list AND exact list| / (number of live slots of the exact list), the two lists being recommend(users, topK,
